@@ -122,6 +122,19 @@ def night_env():
     return _night[0]
 
 
+def build_in_tree(build_all, *builders):
+    """Run a build entry: it takes a lock file in the tree, then rebuilds whatever is stale.  In a tree this user cannot write to (one that
+    build() made as another user) the lock cannot be created; the per-library builders then run without it.  They write only when a source
+    is newer than its library, so an up-to-date tree runs as it is and a stale one still fails loudly."""
+    import errno
+    try:
+        return build_all()
+    except OSError as e:
+        if e.errno not in (errno.EACCES, errno.EPERM, errno.EROFS):
+            raise
+        return [f() for f in builders]
+
+
 def step_async(ctx):
     ctx.wf_logic(False)
     ctx.wf_raygen()
@@ -129,6 +142,55 @@ def step_async(ctx):
     ctx.wf_extend()
     ctx.wf_shadow()
     ctx.end_iteration_async()
+
+
+DUMP_BUDGET_BYTES = 60 << 20         # (< 64 MB however a megabyte is counted)
+DUMP_SEED = 1234
+DUMP_STATE_PATHS = 1 << 15
+
+
+def _state_int_cols():
+    """Columns of the path state (flx_state_export layout) that hold integers, not floats; the seed is unsigned."""
+    from fluctus_amd.wire import COL
+    return (COL.PHASE, COL.PATH_LEN, COL.LAST_SPECULAR, COL.SHADOW_BLOCKED, COL.BACKFACE, COL.PIXEL_INDEX, COL.FIRST_DIFFUSE,
+            COL.HIT_I, COL.AREA_LIGHT_HIT, COL.MAT_ID), COL.SEED
+
+
+def dump_outputs(out_dir, ctxs, counters):
+    """--dump-outputs: what the timed steps computed, read back right after the last of them (before any untimed pass), for comparing two builds
+    output for output (same arguments = same inputs).  Files, all float32 / float64, <= DUMP_BUDGET_BYTES together:
+      pixels.npy            (P, 4) float32: the accumulation image (rgb sum, sample count; flx_read_pixels 0) of this rank's pixels in partition order
+                            -- every pixel, or, when they would not fit, a fixed seeded sample whose positions are in pixels_index.npy (float64)
+      queue_counters.npy    (8,) float64: the queue-counter totals of all timed steps (flx_queue_counters order)
+      path_state.npy        (64, S) float64: the path state (flx_state_export layout) of a fixed seeded sample of S paths of the first wavefront,
+                            integer columns as their values (the float32 state keeps them as bit patterns), ids in path_state_index.npy (float64)
+    Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {"queue_counters": np.asarray(counters, np.float64)}
+    n = ctxs[0].num_tasks
+    ids = np.arange(n) if n <= DUMP_STATE_PATHS else np.sort(rng.choice(n, DUMP_STATE_PATHS, replace=False))
+    st = np.ascontiguousarray(ctxs[0].state_export()[:, ids])
+    state = st.astype(np.float64)
+    int_cols, seed_col = _state_int_cols()
+    for c in int_cols:
+        state[c] = st[c].view(np.int32)
+    state[seed_col] = st[seed_col].view(np.uint32)
+    out["path_state"] = state
+    out["path_state_index"] = ids.astype(np.float64)
+    tiles = [c_.read_pixels(0) for c_ in ctxs]
+    pix = np.empty((sum(t.shape[0] for t in tiles), 4), np.float32)
+    for i, t in enumerate(tiles):
+        pix[i::len(tiles)] = t                      # wavefront i of a rank holds every len(ctxs)-th of the rank's pixels
+    room = DUMP_BUDGET_BYTES - sum(a.nbytes for a in out.values()) - (1 << 16)
+    if pix.nbytes > room:
+        keep = np.sort(rng.choice(pix.shape[0], room // (pix.itemsize * 4 + 8), replace=False))
+        out["pixels_index"] = keep.astype(np.float64)
+        pix = pix[keep]
+    out["pixels"] = pix
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
 
 
 def algorithmic_bytes(stats):
@@ -173,7 +235,7 @@ def cpu_baseline(d, p, env, budget_s=12.0, force_kind=None):
     OpenCL device schedules work-groups.  kind "port" (fallback when that library is absent): oracle/wf_oracle.cpp."""
     from fluctus_amd import driver
     from oracle import build as oracle_build
-    oracle_build.build_all()
+    build_in_tree(oracle_build.build_all, oracle_build.build_oracle, oracle_build.build_ref)
     from oracle.binding import OracleContext, RefContext, ref_available
     cores = usable_cores()
     n = 1 << 16
@@ -318,9 +380,13 @@ def ref_gpu_baseline(ctx, d, p, env, args, settle):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=60)
+    ap.add_argument("--steps", type=int, default=60, help="timed steps in all (split over --windows)")
     ap.add_argument("--warmup", type=int, default=24)
-    ap.add_argument("--windows", type=int, default=5, help="back-to-back timed windows of --steps steps each; the headline is the MEDIAN window (all of them are in the line)")
+    ap.add_argument("--windows", type=int, default=1, help="back-to-back timed windows the --steps steps are split into (at most one per step), each drained before the next "
+                                                            "starts; the headline covers all of them, each window's rate is in the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float32 / float64, under 64 MB in all): the accumulation image, "
+                         "the queue-counter totals of the timed steps and a fixed sample of the path state (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ref-gpu-baseline", action="store_true", help="skip the untimed leg that runs the reference's own gfx950 kernels on this GPU (ref_gpu_baseline)")
     ap.add_argument("--width", type=int, default=None)
@@ -346,11 +412,14 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"), help="multi-GPU: weak = every rank runs --num-tasks paths of its own (default, the driver's SCALE runs); strong = the paths in flight are fixed: --num-tasks // world per rank (the framebuffer is fixed either way: north_star's tile split)")
     ap.add_argument("--kernel-timing", type=int, default=4, help="HIP-event timing inside the timed region: 0 none, 1 every kernel, 2 the trace kernels + span, 3 the extension kernel only, 4 the three kernels of the roofline block (extension, logic, shadow)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
     import __graft_entry__ as entry
-    entry.build_product()             # the checker (oracle/) is built by cpu_baseline(), the only leg that uses it
+    from fluctus_amd import build as product_build
+    build_in_tree(entry.build_product, product_build.build_hip, product_build.build_host)     # the checker (oracle/) is built by cpu_baseline(), the only leg that uses it
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -452,15 +521,17 @@ def main():
     ctx.profile_reset()
     ctx.profile_enable(args.kernel_timing)
 
-    # `--windows` back-to-back windows of EXACTLY --steps steps, each bracketed by barrier + synchronize on both sides; a window is
-    # ~0.1 s of GPU time, one sample of it moves by a few per cent from run to run, so the headline is the median window
-    nwin = max(1, args.windows)
+    # EXACTLY --steps timed steps, split into `--windows` back-to-back windows (sizes differ by at most one step), each bracketed by
+    # barrier + synchronize on both sides.  The headline covers every timed step; the per-window rates show the spread.  Every window
+    # boundary drains the device (~0.1 ms on the kitchen line), so the default is one window: the timed steps run back to back.
+    nwin = max(1, min(args.windows, args.steps))
+    win_steps = [args.steps // nwin + (1 if w_ < args.steps % nwin else 0) for w_ in range(nwin)]
     win_elapsed, win_tot = [], []
-    for _w in range(nwin):
+    for ns in win_steps:
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(ns):
             step_async(ctx)
         ctx.finish()
         torch.cuda.synchronize()
@@ -469,6 +540,7 @@ def main():
         win_elapsed.append(t1 - t0)
         win_tot.append(np.array(ctx.counter_totals(reset=True), dtype=np.float64))
     ctx.profile_enable(False)
+    dumped = dump_outputs(args.dump_outputs, ctxs, np.sum(win_tot, axis=0)) if (args.dump_outputs and rank == 0) else None
 
     tot = np.sum(win_tot, axis=0)                     # all windows: what the event-timed kernel averages cover
     prof = ctx.profile_get()
@@ -504,12 +576,10 @@ def main():
         dist.all_reduce(tr, op=dist.ReduceOp.SUM)
         wins = np.concatenate([te.cpu().numpy()[:, None], tr.cpu().numpy()], axis=1)
     win_mrays = (wins[:, 2] + wins[:, 3]) / wins[:, 0] / 1e6
-    order = np.argsort(win_mrays)
-    med = int(order[len(order) // 2]) if len(order) % 2 else int(order[len(order) // 2 - 1])      # (even count: the lower middle window -- a measured one)
-    elapsed = float(wins[med, 0])
-    prim, ext, sh = float(wins[med, 1]), float(wins[med, 2]), float(wins[med, 3])
+    elapsed = float(wins[:, 0].sum())                  # all timed steps
+    prim, ext, sh = float(wins[:, 1].sum()), float(wins[:, 2].sum()), float(wins[:, 3].sum())
     rays_total = ext + sh
-    ext_all = float(wins[:, 2].sum())                  # extension rays of all windows and ranks
+    ext_all = ext                                      # extension rays of all windows and ranks
 
     # ---- roofline of the dominant kernel (traceExtension): algorithmic bytes / HIP-event time
     # visit counts come from an UNTIMED pass of the counting kernel variants over the same steady state
@@ -550,14 +620,14 @@ def main():
         own_bytes_per_ray = (84 * st_own["ext_rays"] + 64 * st_own["ext_inner"] + 32 * own_leaf["ext_leaf"] + 48 * st_own["ext_tri"]
                              + 64 * st_own["ext_hits"]) / max(1, st_own["ext_rays"])
     ext_ms, ext_n = prof["extend"]
-    rays_per_launch = ext_all / world / C / max(1, args.steps * nwin)
+    rays_per_launch = ext_all / world / C / args.steps
     achieved = (bytes_per_ext_ray * rays_per_launch) / (ext_ms / max(1, ext_n) * 1e-3) / 1e9 if ext_ms > 0 else 0.0
     # k_extend shares the machine with the concurrent k_shadow; the pair's span gives the combined traversal rate
     span_ms, span_n = prof.get("trace_span", (0.0, 0))
     bytes_per_sh_ray = sh_bytes / max(1, st["shadow_rays"])
     combined = None
     if span_n:
-        combined_bytes = bytes_per_ext_ray * rays_per_launch + bytes_per_sh_ray * (float(wins[:, 3].sum()) / world / C / max(1, args.steps * nwin))
+        combined_bytes = bytes_per_ext_ray * rays_per_launch + bytes_per_sh_ray * (float(wins[:, 3].sum()) / world / C / args.steps)
         combined = combined_bytes / (span_ms / span_n * 1e-3) / 1e9
     # fabric-side bytes of the extension kernel per launch, from the committed PMC capture of THIS workload (profiles/traffic_<workload>.json,
     # written by scripts/profile_round.sh: separate --pmc passes, request counters by size = 2 x FETCH_SIZE + WRITE_SIZE with the guide's gfx950
@@ -777,8 +847,9 @@ def main():
             "unit": "Mrays/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_iterations": settle,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "windows": {"count": nwin, "headline": "median window", "Mrays_s": [float(x) for x in win_mrays], "ms_per_step": [float(e / args.steps * 1e3) for e in wins[:, 0]],
-                        "spread_pct": float((win_mrays.max() - win_mrays.min()) / win_mrays[med] * 100.0)},
+            "windows": {"count": nwin, "headline": "all timed steps", "steps": win_steps, "Mrays_s": [float(x) for x in win_mrays],
+                        "ms_per_step": [float(e / n_ * 1e3) for e, n_ in zip(wins[:, 0], win_steps)],
+                        "spread_pct": float((win_mrays.max() - win_mrays.min()) / (rays_total / elapsed / 1e6) * 100.0)},
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": "f32", "data": ("real (reference asset egyptcat.obj + .mtl + texture)" if args.workload == "egyptcat" else
                                      "synthetic (procedural scene, deterministic); environment map: the reference's assets/env_maps/night.hdr" if int(p["useEnvMap"]) else "synthetic (procedural scene, deterministic)"),
@@ -795,6 +866,8 @@ def main():
             "kernel_ms_avg_source": {"timed_region": sorted(k for k, v in prof.items() if v[1] and k not in untimed), "extra_untimed_pass": sorted(untimed)},
             "roofline": roofline,
         }
+        if dumped:
+            line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": [n_ + ".npy" for n_ in dumped]}
         if gather_ms is not None:
             line["gather_ms"] = gather_ms
             line["gather_matches_read_pixels"] = gather_ok

@@ -5,7 +5,6 @@ from fluctus_amd import host, wire, driver
 from fluctus_amd.wire import COL, Q, BXDF
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF_ASSETS = "/root/reference/assets"
 
 # integer-typed columns of the reference state layout (everything else is float)
 INT_COLS = [COL.PHASE, COL.PATH_LEN, COL.SEED, COL.LAST_SPECULAR, COL.SHADOW_BLOCKED, COL.BACKFACE, COL.PIXEL_INDEX,
@@ -149,6 +148,18 @@ def fixture_scene(z):
     if "nodes" in z.files:
         d.nodes = z["nodes"].view(wire.NODE).reshape(-1)
         d.indices = z["indices"]
+    return d
+
+
+def teapot_scene():
+    """The triangles and material of the reference's assets/teapot.ply as loaded by host/scene.cpp (stored in tests/golden/teapot_wf.npz by
+    scripts/make_golden.py), without a hierarchy: the caller builds the one it needs."""
+    z = np.load(os.path.join(GOLDEN, "teapot_wf.npz"))
+    d = host.SceneData()
+    d.tris = z["tris"].view(wire.TRIANGLE).reshape(-1)
+    d.materials = z["materials"].view(wire.MATERIAL).reshape(-1)
+    d.texdesc = np.zeros(0, wire.TEXDESC)
+    d.texdata = np.zeros(0, np.uint8)
     return d
 
 

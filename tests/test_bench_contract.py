@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +12,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_json_line_contract(tmp_path):
     env = dict(os.environ, FLX_BENCH_TRIS="30000", FLX_BVH_CACHE=str(tmp_path))
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "3", "--num-tasks", "262144"],
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "3", "--num-tasks", "262144",
+                          "--windows", "5", "--dump-outputs", str(dump)],
                          env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -38,10 +41,12 @@ def test_bench_json_line_contract(tmp_path):
     for k, o in r["other_kernels"].items():
         assert o["launch_ms"] > 0 and o["timed"] == "timed region" and o["hbm"]["frac"] is None and o["valu"] is None, (k, o)
     assert "shadow_split" in r["capture_key"] and r["capture_key"]["library"] == "libfluctus_hip.so" and "gfx950" in r["capture_key"]["build_flags"]
-    # protocol: settle >= 2 * maxBounces + 2 whatever --warmup says, five windows, headline = the median one
+    # protocol: settle >= 2 * maxBounces + 2 whatever --warmup says; EXACTLY --steps timed steps, split into five windows; the headline covers them all
     assert j["settle_iterations"] >= 2 * j["config"]["max_bounces"] + 2 and j["settle_iterations"] >= j["warmup"]
     w = j["windows"]
-    assert w["count"] == 5 and len(w["Mrays_s"]) == 5 and sorted(w["Mrays_s"])[2] == pytest.approx(j["value"], rel=1e-9)
+    assert w["count"] == 5 and len(w["Mrays_s"]) == 5 and w["steps"] == [2, 1, 1, 1, 1] and sum(w["steps"]) == j["steps"]
+    assert sum(m * n for m, n in zip(w["ms_per_step"], w["steps"])) == pytest.approx(j["ms_per_step"] * j["steps"], rel=1e-9)
+    assert min(w["Mrays_s"]) * (1 - 1e-9) <= j["value"] <= max(w["Mrays_s"]) * (1 + 1e-9)
     assert "extend" in j["kernel_ms_avg_source"]["timed_region"]    # the roofline kernel is event-timed inside the timed region
     c = j["cpu_baseline"]
     for k in ("value", "unit", "cores", "kind", "sample"):
@@ -50,3 +55,13 @@ def test_bench_json_line_contract(tmp_path):
     # whole-job throughput = rays of the timed steps / time
     rays = j["rays"]["extension"] + j["rays"]["shadow"]
     assert abs(j["value"] - rays / (j["ms_per_step"] * 1e-3 * j["steps"]) / 1e6) <= 1e-6 * j["value"]
+    # --dump-outputs: what the timed steps computed, float32 / float64 only, under 64 MB together
+    files = sorted(os.listdir(dump))
+    assert files == sorted(j["dump_outputs"]["files"]) == ["path_state.npy", "path_state_index.npy", "pixels.npy", "queue_counters.npy"]
+    assert sum(os.path.getsize(dump / f) for f in files) < 64e6
+    a = {f[:-len(".npy")]: np.load(dump / f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["pixels"].shape == (j["config"]["width"] * j["config"]["height"], 4) and np.isfinite(a["pixels"]).all() and a["pixels"][:, 3].sum() > 0
+    assert a["path_state"].shape == (64, 32768) and a["path_state_index"].shape == (32768,) and np.isfinite(a["path_state"][61]).all()
+    # the queue-counter totals of the timed steps are the rays the line counts
+    assert a["queue_counters"][1] == j["rays"]["extension"] and a["queue_counters"][2] == j["rays"]["shadow"]

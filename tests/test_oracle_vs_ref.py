@@ -74,8 +74,8 @@ def _iterate(a, b, npix, iters, rtol=RTOL, atol=ATOL, mat_rtol=None):
 
 
 def test_teapot_area_light_single_queue():
-    """Config 1 of BASELINE.json: teapot.ply, Lambertian, area light, 4 bounces."""
-    d = host.load_scene(common.REF_ASSETS + "/teapot.ply")
+    """Config 1 of BASELINE.json: teapot.ply (as loaded into tests/golden/teapot_wf.npz), Lambertian, area light, 4 bounces."""
+    d = common.teapot_scene()
     host.build_bvh(d, "sbvh")
     w = h = 96
     p = wire.default_params(w, h, d.world_radius, d.tris.size)
@@ -132,10 +132,9 @@ def test_first_frame_preview_path():
 
 
 def test_egyptcat_real_asset_textured_glossy():
-    """A real reference asset end to end through the loaders: egyptcat.obj + .mtl (`shader glossy`, Ns 100000) +
+    """A real reference asset as the loaders read it (tests/golden/egyptcat_scene.npz): egyptcat.obj + .mtl (`shader glossy`, Ns 100000) +
     EgyptCat.png (1024^2 diffuse texture), area light, single material queue."""
-    d = host.load_scene(common.REF_ASSETS + "/egyptcat/egyptcat.obj")
-    host.build_bvh(d, "sbvh")
+    d = common.egyptcat_scene()
     assert d.texdesc.size == 1
     w, h, n = 64, 48, 4096
     p = wire.default_params(w, h, d.world_radius, d.tris.size)
