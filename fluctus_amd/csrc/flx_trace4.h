@@ -9,8 +9,11 @@
 // wide test passes whenever the reference's passes (same three conditions: tfar >= 0, tnear <= tfar, tnear < tMax).
 // dinv is clamped to +-2^100 for this test only (a zero direction component gives +-inf and 0 * inf = NaN planes that would
 // switch the axis off and let an axis-parallel ray wander through the whole slab of the scene); e, which grows with |sd|,
-// covers the boundary cases of that substitution.  Near / far planes are picked per axis by the sign of the direction with
-// one v_cndmask on the packed bytes of all four children.
+// covers the boundary cases of that substitution.  The test runs on the direction scaled by a power of two to a largest
+// component in [1, 2) (t' = t * tsc, exact): the clamp then only replaces the inverse of a component that is tiny RELATIVE to
+// the others, whatever the length of the direction (unscaled, a direction shorter than 2^-64 had every axis clamped, its
+// planes scaled differently from its tMax, and nodes the reference enters culled).  Near / far planes are picked per axis by
+// the sign of the direction with one v_cndmask on the packed bytes of all four children.
 //
 // Leaf test: the leaf's exact fp32 box with the reference's arithmetic (slab(), the UNclamped 1/dir), then its triangles in
 // index-list order with the same Moller-Trumbore as the binary path.
@@ -76,7 +79,8 @@ __device__ __forceinline__ float min3_(float a, float b, float c) { return __bui
 // Per-ray constants of the wide traversal
 struct WRay {
     f3 orig, dir, dinv;            // dinv = the reference's native_recip(dir) (exact, may be +-inf): leaf boxes
-    float dwx, dwy, dwz;           // dinv clamped to +-2^100: node test
+    float dwx, dwy, dwz;           // node test: 1 / (dir * 2^-E), clamped to +-2^100; 2^E <= max |dir| < 2^(E+1)
+    float tsc;                     // 2^E: a distance t along dir is t * tsc in the node test's units
     bool negx, negy, negz;
     __device__ __forceinline__ void setup(f3 o, f3 d, float clampNear)
     {
@@ -90,9 +94,13 @@ struct WRay {
         // distance of the other axes, header comment; 2^64 still does for nodes larger than 2^-37 of the scene.)
         const float far = fmaxf_(fmaxf_(absf(o.x), absf(o.y)), absf(o.z));
         const float lim = far < 67108864.0f ? clampNear : FLX_WIDE_DINV_FAR;
-        dwx = fminf_(fmaxf_(dinv.x, -lim), lim);
-        dwy = fminf_(fmaxf_(dinv.y, -lim), lim);
-        dwz = fminf_(fmaxf_(dinv.z, -lim), lim);
+        // biased exponent of the largest component, kept where 2^-E and 2^E are both normal numbers
+        const int eb = min(max((int)(__float_as_uint(fmaxf_(fmaxf_(absf(d.x), absf(d.y)), absf(d.z))) >> 23), 1), 253);
+        const float p = __uint_as_float((uint32_t)(254 - eb) << 23);          // 2^-E
+        tsc = __uint_as_float((uint32_t)eb << 23);                             // 2^E
+        dwx = fminf_(fmaxf_(1.0f / (d.x * p), -lim), lim);
+        dwy = fminf_(fmaxf_(1.0f / (d.y * p), -lim), lim);
+        dwz = fminf_(fmaxf_(1.0f / (d.z * p), -lim), lim);
         negx = (__float_as_uint(dwx) >> 31) != 0u; negy = (__float_as_uint(dwy) >> 31) != 0u; negz = (__float_as_uint(dwz) >> 31) != 0u;
     }
 };
@@ -111,6 +119,7 @@ __device__ __forceinline__ void wide_node_visit(const float4 *wn, WStack &stk, c
 {
     const float4 *np = wn + (size_t)cur * 4;
     const float4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
+    const float tb = tbest * r.tsc;                                        // tMax in the node test's units (WRay::setup)
     // per-axis slope / offset of t(q) = q * sd + od, and the conservative shift e (header comment)
     const float sdx = n0.w * r.dwx, sdy = n1.x * r.dwy, sdz = n1.y * r.dwz;
     const float odx = (n0.x - r.orig.x) * r.dwx, ody = (n0.y - r.orig.y) * r.dwy, odz = (n0.z - r.orig.z) * r.dwz;
@@ -129,7 +138,7 @@ __device__ __forceinline__ void wide_node_visit(const float4 *wn, WStack &stk, c
 #define FLX_CHILD(UB, KEY, HIT) \
     { const float tn = max3_(fma_(UB(qnx), sdx, onx), fma_(UB(qny), sdy, ony), fma_(UB(qnz), sdz, onz)); \
       const float tf = min3_(fma_(UB(qfx), sdx, ofx), fma_(UB(qfy), sdy, ofy), fma_(UB(qfz), sdz, ofz)); \
-      HIT = (tn <= tf) && (tf >= 0.0f) && (tn < tbest); KEY = tn; }
+      HIT = (tn <= tf) && (tf >= 0.0f) && (tn < tb); KEY = tn; }
     float k0, k1, k2, k3; bool h0, h1, h2, h3;
     FLX_CHILD(ub0, k0, h0)
     FLX_CHILD(ub1, k1, h1)

@@ -189,6 +189,17 @@ struct SbvhBuilder {
     // reference: src/sbvh.cpp:225-241
     void partitionObject(Spec &L, Spec &R, const Spec &s, const Split &sp)
     {
+        if (sp.dim < 0) {
+            // no split had a finite SAH cost: the fp32 box areas overflow once coordinates pass ~2^61 (the wide tree accepts up to 2^62).
+            // Halve the references along the longest axis instead; below that size the SAH takes over again.
+            int dim = 0;
+            for (int k = 1; k < 3; k++) if (s.box.mx[k] - s.box.mn[k] > s.box.mx[dim] - s.box.mn[dim]) dim = k;
+            const size_t start = refs.size() - s.refs;
+            sortRefs(refs, start, refs.size() - 1, dim, par);
+            L.refs = s.refs / 2; R.refs = s.refs - L.refs; L.box = Box(); R.box = Box();
+            for (int i = 0; i < s.refs; i++) (i < L.refs ? L.box : R.box).expand(refs[start + i].box);
+            return;
+        }
         sortRefs(refs, refs.size() - s.refs, refs.size() - 1, sp.dim, par);
         L.refs = sp.i; L.box = sp.left; R.refs = s.refs - sp.i; R.box = sp.right;
     }
@@ -238,7 +249,7 @@ struct SbvhBuilder {
         float minCost = std::min(obj.cost, std::min(spatial.cost, parentCost));
         if (minCost == parentCost && s.refs <= MaxLeaf) return leaf(s);
         Spec L, R;
-        if (minCost == spatial.cost) { partitionSpatial(L, R, s, spatial); if (L.refs && R.refs) spatialSplits++; }
+        if (spatial.dim >= 0 && minCost == spatial.cost) { partitionSpatial(L, R, s, spatial); if (L.refs && R.refs) spatialSplits++; }
         if (!L.refs || !R.refs) partitionObject(L, R, s, obj);
         splits++;
         duplicates += (uint32_t)(L.refs + R.refs - s.refs);
@@ -280,7 +291,7 @@ struct SbvhBuilder {
         float minCost = std::min(obj.cost, std::min(spatial.cost, parentCost));
         if (minCost == parentCost && s.refs <= MaxLeaf) { par = false; return leaf(s); }
         Spec L, R;
-        if (minCost == spatial.cost) { partitionSpatial(L, R, s, spatial); if (L.refs && R.refs) spatialSplits++; }
+        if (spatial.dim >= 0 && minCost == spatial.cost) { partitionSpatial(L, R, s, spatial); if (L.refs && R.refs) spatialSplits++; }
         if (!L.refs || !R.refs) partitionObject(L, R, s, obj);
         par = false;
         splits++;

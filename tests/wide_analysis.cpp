@@ -100,8 +100,14 @@ int fh_wide_visits_ex(const void *nodesv, uint64_t nnodes, const void *trisv, ui
         r.dinv = mk3(1.0f / r.dir.x, 1.0f / r.dir.y, 1.0f / r.dir.z);
         const float far = fmaxf_(fmaxf_(absf(r.orig.x), absf(r.orig.y)), absf(r.orig.z));
         const float lim = far < 67108864.0f ? clampNear : 1.8446744e19f;
-        const float di[3] = {r.dinv.x, r.dinv.y, r.dinv.z}, og[3] = {r.orig.x, r.orig.y, r.orig.z};
-        for (int a = 0; a < 3; a++) { r.dw[a] = fminf_(fmaxf_(di[a], -lim), lim); uint32_t b; memcpy(&b, &r.dw[a], 4); r.neg[a] = (b >> 31) != 0u; }
+        // the node test's units: the direction scaled by 2^-E, 2^E <= max |dir| < 2^(E+1) (flx_trace4.h: WRay::setup)
+        const float dm = fmaxf_(fmaxf_(absf(r.dir.x), absf(r.dir.y)), absf(r.dir.z));
+        uint32_t dmb; memcpy(&dmb, &dm, 4);
+        const int eb = std::min(std::max((int)(dmb >> 23), 1), 253);
+        const uint32_t pb = (uint32_t)(254 - eb) << 23, sb = (uint32_t)eb << 23;
+        float p, tsc; memcpy(&p, &pb, 4); memcpy(&tsc, &sb, 4);
+        const float ds[3] = {r.dir.x * p, r.dir.y * p, r.dir.z * p}, og[3] = {r.orig.x, r.orig.y, r.orig.z};
+        for (int a = 0; a < 3; a++) { r.dw[a] = fminf_(fmaxf_(1.0f / ds[a], -lim), lim); uint32_t b; memcpy(&b, &r.dw[a], 4); r.neg[a] = (b >> 31) != 0u; }
         float tbest = rp[3]; int tribest = -1;
         const double nv0 = nv;
         std::vector<uint32_t> stack; stack.reserve(64);
@@ -128,7 +134,7 @@ int fh_wide_visits_ex(const void *nodesv, uint64_t nnodes, const void *trisv, ui
                         const float a_n = __builtin_fmaf((float)((qn[a] >> (8 * c)) & 255u), sd[a], on[a]), a_f = __builtin_fmaf((float)((qf[a] >> (8 * c)) & 255u), sd[a], of[a]);
                         tn = a == 0 ? a_n : fmaxf_(tn, a_n); tf = a == 0 ? a_f : fminf_(tf, a_f);
                     }
-                    hit[c] = (tn <= tf) && (tf >= 0.0f) && (tn < tbest); key[c] = tn;
+                    hit[c] = (tn <= tf) && (tf >= 0.0f) && (tn < tbest * tsc); key[c] = tn;
                 }
                 if (mode == 1) {                       // any hit: last hit slot first, earlier ones pushed in slot order
                     int last = -1; for (int c = 0; c < 4; c++) if (hit[c]) last = c;
