@@ -6,19 +6,27 @@
 
 namespace flxd {
 
-// nearest texel, wrap by double modulo, RGBA8 (reference: src/utils.cl:114-133)
+// one texel coordinate of x = uv * size (reference: src/utils.cl:114-123 getTexelCoords).  The reference wraps (int)floor(x) with `% width` on a
+// uint width, so the modulo is unsigned: floor(x) < 0 wraps through 2^32 (on a width that is not a power of two this is not the signed modulo).
+// Where its conversion is undefined (|floor(x)| >= 2^31, inf, NaN) this is a deliberate choice: floor(x) modulo 2^32 as the same
+// two's complement extension, and a non-finite x reads coordinate 0.  The oracle's texelCoord (oracle/wf_oracle.cpp) is the same function.
+__device__ __forceinline__ int texel_coord(float x, uint32_t n)
+{
+    if (!(absf(x) <= FLX_FLT_MAX)) return 0;
+    const float f = floorf(x);
+    const float af = absf(f);
+    const uint32_t u = af < 2147483648.0f ? (uint32_t)(int)f : (af < 9223372036854775808.0f ? (uint32_t)(long long)f : 0u);
+    const uint32_t t = u % n;
+    const int c = (int)((float)t + x - f);                  // (int2)(tx + uv - floor(uv)): t, or t + 1 (or a multiple of ulp(x)) when the sum rounds up
+    return c < 0 ? 0 : (c > (int)n - 1 ? (int)n - 1 : c);
+}
+
+// nearest texel, RGBA8 (reference: src/utils.cl:114-133)
 __device__ __forceinline__ f3 read_texture(const Scene &sc, f2 uv, int idx)
 {
     const flx_texdesc tex = sc.texdesc[idx];
-    float ux = uv.x * (float)tex.width, uy = uv.y * (float)tex.height;
-    int w = (int)tex.width, h = (int)tex.height;
-    float fx = floorf(ux), fy = floorf(uy);
-    int tx = (((int)fx) % w + w) % w;
-    int ty = (((int)fy) % h + h) % h;
-    int cx = (int)((float)tx + ux - fx);
-    int cy = (int)((float)ty + uy - fy);
-    cx = cx < 0 ? 0 : (cx > w - 1 ? w - 1 : cx);
-    cy = cy < 0 ? 0 : (cy > h - 1 ? h - 1 : cy);
+    const int cx = texel_coord(uv.x * (float)tex.width, tex.width);
+    const int cy = texel_coord(uv.y * (float)tex.height, tex.height);
     const uint32_t texel = *reinterpret_cast<const uint32_t *>(sc.texdata + tex.offset + ((size_t)cx + (size_t)cy * tex.width) * 4);
     return mk3((float)(texel & 255u), (float)((texel >> 8) & 255u), (float)((texel >> 16) & 255u)) / 255.0f;
 }

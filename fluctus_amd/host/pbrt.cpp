@@ -16,6 +16,7 @@
 // missing, so this loader is checked against hand-built scenes only (tests/test_host.py), not against the reference.
 #include "scene.hpp"
 #include "texture.hpp"
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -420,7 +421,9 @@ struct Parser {
 
     void convertMaterials()
     {
-        auto rough = [](float r, bool remap, float ru, float rv) { const float res = r > 0.0f ? r : 0.5f * (ru + rv); return (1.0f - res) * (remap ? 5000.0f : 1.0f); };
+        // pbrt-v3 accepts any roughness; outside [0, 1] the remap would give Ns < 0 (to_roughness NaN / inf: every path through the material NaN)
+        auto rough = [](float r, bool remap, float ru, float rv) { const float res = std::min(1.0f, std::max(0.0f, r > 0.0f ? r : 0.5f * (ru + rv)));
+                                                                  return (1.0f - res) * (remap ? 5000.0f : 1.0f); };
         for (const MatRef &pm : usedMaterials) {
             flx_material m = scene.getMaterials()[0];                        // default parameters (:732)
             const Params &ps = pm->params;

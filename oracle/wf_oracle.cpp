@@ -319,18 +319,28 @@ f3 cosSampleHemisphere(f3 n, uint32_t *seed, float *p)
     return dir;
 }
 
+/* reference: utils.cl:114-123 getTexelCoords, one coordinate of x = uv * size.  `% width` is on a uint width in the reference, so the
+ * modulo is unsigned: floor(x) < 0 wraps through 2^32.  Where the reference's (int) conversion is undefined (|floor(x)| >= 2^31, inf,
+ * NaN; x86 gives INT_MIN, gfx950 saturates) the choice is DESIGN.md's: floor(x) modulo 2^32, and a non-finite x reads coordinate 0. */
+int texelCoord(float x, uint32_t n)
+{
+    if (!(absf(x) <= FLX_FLT_MAX)) return 0;
+    float f = floorf(x);
+    uint32_t u;
+    if (absf(f) < 2147483648.0f) u = (uint32_t)(int)f;
+    else if (absf(f) < 9223372036854775808.0f) u = (uint32_t)(int64_t)f;     /* an integer: exact in int64, then two's complement mod 2^32 */
+    else u = 0u;                                                            /* a multiple of 2^40 */
+    int tx = (int)(u % n);
+    /* (int2)(tx + frac) truncates toward zero; frac in [0,1) so the value is tx (or tx+1, or one ulp of x, when the sum rounds up) */
+    int cx = (int)((float)tx + x - f);
+    return cx < 0 ? 0 : (cx > (int)n - 1 ? (int)n - 1 : cx);
+}
+
 /* reference: utils.cl:114-133 */
 f3 readTexture(Ctx &c, f2 uv, const flx_texdesc &tex)
 {
-    float ux = uv.x * (float)tex.width, uy = uv.y * (float)tex.height;
-    int w = (int)tex.width, h = (int)tex.height;
-    int tx = (((int)floorf(ux)) % w + w) % w;
-    int ty = (((int)floorf(uy)) % h + h) % h;
-    /* (int2)(tx + frac) truncates toward zero; frac in [0,1) so the value is tx (or tx+1 when rounding up) */
-    int cx = (int)((float)tx + ux - floorf(ux));
-    int cy = (int)((float)ty + uy - floorf(uy));
-    cx = cx < 0 ? 0 : (cx > w - 1 ? w - 1 : cx);
-    cy = cy < 0 ? 0 : (cy > h - 1 ? h - 1 : cy);
+    int cx = texelCoord(uv.x * (float)tex.width, tex.width);
+    int cy = texelCoord(uv.y * (float)tex.height, tex.height);
     const uint8_t *pix = c.texdata.data() + tex.offset + (size_t)cx * 4 + (size_t)cy * tex.width * 4;
     return mk3((float)pix[0], (float)pix[1], (float)pix[2]) / 255.0f;
 }

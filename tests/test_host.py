@@ -695,6 +695,28 @@ def test_pbrt_scene_ingest(tmp_path, binary_ply):
     assert d.nodes.size >= 1
 
 
+@pytest.mark.parametrize("remap", ["true", "false"])
+def test_pbrt_roughness_outside_unit_range_keeps_materials_finite(tmp_path, remap):
+    """pbrt-v3 accepts any roughness; the ingest's remap to Ns must keep every emitted material's GGX roughness sqrt(2 / (2 + Ns))
+    (csrc/flx_bsdf.h to_roughness) finite -- roughness > 1 once gave Ns < 0 and a NaN throughput on every path through the material."""
+    mats = [('"plastic"', '"float roughness" 1.5'), ('"plastic"', '"float roughness" 1e6'), ('"plastic"', '"float roughness" -0.5'),
+            ('"substrate"', '"float uroughness" 3 "float vroughness" 5'), ('"uber"', '"float roughness" 2'),
+            ('"metal"', '"float roughness" 7'), ('"metal"', '"float roughness" 0 "float uroughness" 3 "float vroughness" 1.25'), ('"plastic"', '"float roughness" 0.3')]
+    body = ["WorldBegin"]
+    for i, (ty, par) in enumerate(mats):
+        body.append(f'Material {ty} {par} "bool remaproughness" "{remap}"')
+        body.append(f'Shape "trianglemesh" "integer indices" [0 1 2] "point P" [0 0 {i}  1 0 {i}  0 1 {i}]')
+    body.append("WorldEnd")
+    (tmp_path / "r.pbrt").write_text("\n".join(body) + "\n")
+    d = host.load_scene(str(tmp_path / "r.pbrt"))
+    assert d.materials.size == 1 + len(mats)
+    ns = d.materials["Ns"][1:].astype(np.float32)
+    alpha = np.sqrt(np.float32(2) / (np.float32(2) + ns))
+    assert np.isfinite(alpha).all() and (ns >= 0).all(), ns
+    top = 5000.0 if remap == "true" else 1.0
+    assert np.allclose(ns, [0, 0, top, 0, 0, 0, 0, 0.7 * top], rtol=1e-6)     # roughness clamped to [0, 1] before the remap
+
+
 def test_pbrt_errors(tmp_path):
     (tmp_path / "a.pbrt").write_text('WorldBegin\nShape "sphere"\nWorldEnd\n')
     with pytest.raises(RuntimeError, match="without triangle"):
