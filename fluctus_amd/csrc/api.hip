@@ -4,6 +4,7 @@
 #include "flx_wide.h"
 #include "flx_trace.h"
 #include "flx_trace4.h"
+#include "flx_denoise.h"
 #include "../../include/fluctus_hip.h"
 #include <string>
 #include <vector>
@@ -47,6 +48,8 @@ void launch_mk_splat(hipStream_t, const State &, const Frame &, const flx_render
 void launch_end_iteration(hipStream_t, uint32_t *, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t *);
 void launch_bump_extension(hipStream_t, uint32_t *, uint32_t);
 void launch_deinterleave(hipStream_t, const float *, float *, uint32_t, uint32_t, uint32_t);
+void launch_denoise(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float, float,
+                    const flx_render_params &);
 }
 
 using namespace flxd;
@@ -134,6 +137,11 @@ struct flx_ctx {
     int eagerBump = 0;          // A/B: bump the extension counter right after raygen / materials (option eager_bump)
     int denoiser = 0;           // USE_OPTIX_DENOISER of the reference: accumulate the denoiser feature buffers
     std::vector<void *> aovAllocs;
+    // flx_denoise (denoise.hip): working set (ping-pong radiance, packed guides) and which = 6; allocated by the first call, freed with the
+    // framebuffers or the feature buffers.  dnHave: which = 6 holds the output of a flx_denoise on the current buffers
+    std::vector<void *> dnAllocs;
+    float4 *dnE[2] = {nullptr, nullptr}, *dnG = nullptr; float2 *dnG2 = nullptr; float *dnOut = nullptr;
+    bool dnHave = false;
     int nodeLayout = 1;         // 1 = sibling-pair record numbering (see flx_upload_scene), 0 = DFS
     int numCUs = 256;
     // multi-GPU group (flx_group_*): RCCL communicator of this rank, root-side staging
@@ -195,8 +203,14 @@ static uint32_t localPixels(const flx_ctx *c)
 }
 
 // denoiser feature buffers (4 x float4 per local pixel) exist only while the option is on
+static void freeDenoise(flx_ctx *c)
+{
+    freeAll(c->dnAllocs);
+    c->dnE[0] = c->dnE[1] = c->dnG = nullptr; c->dnG2 = nullptr; c->dnOut = nullptr; c->dnHave = false;
+}
 static int allocAov(flx_ctx *c)
 {
+    freeDenoise(c);
     freeAll(c->aovAllocs);
     c->fr.aovAlbedo = c->fr.aovNormal = c->fr.aovAlbedoOut = c->fr.aovNormalOut = nullptr;
     if (!c->denoiser || !c->fr.localPixels) return 0;
@@ -215,6 +229,7 @@ static int allocFrame(flx_ctx *c)
     uint32_t lp = localPixels(c);
     if (lp == c->fr.localPixels && c->fr.pixels) return 0;
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    freeDenoise(c);
     freeAll(c->frameAllocs);
     HIPCHK(c, dalloc(c, c->frameAllocs, &c->fr.pixels, (size_t)lp * 4) ? hipErrorOutOfMemory : hipSuccess);
     HIPCHK(c, dalloc(c, c->frameAllocs, &c->fr.preview, (size_t)lp * 4) ? hipErrorOutOfMemory : hipSuccess);
@@ -381,7 +396,7 @@ int flx_destroy(flx_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) { flx_group_destroy(c); }
     freeAll(c->gatherAllocs);
-    freeAll(c->sceneAllocs); freeAll(c->spillAllocs); freeAll(c->envAllocs); freeAll(c->frameAllocs); freeAll(c->aovAllocs); freeAll(c->fixedAllocs);
+    freeAll(c->sceneAllocs); freeAll(c->spillAllocs); freeAll(c->envAllocs); freeAll(c->frameAllocs); freeAll(c->aovAllocs); freeAll(c->dnAllocs); freeAll(c->fixedAllocs);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pinnedIdx) (void)hipHostFree(c->pinnedIdx);
     if (c->pinnedMk) (void)hipHostFree(c->pinnedMk);
@@ -931,6 +946,34 @@ int flx_wf_materials(flx_ctx *c)
 }
 int flx_postprocess(flx_ctx *c) { READY(c, CALL_OBSERVE); { ScopedTimer t(c, FLX_K_POSTPROCESS); launch_postprocess(c->stream, c->fr, c->params); } LAUNCHED(c); return 0; }
 
+// DenoiserOptix::denoise (reference: src/denoiser/OptixDenoiser.cpp) as the guided a-trous filter of csrc/flx_denoise.h: reads which = 0 / 4 / 5,
+// writes which = 6 and the preview (which = 1).  Asynchronous; deferred and fused launches are flushed first (CALL_OBSERVE).
+int flx_denoise(flx_ctx *c, const flx_denoise_params *pp)
+{
+    READY(c, CALL_OBSERVE);
+    NEED(c, c->denoiser && c->fr.aovAlbedo && c->fr.aovNormal, "flx_denoise: needs the feature buffers: flx_set_option(ctx, \"denoiser\", 1)");
+    NEED(c, c->fr.nranks == 1, "flx_denoise: the context is partitioned (nranks > 1): a pixel's neighbours are on other ranks -- single-GPU only");
+    flx_denoise_params p = {FLX_DN_DEFAULT_ITERATIONS, FLX_DN_DEFAULT_SIGMA_COLOR, FLX_DN_DEFAULT_SIGMA_NORMAL, FLX_DN_DEFAULT_SIGMA_ALBEDO, 0.0f};
+    if (pp) p = *pp;
+    NEED(c, p.iterations >= 0 && p.iterations <= FLX_DN_MAX_ITERATIONS, "flx_denoise: iterations must be 0..8");
+    NEED(c, dn_finite(p.sigma_color) && p.sigma_color > 0.0f && dn_finite(p.sigma_normal) && p.sigma_normal > 0.0f &&
+            dn_finite(p.sigma_albedo) && p.sigma_albedo > 0.0f, "flx_denoise: sigma_color, sigma_normal and sigma_albedo must be finite and > 0");
+    NEED(c, p.blend == p.blend, "flx_denoise: blend is NaN");
+    const int W = (int)c->params.width, H = (int)c->params.height;
+    NEED(c, (uint64_t)W * H == c->fr.localPixels, "flx_denoise: framebuffer does not match width x height");
+    if (!c->dnOut) {
+        const size_t n = c->fr.localPixels;
+        if (dalloc(c, c->dnAllocs, &c->dnE[0], n) || dalloc(c, c->dnAllocs, &c->dnE[1], n) || dalloc(c, c->dnAllocs, &c->dnG, n) ||
+            dalloc(c, c->dnAllocs, &c->dnG2, n) || dalloc(c, c->dnAllocs, &c->dnOut, n * 4)) { freeDenoise(c); return 1; }
+    }
+    { ScopedTimer t(c, FLX_K_DENOISE);
+      launch_denoise(c->stream, c->fr, c->dnE[0], c->dnE[1], c->dnG, c->dnG2, c->dnOut, W, H, p.iterations, p.sigma_color, p.sigma_normal, p.sigma_albedo,
+                     dn_blend(p.blend), c->params); }
+    LAUNCHED(c);
+    c->dnHave = true;
+    return 0;
+}
+
 // ---- microkernel integrator.  One path per pixel, framebuffers indexed by the path id: single-GPU only, the pixel
 // partition belongs to the wavefront path (allocFrame sizes the buffers for the rank's LOCAL pixels).
 #define MK_READY(c) do { READY(c, CALL_OBSERVE); NEED(c, (c)->fr.nranks == 1, "the microkernel integrator is single-GPU: flx_set_partition(ctx, 0, 1) first"); } while (0)
@@ -1051,10 +1094,23 @@ int flx_read_pixels(flx_ctx *c, int which, float *out)
     ENTER(c, CALL_NEUTRAL);                                       // framebuffers only
     NEED(c, c->fr.pixels && out, "flx_read_pixels: no framebuffer");
     HIPCHK(c, hipSetDevice(c->device));
-    NEED(c, which >= 0 && which <= 5, "flx_read_pixels: which must be 0..5");
-    const float *src[6] = {c->fr.pixels, c->fr.preview, c->fr.aovAlbedoOut, c->fr.aovNormalOut, c->fr.aovAlbedo, c->fr.aovNormal};
+    NEED(c, which >= 0 && which <= 6, "flx_read_pixels: which must be 0..6");
+    NEED(c, which != 6 || c->dnHave, "flx_read_pixels: which = 6 is the output of flx_denoise (option \"denoiser\" on): none since the buffers were made");
+    const float *src[7] = {c->fr.pixels, c->fr.preview, c->fr.aovAlbedoOut, c->fr.aovNormalOut, c->fr.aovAlbedo, c->fr.aovNormal, c->dnOut};
     NEED(c, src[which], "flx_read_pixels: the denoiser feature buffers need flx_set_option(ctx, \"denoiser\", 1)");
     HIPCHK(c, hipMemcpyAsync(out, src[which], (size_t)c->fr.localPixels * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+int flx_write_pixels(flx_ctx *c, int which, const float *in)
+{
+    ENTER(c, CALL_NEUTRAL);                                       // framebuffers only
+    NEED(c, c->fr.pixels && in, "flx_write_pixels: no framebuffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, which == 0 || which == 4 || which == 5, "flx_write_pixels: which must be 0, 4 or 5");
+    float *dst = which == 0 ? c->fr.pixels : which == 4 ? c->fr.aovAlbedo : c->fr.aovNormal;
+    NEED(c, dst, "flx_write_pixels: the denoiser feature buffers need flx_set_option(ctx, \"denoiser\", 1)");
+    HIPCHK(c, hipMemcpyAsync(dst, in, (size_t)c->fr.localPixels * 16, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -3,6 +3,7 @@
 // Replaces reference kernels reset (src/wf_reset.cl:5-66), genRays (src/wf_raygen.cl:4-97) and
 // process (src/mk_postprocess.cl:7-55, src/tonemap.cl:3-26).
 #include "flx_shading.h"
+#include "flx_denoise.h"
 
 namespace flxd {
 
@@ -116,24 +117,14 @@ void launch_bump_extension(hipStream_t s, uint32_t *counters, uint32_t srcMask)
     hipLaunchKernelGGL(k_bump_extension, dim3(1), dim3(64), 0, s, counters, srcMask);
 }
 
-__device__ __forceinline__ f3 uc2_func(f3 x)
-{
-    const float A = 0.22f, B = 0.30f, C = 0.10f, D = 0.20f, E = 0.01f, Fq = 0.30f;
-    return ((x * (A * x + mk3(C * B)) + mk3(D * E)) / (x * (A * x + mk3(B)) + mk3(D * Fq))) - mk3(E / Fq);
-}
-
 __global__ __launch_bounds__(MISC_BLOCK) void k_postprocess(Frame fr, flx_render_params p)
 {
     const uint32_t gid = blockIdx.x * MISC_BLOCK + threadIdx.x;
     if (gid >= fr.localPixels) return;
     const float4 in = reinterpret_cast<const float4 *>(fr.pixels)[gid];
-    f3 col = ld3(in); float w = in.w;
-    if (w > 0.0f) { col = col / w; w = w / w; }
-    col = col * p.exposure;
-    if (p.tmOperator == 1u) col = col / (mk3(1.0f) + col);
-    if (p.tmOperator == 2u) col = uc2_func(2.0f * col) / uc2_func(mk3(11.2f));
-    col = pow3(col, 1.0f / 2.2f);
-    reinterpret_cast<float4 *>(fr.preview)[gid] = mk4(col, w);
+    float4 out;
+    postprocess_px(&in.x, p.exposure, p.tmOperator, &out.x);            // flx_denoise's preview runs the same function (flx_denoise.h)
+    reinterpret_cast<float4 *>(fr.preview)[gid] = out;
     if (fr.aovNormal) {                                                                          // src/mk_postprocess.cl:49-54
         const float4 n = reinterpret_cast<const float4 *>(fr.aovNormal)[gid], a = reinterpret_cast<const float4 *>(fr.aovAlbedo)[gid];
         reinterpret_cast<float4 *>(fr.aovNormalOut)[gid] = n.w > 1.0f ? make_float4(n.x / n.w, n.y / n.w, n.z / n.w, n.w / n.w) : n;

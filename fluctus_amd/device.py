@@ -21,9 +21,19 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_copy_pixels_to_device", "flx_stream", "flx_group_unique_id", "flx_group_init", "flx_group_init_local", "flx_gather", "flx_gather_local", "flx_group_destroy", "flx_group_info", "flx_profile_enable", "flx_profile_get", "flx_profile_reset",
            "flx_trace_stats_enable", "flx_trace_stats_get", "flx_trace_stats_get_ex", "flx_trace_stats_get_all", "flx_scene_info", "flx_trace_stats_reset", "flx_state_export", "flx_state_import", "flx_math_probe", "flx_env_sample_table",
            "flx_queue_read", "flx_queue_write", "flx_set_counters", "flx_set_option", "flx_get_option", "flx_mk_reset", "flx_mk_raygen", "flx_mk_next_vertex",
-           "flx_mk_sample_bsdf", "flx_mk_splat", "flx_mk_splat_preview", "flx_mk_stats_async", "flx_mk_stats_reset"]
+           "flx_mk_sample_bsdf", "flx_mk_splat", "flx_mk_splat_preview", "flx_mk_stats_async", "flx_mk_stats_reset", "flx_write_pixels", "flx_denoise"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
+K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with HipContext.denoise_profile (not part of profile_get)
+
+
+class DenoiseParams(C.Structure):
+    """flx_denoise_params (include/fluctus_hip.h)"""
+    _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("blend", C.c_float)]
+
+
+# the library's defaults (FLX_DN_DEFAULT_*, csrc/flx_denoise.h; DESIGN.md 4.3.1)
+DENOISE_DEFAULTS = dict(iterations=5, sigma_color=2.0, sigma_normal=0.3, sigma_albedo=0.1, blend=0.0)
 
 
 def _preload_torch_runtime():
@@ -163,6 +173,31 @@ class HipContext:
         out = np.zeros((self.local_pixels(), 4), np.float32)
         self._chk(self.L.flx_read_pixels(self.h, which, _p(out)))
         return out
+
+    def write_pixels(self, which, arr):
+        """which = 0 raw accumulation, 4 / 5 albedo / normal accumulators: (local pixels, 4) float32, blocking"""
+        arr = np.ascontiguousarray(arr, np.float32).reshape(-1, 4)
+        assert arr.shape[0] == self.local_pixels(), (arr.shape, self.local_pixels())
+        self._chk(self.L.flx_write_pixels(self.h, int(which), _p(arr)))
+
+    def denoise(self, **params):
+        """flx_denoise (asynchronous): iterations, sigma_color, sigma_normal, sigma_albedo, blend; missing ones take the defaults.
+        No keyword at all passes NULL (the library's defaults).  Result: read_pixels(6) and the preview read_pixels(1)."""
+        unknown = set(params) - set(DENOISE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"denoise: unknown parameters {sorted(unknown)}")
+        if not params:
+            self._chk(self.L.flx_denoise(self.h, None))
+            return
+        P = dict(DENOISE_DEFAULTS, **params)
+        dp = DenoiseParams(int(P["iterations"]), float(P["sigma_color"]), float(P["sigma_normal"]), float(P["sigma_albedo"]), float(P["blend"]))
+        self._chk(self.L.flx_denoise(self.h, C.byref(dp)))
+
+    def denoise_profile(self):
+        """(milliseconds, launches) of flx_denoise accumulated while profiling (level 1) since the last profile_reset; after finish()"""
+        ms, n = C.c_double(), C.c_uint64()
+        self._chk(self.L.flx_profile_get(self.h, K_DENOISE, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     # multi-GPU group (RCCL); see include/fluctus_hip.h
     def group_init(self, rank, nranks, unique_id):

@@ -51,6 +51,10 @@ public:
     void enqueueClearWfQueues();                                  // src/clcontext.cpp:877-883
     void enqueueGetCounters(QueueCounters *cnt);                  // async; valid after finishQueue()
     void enqueuePostprocessKernel(const RenderParams &params);
+    // DenoiserOptix::denoise (reference: src/denoiser/OptixDenoiser.cpp) as the guided a-trous filter of flx_denoise: the feature buffers in,
+    // the preview out; blend = DenoiserOptix' blendFactor (0 = fully denoised).  Asynchronous, like enqueuePostprocessKernel.
+    struct DenoiseParams { int iterations = 5; float sigmaColor = 2.0f, sigmaNormal = 0.3f, sigmaAlbedo = 0.1f, blend = 0.0f; };
+    void denoise(const DenoiseParams &params);
     void finishQueue();
     void updatePixelIndex(uint32_t numPixels, uint32_t numNewPaths);
     void resetPixelIndex();

@@ -150,6 +150,19 @@ bool Tracer::loadState()
     return true;
 }
 
+void Tracer::setDenoiserStrength(float s)
+{
+    if (s > 0.0f && !peers.empty()) throw std::runtime_error("setDenoiserStrength: the denoiser is single-GPU (a pixel's neighbours are on other ranks)");
+    denoiserStrength = s;
+}
+// DenoiserOptix::setBlend(1 - strength) + denoise (src/tracer.cpp:310-328): behind the post-process, on the stream
+void Tracer::denoiseStep()
+{
+    HipContext::DenoiseParams dp;
+    dp.blend = 1.0f - denoiserStrength;
+    clctx->denoise(dp);
+}
+
 // reference: src/tracer.cpp:95-187
 void Tracer::renderSingle(int spp, bool denoise)
 {
@@ -173,6 +186,7 @@ void Tracer::renderSingle(int spp, bool denoise)
         clctx->finishQueue();
         iteration++;
     }
+    if (denoise && denoiserStrength > 0.0f) { denoiseStep(); clctx->finishQueue(); }   // :160-165 (output_<spp>_denoised)
 }
 
 // reference: src/tracer.cpp:268-299, microkernel branch of update()
@@ -193,6 +207,7 @@ void Tracer::updateMicrokernel()
         clctx->enqueueSplatKernel(params);
     }
     clctx->enqueuePostprocessKernel(params);
+    if (useDenoiser && denoiserStrength > 0.0f && iteration >= 10 && iteration % 10 == 0) denoiseStep();   // :310-328
     clctx->fetchStatsAsync();                                            // :343-344
     clctx->finishQueue();
     iteration++;
@@ -238,6 +253,7 @@ void Tracer::update()
     }
     if (iteration == 0) { params.maxBounces = maxBounces; for (auto *c : R) c->updateParams(params); }
     for (auto *c : R) c->enqueuePostprocessKernel(params);
+    if (useDenoiser && denoiserStrength > 0.0f && iteration >= 10 && iteration % 10 == 0) denoiseStep();   // :310-328 (single-GPU: setDenoiserStrength)
     for (auto *c : R) c->finishQueue();
     QueueCounters sum; std::memset(&sum, 0, sizeof(sum));
     for (size_t r = 0; r < R.size(); r++) {

@@ -4,7 +4,8 @@
 // src/tracer.cpp): resetParams (:38-52), init (:55-80), initHierarchy (:574-590, BVH cache keyed by a hash of
 // the mesh), update() WF branch (:222-266, :302-340) and runBenchmark() WF body (:362-528, CSV schema
 // `scene;time;primary;extension;shadow;total;samples` :393), plus the microkernel integrator's branches of the same
-// functions and renderSingle (:95-187).  No window, no GL, no denoiser.
+// functions and renderSingle (:95-187), and the denoiser step of update() / renderSingle (:160-165, :310-328)
+// with flx_denoise in place of OptiX.  No window, no GL.
 #pragma once
 #include <memory>
 #include <string>
@@ -33,7 +34,12 @@ public:
     std::string runBenchmark(double seconds, int iterations = 0);
     // final-frame render: exactly `spp` samples in every pixel (reference: src/tracer.cpp:95-187).  Switches to the
     // microkernel integrator and turns Russian roulette off, as the reference does; needs numTasks >= width*height.
-    void renderSingle(int spp, bool denoise = false);                             // denoise: also fill the denoiser feature buffers
+    void renderSingle(int spp, bool denoise = false);                             // denoise: also fill the denoiser feature buffers (and denoise, strength > 0)
+    // the reference's denoiser strength slider (src/tracer_ui.cpp:359): blend = 1 - strength.  0 (this library's default; the reference's is 1,
+    // INTEGRATION.md) only fills the feature buffers; > 0 denoises the preview every 10th frame from frame 10 on, and renderSingle's final frame.
+    // Single-GPU: throws on a multi-rank Tracer.
+    void setDenoiserStrength(float s);
+    float getDenoiserStrength() const { return denoiserStrength; }
     void setDenoiser(bool on) { useDenoiser = on; for (auto *c : ranks()) c->recompileKernels(on); iteration = 0; }
     void toggleRenderer() { useWavefront = !useWavefront; iteration = 0; }        // src/tracer.cpp:881-886
     void setOption(const std::string &name, int value) { for (auto *c : ranks()) c->setOption(name, value); }   // every rank (HipContext::setOption)
@@ -73,7 +79,9 @@ private:
     BVH *bvh = nullptr;
     uint32_t iteration = 0;
     bool paramsUpdatePending = true;
-    bool useDenoiser = false;                                                     // feature buffers only; the OptiX denoiser itself is out of scope
+    bool useDenoiser = false;                                                     // the feature buffers (+ flx_denoise while denoiserStrength > 0)
+    float denoiserStrength = 0.0f;
+    void denoiseStep();                                                           // flx_denoise with blend = 1 - strength (rank 0; single-GPU)
     bool useWavefront = true;                                                     // this library's default; the reference starts on MK (src/tracer.cpp:11)
     QueueCounters lastCnt {};
     std::string sceneName;

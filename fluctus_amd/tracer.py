@@ -69,6 +69,12 @@ class Tracer:
     def set_denoiser(self, on):
         host._chk(self.L.fh_tracer_set_denoiser(self.h, int(bool(on))))
 
+    def set_denoiser_strength(self, s):
+        """The reference's denoiser strength (blend = 1 - s).  0 (the default) only fills the feature buffers; > 0 makes update() denoise
+        the preview at iterations 10, 20, ... and render_single(spp, denoise=True) denoise its final frame (read_pixels(6), read_pixels(1)).
+        Single-GPU."""
+        host._chk(self.L.fh_tracer_set_denoiser_strength(self.h, C.c_float(float(s))))
+
     def set_option(self, name, value):
         """HipContext::setOption -> flx_set_option (e.g. "extend_tree", 2 for the reference's bit-exact visit order)."""
         host._chk(self.L.fh_tracer_set_option(self.h, name.encode(), int(value)))

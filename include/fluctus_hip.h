@@ -95,8 +95,22 @@ int flx_postprocess(flx_ctx *ctx);
  * src/clcontext.cpp:852-874; buffers :337-338) -- `logic` / the microkernels also accumulate the denoiser feature
  * buffers and flx_postprocess resolves them: which = 2 albedo of the first non-singular hit, 3 first-hit normal in
  * camera space (both as written to denoiserAlbedoGL / denoiserNormalGL, src/mk_postprocess.cl:49-54), 4 / 5 the raw
- * accumulators (sum, count). */
+ * accumulators (sum, count); 6 the output of the last flx_denoise. */
 int flx_read_pixels(flx_ctx *ctx, int which, float *out_rgba);
+/* the blocking counterpart of flx_read_pixels for which = 0 (raw accumulation), 4 / 5 (the albedo / normal accumulators; option "denoiser"):
+ * lets a caller hand flx_denoise an accumulation of its own */
+int flx_write_pixels(flx_ctx *ctx, int which, const float *in_rgba);
+
+/* DenoiserOptix::denoise / setBlend / bindBuffers (src/denoiser/OptixDenoiser.cpp, src/tracer.cpp:310-328) as a guided a-trous wavelet
+ * filter for gfx950 (Dammertz et al., HPG 2010; csrc/flx_denoise.h): linear radiance (which = 0) demodulated by the floored
+ * first-hit albedo, edge-stopped by albedo and normal (which = 4 / 5, resolved as flx_postprocess resolves them -- it need not have run),
+ * `iterations` passes of step 1, 2, 4, ...  Writes the denoised linear image, readable as flx_read_pixels(ctx, 6, ...) (rgb, w = 1; a pixel
+ * with no samples or a non-finite value is passed through as it is), and the preview (which = 1) post-processed from it.  blend is OptiX'
+ * blendFactor (0 = fully denoised, 1 = the input), clamped to [0, 1]; blend 1 or 0 iterations return the input colour exactly.
+ * Asynchronous on the context stream like flx_postprocess.  Fails when the option "denoiser" is off, when the context is partitioned,
+ * when iterations is outside 0..8, when a sigma is not finite or <= 0, or when blend is NaN.  params NULL = the defaults. */
+typedef struct { int iterations; float sigma_color, sigma_normal, sigma_albedo, blend; } flx_denoise_params;
+int flx_denoise(flx_ctx *ctx, const flx_denoise_params *params);
 
 /* ---- microkernel integrator (the reference's second integrator).  One path per pixel (needs
  * num_tasks >= width*height to cover the image), `phase` state machine, exactly one sample per pixel per pass.
@@ -152,7 +166,8 @@ enum { FLX_K_RESET = 0, FLX_K_RAYGEN = 1, FLX_K_EXTEND = 2, FLX_K_SHADOW = 3, FL
        FLX_K_POSTPROCESS = 6,
        FLX_K_TRACE_SPAN = 7,   /* start of the extension kernel .. end of the (concurrent) shadow kernel */
        FLX_K_LOGIC_FUSED = 8,  /* logic + the inlined material step as one pass (option "fuse"); FLX_K_MATERIALS then covers the rest */
-       FLX_K_COUNT = 9 };
+       FLX_K_DENOISE = 9,      /* the whole of one flx_denoise */
+       FLX_K_COUNT = 10 };
 /* on: 0 off | 1 time every kernel | 2 time only the two trace kernels (+ their span), as the reference does | 3 only the
  * extension kernel | 4 the three kernels bench.py prices against a roof: extension, logic (the fused pass incl. its queue scan + scatter), shadow.
  * Each event pair costs a few microseconds of stream time, which shows at ~11 launches per 0.7 ms
