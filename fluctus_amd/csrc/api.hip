@@ -5,6 +5,7 @@
 #include "flx_trace.h"
 #include "flx_trace4.h"
 #include "flx_denoise.h"
+#include "flx_denoise_vg.h"
 #include "../../include/fluctus_hip.h"
 #include <string>
 #include <vector>
@@ -50,6 +51,8 @@ void launch_bump_extension(hipStream_t, uint32_t *, uint32_t);
 void launch_deinterleave(hipStream_t, const float *, float *, uint32_t, uint32_t, uint32_t);
 void launch_denoise(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float, float,
                     const flx_render_params &);
+void launch_denoise_vg(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float, float,
+                       const flx_render_params &);
 }
 
 using namespace flxd;
@@ -142,6 +145,8 @@ struct flx_ctx {
     std::vector<void *> dnAllocs;
     float4 *dnE[2] = {nullptr, nullptr}, *dnG = nullptr; float2 *dnG2 = nullptr; float *dnOut = nullptr;
     bool dnHave = false;
+    int moments = 0;            // option "moments": the splats accumulate the luminance moments (Frame::moments, which = 7)
+    std::vector<void *> momAllocs;
     int nodeLayout = 1;         // 1 = sibling-pair record numbering (see flx_upload_scene), 0 = DFS
     int numCUs = 256;
     // multi-GPU group (flx_group_*): RCCL communicator of this rank, root-side staging
@@ -208,6 +213,17 @@ static void freeDenoise(flx_ctx *c)
     freeAll(c->dnAllocs);
     c->dnE[0] = c->dnE[1] = c->dnG = nullptr; c->dnG2 = nullptr; c->dnOut = nullptr; c->dnHave = false;
 }
+// the luminance moments (float4 per local pixel) exist only while the option "moments" is on; zeroed when made
+static int allocMoments(flx_ctx *c)
+{
+    freeAll(c->momAllocs);
+    c->fr.moments = nullptr;
+    if (!c->moments || !c->fr.localPixels) return 0;
+    const size_t n = (size_t)c->fr.localPixels * 4;
+    HIPCHK(c, dalloc(c, c->momAllocs, &c->fr.moments, n) ? hipErrorOutOfMemory : hipSuccess);
+    HIPCHK(c, hipMemsetAsync(c->fr.moments, 0, n * 4, c->stream));
+    return 0;
+}
 static int allocAov(flx_ctx *c)
 {
     freeDenoise(c);
@@ -236,6 +252,7 @@ static int allocFrame(flx_ctx *c)
     HIPCHK(c, hipMemsetAsync(c->fr.pixels, 0, (size_t)lp * 16, c->stream));
     HIPCHK(c, hipMemsetAsync(c->fr.preview, 0, (size_t)lp * 16, c->stream));
     c->fr.localPixels = lp;
+    if (allocMoments(c)) return 1;
     return allocAov(c);
 }
 
@@ -396,7 +413,7 @@ int flx_destroy(flx_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) { flx_group_destroy(c); }
     freeAll(c->gatherAllocs);
-    freeAll(c->sceneAllocs); freeAll(c->spillAllocs); freeAll(c->envAllocs); freeAll(c->frameAllocs); freeAll(c->aovAllocs); freeAll(c->dnAllocs); freeAll(c->fixedAllocs);
+    freeAll(c->sceneAllocs); freeAll(c->spillAllocs); freeAll(c->envAllocs); freeAll(c->frameAllocs); freeAll(c->aovAllocs); freeAll(c->dnAllocs); freeAll(c->momAllocs); freeAll(c->fixedAllocs);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pinnedIdx) (void)hipHostFree(c->pinnedIdx);
     if (c->pinnedMk) (void)hipHostFree(c->pinnedMk);
@@ -974,6 +991,35 @@ int flx_denoise(flx_ctx *c, const flx_denoise_params *pp)
     return 0;
 }
 
+// the variance-guided filter of csrc/flx_denoise_vg.h: flx_denoise's inputs plus the luminance moments (which = 7); the same
+// outputs, working set (the variance rides in e.w), timer and flushing.
+int flx_denoise_variance_guided(flx_ctx *c, const flx_denoise_vg_params *pp)
+{
+    READY(c, CALL_OBSERVE);
+    NEED(c, c->denoiser && c->fr.aovAlbedo && c->fr.aovNormal, "flx_denoise_variance_guided: needs the feature buffers: flx_set_option(ctx, \"denoiser\", 1)");
+    NEED(c, c->moments && c->fr.moments, "flx_denoise_variance_guided: needs the luminance moments: flx_set_option(ctx, \"moments\", 1)");
+    NEED(c, c->fr.nranks == 1, "flx_denoise_variance_guided: the context is partitioned (nranks > 1): a pixel's neighbours are on other ranks -- single-GPU only");
+    flx_denoise_vg_params p = {FLX_VG_DEFAULT_ITERATIONS, FLX_VG_DEFAULT_SIGMA_LUMINANCE, FLX_VG_DEFAULT_SIGMA_NORMAL, FLX_VG_DEFAULT_SIGMA_ALBEDO, 0.0f};
+    if (pp) p = *pp;
+    NEED(c, p.iterations >= 0 && p.iterations <= FLX_DN_MAX_ITERATIONS, "flx_denoise_variance_guided: iterations must be 0..8");
+    NEED(c, dn_finite(p.sigma_luminance) && p.sigma_luminance > 0.0f && dn_finite(p.sigma_normal) && p.sigma_normal > 0.0f &&
+            dn_finite(p.sigma_albedo) && p.sigma_albedo > 0.0f, "flx_denoise_variance_guided: sigma_luminance, sigma_normal and sigma_albedo must be finite and > 0");
+    NEED(c, p.blend == p.blend, "flx_denoise_variance_guided: blend is NaN");
+    const int W = (int)c->params.width, H = (int)c->params.height;
+    NEED(c, (uint64_t)W * H == c->fr.localPixels, "flx_denoise_variance_guided: framebuffer does not match width x height");
+    if (!c->dnOut) {
+        const size_t n = c->fr.localPixels;
+        if (dalloc(c, c->dnAllocs, &c->dnE[0], n) || dalloc(c, c->dnAllocs, &c->dnE[1], n) || dalloc(c, c->dnAllocs, &c->dnG, n) ||
+            dalloc(c, c->dnAllocs, &c->dnG2, n) || dalloc(c, c->dnAllocs, &c->dnOut, n * 4)) { freeDenoise(c); return 1; }
+    }
+    { ScopedTimer t(c, FLX_K_DENOISE);
+      launch_denoise_vg(c->stream, c->fr, c->dnE[0], c->dnE[1], c->dnG, c->dnG2, c->dnOut, W, H, p.iterations, p.sigma_luminance, p.sigma_normal,
+                        p.sigma_albedo, dn_blend(p.blend), c->params); }
+    LAUNCHED(c);
+    c->dnHave = true;
+    return 0;
+}
+
 // ---- microkernel integrator.  One path per pixel, framebuffers indexed by the path id: single-GPU only, the pixel
 // partition belongs to the wavefront path (allocFrame sizes the buffers for the rank's LOCAL pixels).
 #define MK_READY(c) do { READY(c, CALL_OBSERVE); NEED(c, (c)->fr.nranks == 1, "the microkernel integrator is single-GPU: flx_set_partition(ctx, 0, 1) first"); } while (0)
@@ -1094,9 +1140,10 @@ int flx_read_pixels(flx_ctx *c, int which, float *out)
     ENTER(c, CALL_NEUTRAL);                                       // framebuffers only
     NEED(c, c->fr.pixels && out, "flx_read_pixels: no framebuffer");
     HIPCHK(c, hipSetDevice(c->device));
-    NEED(c, which >= 0 && which <= 6, "flx_read_pixels: which must be 0..6");
+    NEED(c, which >= 0 && which <= 7, "flx_read_pixels: which must be 0..7");
     NEED(c, which != 6 || c->dnHave, "flx_read_pixels: which = 6 is the output of flx_denoise (option \"denoiser\" on): none since the buffers were made");
-    const float *src[7] = {c->fr.pixels, c->fr.preview, c->fr.aovAlbedoOut, c->fr.aovNormalOut, c->fr.aovAlbedo, c->fr.aovNormal, c->dnOut};
+    NEED(c, which != 7 || c->fr.moments, "flx_read_pixels: which = 7 (the luminance moments) needs flx_set_option(ctx, \"moments\", 1)");
+    const float *src[8] = {c->fr.pixels, c->fr.preview, c->fr.aovAlbedoOut, c->fr.aovNormalOut, c->fr.aovAlbedo, c->fr.aovNormal, c->dnOut, c->fr.moments};
     NEED(c, src[which], "flx_read_pixels: the denoiser feature buffers need flx_set_option(ctx, \"denoiser\", 1)");
     HIPCHK(c, hipMemcpyAsync(out, src[which], (size_t)c->fr.localPixels * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1107,8 +1154,9 @@ int flx_write_pixels(flx_ctx *c, int which, const float *in)
     ENTER(c, CALL_NEUTRAL);                                       // framebuffers only
     NEED(c, c->fr.pixels && in, "flx_write_pixels: no framebuffer");
     HIPCHK(c, hipSetDevice(c->device));
-    NEED(c, which == 0 || which == 4 || which == 5, "flx_write_pixels: which must be 0, 4 or 5");
-    float *dst = which == 0 ? c->fr.pixels : which == 4 ? c->fr.aovAlbedo : c->fr.aovNormal;
+    NEED(c, which == 0 || which == 4 || which == 5 || which == 7, "flx_write_pixels: which must be 0, 4 or 5, or 7 with option \"moments\"");
+    NEED(c, which != 7 || c->fr.moments, "flx_write_pixels: which = 7 (the luminance moments) needs flx_set_option(ctx, \"moments\", 1)");
+    float *dst = which == 0 ? c->fr.pixels : which == 4 ? c->fr.aovAlbedo : which == 5 ? c->fr.aovNormal : c->fr.moments;
     NEED(c, dst, "flx_write_pixels: the denoiser feature buffers need flx_set_option(ctx, \"denoiser\", 1)");
     HIPCHK(c, hipMemcpyAsync(dst, in, (size_t)c->fr.localPixels * 16, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1502,6 +1550,11 @@ int flx_set_option(flx_ctx *c, const char *name, int value)
         if (c->denoiser != value) { c->denoiser = value; HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipStreamSynchronize(c->stream)); return allocAov(c); }
         return 0;
     }
+    if (name && strcmp(name, "moments") == 0 && (value == 0 || value == 1)) {
+        ENTER(c, CALL_OBSERVE);
+        if (c->moments != value) { c->moments = value; HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipStreamSynchronize(c->stream)); return allocMoments(c); }
+        return 0;
+    }
     if (name && strcmp(name, "refill_extend") == 0 && refill_value_ok(value)) { ENTER(c, CALL_OBSERVE); c->refillExt = value; return 0; }
     if (name && strcmp(name, "refill_shadow") == 0 && (value == -1 || refill_value_ok(value))) { ENTER(c, CALL_OBSERVE); c->refillShadowOpt = value; pickSchedule(c); return 0; }
     if (name && (strcmp(name, "refill_extend") == 0 || strcmp(name, "refill_shadow") == 0)) { c->err = "flx_set_option: refill value must be 0 or refillMin (1..64) | waitMax (0..64) << 8"; return 1; }
@@ -1523,7 +1576,7 @@ int flx_get_option(flx_ctx *c, const char *name, int *value)
     NEED(c, name && value, "flx_get_option: null");
     const struct { const char *n; int v; } tab[] = {
         {"xcd_remap", c->xcdRemap}, {"fuse", c->fuse}, {"overlap", c->overlap}, {"shadow_tree", c->shadowTree}, {"extend_tree", c->extendTree},
-        {"denoiser", c->denoiser}, {"eager_bump", c->eagerBump}, {"node_layout", c->nodeLayout}, {"fuse_set", c->fuseSet}, {"ext_order", c->extOrder}, {"regen", c->regenOpt}, {"regroup", c->regroup}, {"regen_prep", c->prepOpt}, {"refill_extend", c->refillExt}, {"refill_shadow", c->refillShadow}, {"shadow_split", c->shadowSplit}, {"fused_queue_mask", (int)fused_queue_mask(fuseSetNow(c))}, {"fuse_set_now", fuseSetNow(c)}};
+        {"denoiser", c->denoiser}, {"moments", c->moments}, {"eager_bump", c->eagerBump}, {"node_layout", c->nodeLayout}, {"fuse_set", c->fuseSet}, {"ext_order", c->extOrder}, {"regen", c->regenOpt}, {"regroup", c->regroup}, {"regen_prep", c->prepOpt}, {"refill_extend", c->refillExt}, {"refill_shadow", c->refillShadow}, {"shadow_split", c->shadowSplit}, {"fused_queue_mask", (int)fused_queue_mask(fuseSetNow(c))}, {"fuse_set_now", fuseSetNow(c)}};
     for (const auto &t : tab) if (strcmp(name, t.n) == 0) { *value = t.v; return 0; }
     if (strcmp(name, "phase") == 0) { *value = phaseCode(c); return 0; }
     c->err = std::string("flx_get_option: unknown option ") + name;

@@ -116,6 +116,11 @@ FLX_HD void dn_finish(const float px[4], const dn_pix &pi, f3 c, f3 ef, float bl
     out[0] = o.x; out[1] = o.y; out[2] = o.z; out[3] = 1.0f;
 }
 
+/* ---- luminance of a sample (option "moments": the integrators' splats accumulate (sum l, sum l^2, 0, n) per pixel, flx_read_pixels which = 7;
+ * the variance-guided filter of flx_denoise_vg.h).  Rec. 709 weights in this fixed order; every file that includes this header is built with
+ * -ffp-contract=off, so no product is fused into an FMA and the host, the device and numpy float32 give the same bits. */
+FLX_HD float flx_lum(f3 v) { return (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z; }
+
 /* ---- the post-process (reference: src/mk_postprocess.cl:7-55, src/tonemap.cl:3-26): k_postprocess and the denoiser's preview */
 FLX_HD f3 uc2_tonemap(f3 x)
 {

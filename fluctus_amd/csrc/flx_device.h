@@ -115,6 +115,9 @@ struct Frame {                    // framebuffers + cursor + partition
     // denoiser feature buffers (reference: USE_OPTIX_DENOISER build; src/clcontext.cpp:337-338): float4 per local pixel,
     // accumulators + the resolved outputs of `process`; nullptr while the option is off
     float *aovAlbedo, *aovNormal, *aovAlbedoOut, *aovNormalOut;
+    // option "moments": float4 per local pixel, (sum l, sum l^2, 0, n) of the luminance l = flx_lum(Ei) of every splatted sample
+    // (flx_denoise.h); nullptr while the option is off
+    float *moments;
     uint32_t *currPixelIdx;       // device copy of the pixel cursor
     uint32_t rank, nranks;
     uint32_t localPixels;

@@ -24,6 +24,7 @@
 // scatter kernel appends the material lists to the extension queue at the slots the material kernels would compute.
 #include "flx_bsdf.h"
 #include "flx_trace.h"          // hit_values_raw: the commit of traceExtension for RAW hit records
+#include "flx_denoise.h"        // flx_lum: the luminance moments (option "moments")
 
 namespace flxd {
 
@@ -309,6 +310,11 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
                 float *px = fr.pixels + (size_t)pixIdx * 4;
                 unsafeAtomicAdd(px + 0, Ei.x); unsafeAtomicAdd(px + 1, Ei.y);
                 unsafeAtomicAdd(px + 2, Ei.z); unsafeAtomicAdd(px + 3, 1.0f);
+                if (fr.moments) {                                     // option "moments": (sum l, sum l^2, 0, n), opt-in scattered atomics
+                    const float l = flx_lum(Ei);
+                    float *m = fr.moments + (size_t)pixIdx * 4;
+                    unsafeAtomicAdd(m + 0, l); unsafeAtomicAdd(m + 1, l * l); unsafeAtomicAdd(m + 3, 1.0f);
+                }
             }
 #endif
         };

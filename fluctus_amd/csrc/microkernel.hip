@@ -8,6 +8,7 @@
 // wavefront path; gid = pixel = path, so the framebuffer is written without atomics.
 #include "flx_trace.h"
 #include "flx_bsdf.h"
+#include "flx_denoise.h"        // flx_lum: the luminance moments (option "moments")
 
 namespace flxd {
 
@@ -32,6 +33,7 @@ __global__ __launch_bounds__(256) void k_mk_reset(State st, Frame fr, flx_render
     const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
     if (gid >= mk_limit(st, p)) return;
     reinterpret_cast<float4 *>(fr.pixels)[gid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (fr.moments) reinterpret_cast<float4 *>(fr.moments)[gid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (fr.aovNormal) {                                                                           // src/mk_reset.cl:24-25
         reinterpret_cast<float4 *>(fr.aovNormal)[gid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         reinterpret_cast<float4 *>(fr.aovAlbedo)[gid] = make_float4(0.1f, 0.1f, 0.1f, 0.0f);
@@ -262,6 +264,13 @@ __global__ __launch_bounds__(256) void k_mk_splat(State st, Frame fr, flx_render
             const float4 prev = *px;
             if (prev.w > 0.0f) { col.x += prev.x; col.y += prev.y; col.z += prev.z; col.w += prev.w; }
             *px = col;
+            if (fr.moments) {                                       // option "moments": one thread per pixel, a plain read-modify-write;
+                const float l = flx_lum(mk3(ei.x, ei.y, ei.z));     // restarted with the colour after a preview (alpha 0)
+                float4 *m = reinterpret_cast<float4 *>(fr.moments) + gid;
+                float4 mv = prev.w > 0.0f ? *m : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                mv.x += l; mv.y += l * l; mv.w += 1.0f;
+                *m = mv;
+            }
         }
         wr4(st.at(S_EI, gid), make_float4(0.0f, 0.0f, 0.0f, ei.w));
         const float4 thr = rd4(st.at(S_THR, gid)); wr4(st.at(S_THR, gid), mk4u(mk3(1.0f), __float_as_uint(thr.w)));

@@ -34,6 +34,7 @@ __global__ __launch_bounds__(MISC_BLOCK) void k_reset(State st, Queues qs, Frame
     if (gid >= n) return;
     if (gid < fr.localPixels) {
         reinterpret_cast<float4 *>(fr.pixels)[gid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (fr.moments) reinterpret_cast<float4 *>(fr.moments)[gid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (fr.aovNormal) {                                                                      // src/wf_reset.cl:22-24
             reinterpret_cast<float4 *>(fr.aovNormal)[gid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             reinterpret_cast<float4 *>(fr.aovAlbedo)[gid] = make_float4(0.1f, 0.1f, 0.1f, 0.0f);   // default for direct emission

@@ -21,7 +21,8 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_copy_pixels_to_device", "flx_stream", "flx_group_unique_id", "flx_group_init", "flx_group_init_local", "flx_gather", "flx_gather_local", "flx_group_destroy", "flx_group_info", "flx_profile_enable", "flx_profile_get", "flx_profile_reset",
            "flx_trace_stats_enable", "flx_trace_stats_get", "flx_trace_stats_get_ex", "flx_trace_stats_get_all", "flx_scene_info", "flx_trace_stats_reset", "flx_state_export", "flx_state_import", "flx_math_probe", "flx_env_sample_table",
            "flx_queue_read", "flx_queue_write", "flx_set_counters", "flx_set_option", "flx_get_option", "flx_mk_reset", "flx_mk_raygen", "flx_mk_next_vertex",
-           "flx_mk_sample_bsdf", "flx_mk_splat", "flx_mk_splat_preview", "flx_mk_stats_async", "flx_mk_stats_reset", "flx_write_pixels", "flx_denoise"]
+           "flx_mk_sample_bsdf", "flx_mk_splat", "flx_mk_splat_preview", "flx_mk_stats_async", "flx_mk_stats_reset", "flx_write_pixels", "flx_denoise",
+           "flx_denoise_variance_guided"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
 K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with HipContext.denoise_profile (not part of profile_get)
@@ -34,6 +35,15 @@ class DenoiseParams(C.Structure):
 
 # the library's defaults (FLX_DN_DEFAULT_*, csrc/flx_denoise.h)
 DENOISE_DEFAULTS = dict(iterations=5, sigma_color=2.0, sigma_normal=0.3, sigma_albedo=0.1, blend=0.0)
+
+
+class DenoiseVgParams(C.Structure):
+    """flx_denoise_vg_params (include/fluctus_hip.h)"""
+    _fields_ = [("iterations", C.c_int), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("blend", C.c_float)]
+
+
+# the library's defaults (FLX_VG_DEFAULT_*, csrc/flx_denoise_vg.h; DESIGN.md 4.3.2)
+DENOISE_VG_DEFAULTS = dict(iterations=5, sigma_luminance=4.0, sigma_normal=0.3, sigma_albedo=0.1, blend=0.0)
 
 
 def _preload_torch_runtime():
@@ -175,7 +185,8 @@ class HipContext:
         return out
 
     def write_pixels(self, which, arr):
-        """which = 0 raw accumulation, 4 / 5 albedo / normal accumulators: (local pixels, 4) float32, blocking"""
+        """which = 0 raw accumulation, 4 / 5 albedo / normal accumulators, 7 luminance moments (option "moments"): (local pixels, 4) float32,
+        blocking"""
         arr = np.ascontiguousarray(arr, np.float32).reshape(-1, 4)
         assert arr.shape[0] == self.local_pixels(), (arr.shape, self.local_pixels())
         self._chk(self.L.flx_write_pixels(self.h, int(which), _p(arr)))
@@ -192,6 +203,19 @@ class HipContext:
         P = dict(DENOISE_DEFAULTS, **params)
         dp = DenoiseParams(int(P["iterations"]), float(P["sigma_color"]), float(P["sigma_normal"]), float(P["sigma_albedo"]), float(P["blend"]))
         self._chk(self.L.flx_denoise(self.h, C.byref(dp)))
+
+    def denoise_variance_guided(self, **params):
+        """flx_denoise_variance_guided (asynchronous; options "denoiser" and "moments"): iterations, sigma_luminance, sigma_normal, sigma_albedo,
+        blend; missing ones take the defaults, no keyword at all passes NULL.  Result: read_pixels(6) and the preview read_pixels(1)."""
+        unknown = set(params) - set(DENOISE_VG_DEFAULTS)
+        if unknown:
+            raise TypeError(f"denoise_variance_guided: unknown parameters {sorted(unknown)}")
+        if not params:
+            self._chk(self.L.flx_denoise_variance_guided(self.h, None))
+            return
+        P = dict(DENOISE_VG_DEFAULTS, **params)
+        dp = DenoiseVgParams(int(P["iterations"]), float(P["sigma_luminance"]), float(P["sigma_normal"]), float(P["sigma_albedo"]), float(P["blend"]))
+        self._chk(self.L.flx_denoise_variance_guided(self.h, C.byref(dp)))
 
     def denoise_profile(self):
         """(milliseconds, launches) of flx_denoise accumulated while profiling (level 1) since the last profile_reset; after finish()"""

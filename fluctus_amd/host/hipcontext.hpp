@@ -55,6 +55,9 @@ public:
     // the preview out; blend = DenoiserOptix' blendFactor (0 = fully denoised).  Asynchronous, like enqueuePostprocessKernel.
     struct DenoiseParams { int iterations = 5; float sigmaColor = 2.0f, sigmaNormal = 0.3f, sigmaAlbedo = 0.1f, blend = 0.0f; };
     void denoise(const DenoiseParams &params);
+    // the variance-guided filter (flx_denoise_variance_guided): needs the options "denoiser" and "moments"; otherwise as denoise()
+    struct DenoiseVgParams { int iterations = 5; float sigmaLuminance = 4.0f, sigmaNormal = 0.3f, sigmaAlbedo = 0.1f, blend = 0.0f; };
+    void denoiseVarianceGuided(const DenoiseVgParams &params);
     void finishQueue();
     void updatePixelIndex(uint32_t numPixels, uint32_t numNewPaths);
     void resetPixelIndex();

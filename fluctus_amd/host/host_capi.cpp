@@ -295,6 +295,7 @@ int fh_tracer_render_single(void *t, int spp, int denoise) { FH_TRY ((Tracer *)t
 int fh_tracer_set_option(void *t, const char *name, int value) { FH_TRY ((Tracer *)t)->setOption(name ? name : "", value); FH_CATCH }
 int fh_tracer_set_denoiser(void *t, int on) { FH_TRY ((Tracer *)t)->setDenoiser(on != 0); FH_CATCH }
 int fh_tracer_set_denoiser_strength(void *t, float s) { FH_TRY ((Tracer *)t)->setDenoiserStrength(s); FH_CATCH }
+int fh_tracer_set_denoiser_mode(void *t, int mode) { FH_TRY ((Tracer *)t)->setDenoiserMode((Tracer::DenoiserMode)mode); FH_CATCH }
 int fh_tracer_toggle_renderer(void *t) { FH_TRY ((Tracer *)t)->toggleRenderer(); FH_CATCH }
 int fh_tracer_uses_wavefront(void *t) { return ((Tracer *)t)->usesWavefront() ? 1 : 0; }
 int fh_tracer_stats(void *t, uint64_t *out4)

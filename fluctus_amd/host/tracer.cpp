@@ -158,9 +158,31 @@ void Tracer::setDenoiserStrength(float s)
 // DenoiserOptix::setBlend(1 - strength) + denoise (src/tracer.cpp:310-328): behind the post-process, on the stream
 void Tracer::denoiseStep()
 {
+    if (denoiserMode == VarianceGuided) {
+        HipContext::DenoiseVgParams dp;
+        dp.blend = 1.0f - denoiserStrength;
+        clctx->denoiseVarianceGuided(dp);
+        return;
+    }
     HipContext::DenoiseParams dp;
     dp.blend = 1.0f - denoiserStrength;
     clctx->denoise(dp);
+}
+void Tracer::applyMoments()
+{
+    const bool on = useDenoiser && denoiserMode == VarianceGuided;
+    if (on == momentsOn) return;
+    for (auto *c : ranks()) c->setOption("moments", on ? 1 : 0);
+    momentsOn = on;
+}
+void Tracer::setDenoiserMode(DenoiserMode m)
+{
+    if (m != Guided && m != VarianceGuided) throw std::runtime_error("setDenoiserMode: unknown mode");
+    if (m == denoiserMode) return;
+    denoiserMode = m;
+    const bool was = momentsOn;
+    applyMoments();
+    if (momentsOn != was) iteration = 0;                                 // restart the accumulation with its moments
 }
 
 // reference: src/tracer.cpp:95-187

@@ -40,7 +40,12 @@ public:
     // Single-GPU: throws on a multi-rank Tracer.
     void setDenoiserStrength(float s);
     float getDenoiserStrength() const { return denoiserStrength; }
-    void setDenoiser(bool on) { useDenoiser = on; for (auto *c : ranks()) c->recompileKernels(on); iteration = 0; }
+    void setDenoiser(bool on) { useDenoiser = on; for (auto *c : ranks()) c->recompileKernels(on); applyMoments(); iteration = 0; }
+    // which filter the denoiser step runs: Guided (default, flx_denoise) or VarianceGuided (flx_denoise_variance_guided, which also needs
+    // the luminance moments: while the denoiser is on in this mode, every rank accumulates them).  Same schedule either way.
+    enum DenoiserMode { Guided = 0, VarianceGuided = 1 };
+    void setDenoiserMode(DenoiserMode m);
+    DenoiserMode getDenoiserMode() const { return denoiserMode; }
     void toggleRenderer() { useWavefront = !useWavefront; iteration = 0; }        // src/tracer.cpp:881-886
     void setOption(const std::string &name, int value) { for (auto *c : ranks()) c->setOption(name, value); }   // every rank (HipContext::setOption)
     bool usesWavefront() const { return useWavefront; }
@@ -81,7 +86,10 @@ private:
     bool paramsUpdatePending = true;
     bool useDenoiser = false;                                                     // the feature buffers (+ flx_denoise while denoiserStrength > 0)
     float denoiserStrength = 0.0f;
-    void denoiseStep();                                                           // flx_denoise with blend = 1 - strength (rank 0; single-GPU)
+    DenoiserMode denoiserMode = Guided;
+    bool momentsOn = false;                                                       // the ranks' option "moments" as applyMoments left it
+    void applyMoments();                                                          // "moments" on iff the denoiser is on in VarianceGuided mode
+    void denoiseStep();                                                           // the mode's filter with blend = 1 - strength (rank 0; single-GPU)
     bool useWavefront = true;                                                     // this library's default; the reference starts on MK (src/tracer.cpp:11)
     QueueCounters lastCnt {};
     std::string sceneName;

@@ -75,6 +75,14 @@ class Tracer:
         Single-GPU."""
         host._chk(self.L.fh_tracer_set_denoiser_strength(self.h, C.c_float(float(s))))
 
+    def set_denoiser_mode(self, mode):
+        """Tracer::setDenoiserMode: "guided" (the default, flx_denoise) or "variance" (flx_denoise_variance_guided; while the denoiser is on
+        the splats also accumulate the luminance moments, read_pixels(7)).  The denoising schedule is the same in both modes."""
+        modes = {"guided": 0, "variance": 1}
+        if mode not in modes:
+            raise ValueError(f"set_denoiser_mode: mode must be one of {sorted(modes)}, not {mode!r}")
+        host._chk(self.L.fh_tracer_set_denoiser_mode(self.h, modes[mode]))
+
     def set_option(self, name, value):
         """HipContext::setOption -> flx_set_option (e.g. "extend_tree", 2 for the reference's bit-exact visit order)."""
         host._chk(self.L.fh_tracer_set_option(self.h, name.encode(), int(value)))

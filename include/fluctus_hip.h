@@ -95,10 +95,12 @@ int flx_postprocess(flx_ctx *ctx);
  * src/clcontext.cpp:852-874; buffers :337-338) -- `logic` / the microkernels also accumulate the denoiser feature
  * buffers and flx_postprocess resolves them: which = 2 albedo of the first non-singular hit, 3 first-hit normal in
  * camera space (both as written to denoiserAlbedoGL / denoiserNormalGL, src/mk_postprocess.cl:49-54), 4 / 5 the raw
- * accumulators (sum, count); 6 the output of the last flx_denoise. */
+ * accumulators (sum, count); 6 the output of the last flx_denoise or flx_denoise_variance_guided.
+ * which = 7, with flx_set_option(ctx, "moments", 1): the luminance moments (sum l, sum l^2, 0, n) of the samples splatted into each pixel,
+ * l = the Rec. 709 luminance of the sample (csrc/flx_denoise.h: flx_lum).  The moments are LOCAL to a rank: flx_gather does not carry them. */
 int flx_read_pixels(flx_ctx *ctx, int which, float *out_rgba);
-/* the blocking counterpart of flx_read_pixels for which = 0 (raw accumulation), 4 / 5 (the albedo / normal accumulators; option "denoiser"):
- * lets a caller hand flx_denoise an accumulation of its own */
+/* the blocking counterpart of flx_read_pixels for which = 0 (raw accumulation), 4 / 5 (the albedo / normal accumulators; option "denoiser"),
+ * 7 (the luminance moments; option "moments"): lets a caller hand the denoisers an accumulation of its own */
 int flx_write_pixels(flx_ctx *ctx, int which, const float *in_rgba);
 
 /* DenoiserOptix::denoise / setBlend / bindBuffers (src/denoiser/OptixDenoiser.cpp, src/tracer.cpp:310-328) as a guided a-trous wavelet
@@ -111,6 +113,17 @@ int flx_write_pixels(flx_ctx *ctx, int which, const float *in_rgba);
  * when iterations is outside 0..8, when a sigma is not finite or <= 0, or when blend is NaN.  params NULL = the defaults. */
 typedef struct { int iterations; float sigma_color, sigma_normal, sigma_albedo, blend; } flx_denoise_params;
 int flx_denoise(flx_ctx *ctx, const flx_denoise_params *params);
+
+/* The variance-guided a-trous filter (the spatial filter of SVGF, Schied et al., HPG 2017; csrc/flx_denoise_vg.h): flx_denoise
+ * with the fixed colour stop replaced by a luminance stop scaled by sigma_luminance times the prefiltered standard deviation of each pixel's
+ * mean, estimated from the luminance moments (which = 7; a spatial estimate where a pixel has fewer than 2 samples) and carried through the
+ * passes (the prefilter clamped by the pixel's own variance).  A pixel none of whose samples hit a surface (albedo accumulator count 0: it saw
+ * the area light or the environment directly) is returned as its colour and is never a neighbour.
+ * Needs the options "denoiser" and "moments" on and an unpartitioned context; writes which = 6 and the preview exactly as flx_denoise
+ * does, timed under FLX_K_DENOISE.  Fails as flx_denoise does (iterations outside 0..8, a sigma not finite or <= 0, a NaN blend) and when
+ * the option "moments" is off.  params NULL = the defaults. */
+typedef struct { int iterations; float sigma_luminance, sigma_normal, sigma_albedo, blend; } flx_denoise_vg_params;
+int flx_denoise_variance_guided(flx_ctx *ctx, const flx_denoise_vg_params *params);
 
 /* ---- microkernel integrator (the reference's second integrator).  One path per pixel (needs
  * num_tasks >= width*height to cover the image), `phase` state machine, exactly one sample per pixel per pass.
@@ -166,7 +179,7 @@ enum { FLX_K_RESET = 0, FLX_K_RAYGEN = 1, FLX_K_EXTEND = 2, FLX_K_SHADOW = 3, FL
        FLX_K_POSTPROCESS = 6,
        FLX_K_TRACE_SPAN = 7,   /* start of the extension kernel .. end of the (concurrent) shadow kernel */
        FLX_K_LOGIC_FUSED = 8,  /* logic + the inlined material step as one pass (option "fuse"); FLX_K_MATERIALS then covers the rest */
-       FLX_K_DENOISE = 9,      /* the whole of one flx_denoise */
+       FLX_K_DENOISE = 9,      /* the whole of one flx_denoise or flx_denoise_variance_guided */
        FLX_K_COUNT = 10 };
 /* on: 0 off | 1 time every kernel | 2 time only the two trace kernels (+ their span), as the reference does | 3 only the
  * extension kernel | 4 the three kernels bench.py prices against a roof: extension, logic (the fused pass incl. its queue scan + scatter), shadow.
@@ -255,6 +268,9 @@ int flx_set_counters(flx_ctx *ctx, const void *in32);
  *                     it with fuse_set (1 with 31, 2 with 1); set it afterwards to override
  *   node_layout       1 (default) sibling-pair record numbering of the binary tree | 0 DFS numbering; takes effect at the next flx_upload_scene
  *   denoiser          1: accumulate the denoiser feature buffers (see flx_read_pixels); default 0
+ *   moments           1: the splats (flx_wf_logic, flx_mk_splat) also accumulate the luminance moments of their samples (flx_read_pixels
+ *                     which = 7), three more scattered float atomics per terminating path in the wavefront integrator; the resets zero
+ *                     them.  Default 0.  Local to each rank (flx_gather does not carry them)
  *   xcd_remap, eager_bump: A/B knobs of the binary kernels */
 int flx_set_option(flx_ctx *ctx, const char *name, int value);
 /* current value of an option above, or of the read-only "fused_queue_mask" (bit q set = the fused pass inlines the material step of
