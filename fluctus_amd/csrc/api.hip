@@ -49,10 +49,9 @@ void launch_mk_splat(hipStream_t, const State &, const Frame &, const flx_render
 void launch_end_iteration(hipStream_t, uint32_t *, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t *);
 void launch_bump_extension(hipStream_t, uint32_t *, uint32_t);
 void launch_deinterleave(hipStream_t, const float *, float *, uint32_t, uint32_t, uint32_t);
-void launch_denoise(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float, float,
-                    const flx_render_params &);
-void launch_denoise_vg(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float, float,
-                       const flx_render_params &);
+struct DnGuided; struct DnVg;     // the two filters of denoise.hip
+template <class F> void launch_denoise(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float,
+                                       float, const flx_render_params &);
 }
 
 using namespace flxd;
@@ -963,61 +962,54 @@ int flx_wf_materials(flx_ctx *c)
 }
 int flx_postprocess(flx_ctx *c) { READY(c, CALL_OBSERVE); { ScopedTimer t(c, FLX_K_POSTPROCESS); launch_postprocess(c->stream, c->fr, c->params); } LAUNCHED(c); return 0; }
 
-// DenoiserOptix::denoise (reference: src/denoiser/OptixDenoiser.cpp) as the guided a-trous filter of csrc/flx_denoise.h: reads which = 0 / 4 / 5,
-// writes which = 6 and the preview (which = 1).  Asynchronous; deferred and fused launches are flushed first (CALL_OBSERVE).
-int flx_denoise(flx_ctx *c, const flx_denoise_params *pp)
+// flx_denoise and flx_denoise_variance_guided: the checks, the working set (allocated by the first call), the timer and dnHave.  fn names the
+// entry point in the messages, sigma0 its first sigma; the variance-guided filter needs the luminance moments.
+typedef void (*DenoiseLaunch)(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float, float,
+                              const flx_render_params &);
+static int denoiseCall(flx_ctx *c, const char *fn, DenoiseLaunch launch, bool moments, const char *sigma0, int iterations, float s0, float sigma_n,
+                       float sigma_a, float blend)
 {
     READY(c, CALL_OBSERVE);
-    NEED(c, c->denoiser && c->fr.aovAlbedo && c->fr.aovNormal, "flx_denoise: needs the feature buffers: flx_set_option(ctx, \"denoiser\", 1)");
-    NEED(c, c->fr.nranks == 1, "flx_denoise: the context is partitioned (nranks > 1): a pixel's neighbours are on other ranks -- single-GPU only");
-    flx_denoise_params p = {FLX_DN_DEFAULT_ITERATIONS, FLX_DN_DEFAULT_SIGMA_COLOR, FLX_DN_DEFAULT_SIGMA_NORMAL, FLX_DN_DEFAULT_SIGMA_ALBEDO, 0.0f};
-    if (pp) p = *pp;
-    NEED(c, p.iterations >= 0 && p.iterations <= FLX_DN_MAX_ITERATIONS, "flx_denoise: iterations must be 0..8");
-    NEED(c, dn_finite(p.sigma_color) && p.sigma_color > 0.0f && dn_finite(p.sigma_normal) && p.sigma_normal > 0.0f &&
-            dn_finite(p.sigma_albedo) && p.sigma_albedo > 0.0f, "flx_denoise: sigma_color, sigma_normal and sigma_albedo must be finite and > 0");
-    NEED(c, p.blend == p.blend, "flx_denoise: blend is NaN");
+    NEED(c, c->denoiser && c->fr.aovAlbedo && c->fr.aovNormal, std::string(fn) + ": needs the feature buffers: flx_set_option(ctx, \"denoiser\", 1)");
+    if (moments)
+        NEED(c, c->moments && c->fr.moments, std::string(fn) + ": needs the luminance moments: flx_set_option(ctx, \"moments\", 1)");
+    NEED(c, c->fr.nranks == 1, std::string(fn) + ": the context is partitioned (nranks > 1): a pixel's neighbours are on other ranks -- single-GPU only");
+    NEED(c, iterations >= 0 && iterations <= FLX_DN_MAX_ITERATIONS, std::string(fn) + ": iterations must be 0..8");
+    NEED(c, dn_finite(s0) && s0 > 0.0f && dn_finite(sigma_n) && sigma_n > 0.0f && dn_finite(sigma_a) && sigma_a > 0.0f,
+         std::string(fn) + ": " + sigma0 + ", sigma_normal and sigma_albedo must be finite and > 0");
+    NEED(c, blend == blend, std::string(fn) + ": blend is NaN");
     const int W = (int)c->params.width, H = (int)c->params.height;
-    NEED(c, (uint64_t)W * H == c->fr.localPixels, "flx_denoise: framebuffer does not match width x height");
+    NEED(c, (uint64_t)W * H == c->fr.localPixels, std::string(fn) + ": framebuffer does not match width x height");
     if (!c->dnOut) {
         const size_t n = c->fr.localPixels;
         if (dalloc(c, c->dnAllocs, &c->dnE[0], n) || dalloc(c, c->dnAllocs, &c->dnE[1], n) || dalloc(c, c->dnAllocs, &c->dnG, n) ||
             dalloc(c, c->dnAllocs, &c->dnG2, n) || dalloc(c, c->dnAllocs, &c->dnOut, n * 4)) { freeDenoise(c); return 1; }
     }
     { ScopedTimer t(c, FLX_K_DENOISE);
-      launch_denoise(c->stream, c->fr, c->dnE[0], c->dnE[1], c->dnG, c->dnG2, c->dnOut, W, H, p.iterations, p.sigma_color, p.sigma_normal, p.sigma_albedo,
-                     dn_blend(p.blend), c->params); }
+      launch(c->stream, c->fr, c->dnE[0], c->dnE[1], c->dnG, c->dnG2, c->dnOut, W, H, iterations, s0, sigma_n, sigma_a, dn_blend(blend), c->params); }
     LAUNCHED(c);
     c->dnHave = true;
     return 0;
+}
+
+// DenoiserOptix::denoise (reference: src/denoiser/OptixDenoiser.cpp) as the guided a-trous filter of csrc/flx_denoise.h: reads which = 0 / 4 / 5,
+// writes which = 6 and the preview (which = 1).  Asynchronous; deferred and fused launches are flushed first (CALL_OBSERVE).
+int flx_denoise(flx_ctx *c, const flx_denoise_params *pp)
+{
+    flx_denoise_params p = {FLX_DN_DEFAULT_ITERATIONS, FLX_DN_DEFAULT_SIGMA_COLOR, FLX_DN_DEFAULT_SIGMA_NORMAL, FLX_DN_DEFAULT_SIGMA_ALBEDO, 0.0f};
+    if (pp) p = *pp;
+    return denoiseCall(c, "flx_denoise", launch_denoise<DnGuided>, false, "sigma_color", p.iterations, p.sigma_color, p.sigma_normal, p.sigma_albedo,
+                       p.blend);
 }
 
 // the variance-guided filter of csrc/flx_denoise_vg.h: flx_denoise's inputs plus the luminance moments (which = 7); the same
 // outputs, working set (the variance rides in e.w), timer and flushing.
 int flx_denoise_variance_guided(flx_ctx *c, const flx_denoise_vg_params *pp)
 {
-    READY(c, CALL_OBSERVE);
-    NEED(c, c->denoiser && c->fr.aovAlbedo && c->fr.aovNormal, "flx_denoise_variance_guided: needs the feature buffers: flx_set_option(ctx, \"denoiser\", 1)");
-    NEED(c, c->moments && c->fr.moments, "flx_denoise_variance_guided: needs the luminance moments: flx_set_option(ctx, \"moments\", 1)");
-    NEED(c, c->fr.nranks == 1, "flx_denoise_variance_guided: the context is partitioned (nranks > 1): a pixel's neighbours are on other ranks -- single-GPU only");
     flx_denoise_vg_params p = {FLX_VG_DEFAULT_ITERATIONS, FLX_VG_DEFAULT_SIGMA_LUMINANCE, FLX_VG_DEFAULT_SIGMA_NORMAL, FLX_VG_DEFAULT_SIGMA_ALBEDO, 0.0f};
     if (pp) p = *pp;
-    NEED(c, p.iterations >= 0 && p.iterations <= FLX_DN_MAX_ITERATIONS, "flx_denoise_variance_guided: iterations must be 0..8");
-    NEED(c, dn_finite(p.sigma_luminance) && p.sigma_luminance > 0.0f && dn_finite(p.sigma_normal) && p.sigma_normal > 0.0f &&
-            dn_finite(p.sigma_albedo) && p.sigma_albedo > 0.0f, "flx_denoise_variance_guided: sigma_luminance, sigma_normal and sigma_albedo must be finite and > 0");
-    NEED(c, p.blend == p.blend, "flx_denoise_variance_guided: blend is NaN");
-    const int W = (int)c->params.width, H = (int)c->params.height;
-    NEED(c, (uint64_t)W * H == c->fr.localPixels, "flx_denoise_variance_guided: framebuffer does not match width x height");
-    if (!c->dnOut) {
-        const size_t n = c->fr.localPixels;
-        if (dalloc(c, c->dnAllocs, &c->dnE[0], n) || dalloc(c, c->dnAllocs, &c->dnE[1], n) || dalloc(c, c->dnAllocs, &c->dnG, n) ||
-            dalloc(c, c->dnAllocs, &c->dnG2, n) || dalloc(c, c->dnAllocs, &c->dnOut, n * 4)) { freeDenoise(c); return 1; }
-    }
-    { ScopedTimer t(c, FLX_K_DENOISE);
-      launch_denoise_vg(c->stream, c->fr, c->dnE[0], c->dnE[1], c->dnG, c->dnG2, c->dnOut, W, H, p.iterations, p.sigma_luminance, p.sigma_normal,
-                        p.sigma_albedo, dn_blend(p.blend), c->params); }
-    LAUNCHED(c);
-    c->dnHave = true;
-    return 0;
+    return denoiseCall(c, "flx_denoise_variance_guided", launch_denoise<DnVg>, true, "sigma_luminance", p.iterations, p.sigma_luminance,
+                       p.sigma_normal, p.sigma_albedo, p.blend);
 }
 
 // ---- microkernel integrator.  One path per pixel, framebuffers indexed by the path id: single-GPU only, the pixel

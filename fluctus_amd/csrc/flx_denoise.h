@@ -41,6 +41,10 @@ struct dn_pix { f3 e; f3 n; f3 a; bool valid; };
 FLX_HD bool dn_finite(float v) { return absf(v) <= FLX_FLT_MAX; }
 FLX_HD bool dn_finite3(f3 v) { return dn_finite(v.x) && dn_finite(v.y) && dn_finite(v.z); }
 
+/* the guided filter's part of a pixel, for code shared by both filters (flx_denoise_vg.h: dn_part of a vg_pix) */
+FLX_HD const dn_pix &dn_part(const dn_pix &p) { return p; }
+FLX_HD dn_pix &dn_part(dn_pix &p) { return p; }
+
 /* B3-spline tap of offset t in -2..2 */
 FLX_HD float dn_h(int t) { return t == 0 ? 0.375f : (t == 1 || t == -1) ? 0.25f : 0.0625f; }
 
@@ -79,28 +83,48 @@ FLX_HD float dn_weight(const dn_pix &pi, const dn_pix &pj, int dx, int dy, float
     return q < FLX_DN_EXP_CUT ? hw * expf_(-q) : 0.0f;
 }
 
-/* one pass at pixel (x, y) of a valid centre pi, step s: taps row-major (dy outer, dx inner), the centre included; taps outside the
- * image or on an invalid pixel are skipped and the weights renormalise.  fetch(xj, yj) -> dn_pix of pixel (xj, yj) in this pass' input.
- * The centre tap weighs h[0]^2 > 0, so the sum of weights is never zero. */
+/* the taps of the (2R+1) x (2R+1) stencil at step s around (x, y) that lie inside the W x H image, row-major (dy outer, dx inner), the centre
+ * included: tap(xj, yj, dx, dy) for each.  Every filter loop of this header and of flx_denoise_vg.h is this walk; its order is the summation order. */
+template <int R, class Tap>
+FLX_HD void dn_taps(int x, int y, int W, int H, int s, Tap tap)
+{
+    for (int dy = -R; dy <= R; dy++) {
+        const int yj = y + dy * s;
+        if (yj < 0 || yj >= H) continue;
+        for (int dx = -R; dx <= R; dx++) {
+            const int xj = x + dx * s;
+            if (xj < 0 || xj >= W) continue;
+            tap(xj, yj, dx, dy);
+        }
+    }
+}
+
+/* one pass at pixel (x, y) of a valid centre pi, step s: the 5 x 5 taps of dn_taps; taps on an invalid pixel are skipped and the weights
+ * renormalise.  fetch(xj, yj) -> dn_pix of pixel (xj, yj) in this pass' input.  The centre tap weighs h[0]^2 > 0, so the sum of weights is
+ * never zero. */
 template <class Fetch>
 FLX_HD f3 dn_atrous(int x, int y, int W, int H, int s, const dn_pix &pi, float ic, float in_, float ia, Fetch fetch)
 {
     f3 acc = mk3(0.0f);
     float ws = 0.0f;
-    for (int dy = -2; dy <= 2; dy++) {
-        const int yj = y + dy * s;
-        if (yj < 0 || yj >= H) continue;
-        for (int dx = -2; dx <= 2; dx++) {
-            const int xj = x + dx * s;
-            if (xj < 0 || xj >= W) continue;
-            const dn_pix pj = fetch(xj, yj);
-            if (!pj.valid) continue;
-            const float w = dn_weight(pi, pj, dx, dy, ic, in_, ia);
-            acc = acc + pj.e * w;
-            ws = ws + w;
-        }
-    }
+    dn_taps<2>(x, y, W, H, s, [&](int xj, int yj, int dx, int dy) {
+        const dn_pix pj = fetch(xj, yj);
+        if (!pj.valid) return;
+        const float w = dn_weight(pi, pj, dx, dy, ic, in_, ia);
+        acc = acc + pj.e * w;
+        ws = ws + w;
+    });
     return acc / ws;
+}
+
+/* dn_atrous as both filters call it (flx_denoise_vg.h: the overloads for a vg_pix): a prefiltered variance gv and an out-argument for what
+ * the pass propagates, neither of which the guided filter has */
+template <class Fetch>
+FLX_HD float dn_prefilter(int, int, int, int, const dn_pix &, Fetch) { return 0.0f; }
+template <class Fetch>
+FLX_HD f3 dn_atrous(int x, int y, int W, int H, int s, const dn_pix &pi, float, float ic, float in_, float ia, Fetch fetch, float *)
+{
+    return dn_atrous(x, y, W, H, s, pi, ic, in_, ia, fetch);
 }
 
 /* the finish step: which = 6 of pixel i.  Invalid: the raw accumulation unchanged.  Valid: (out_i, 1) with out_i the blend of c_i and

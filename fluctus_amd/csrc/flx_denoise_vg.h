@@ -4,7 +4,7 @@
  * The spatial filter of SVGF (Schied et al.: "Spatiotemporal Variance-Guided Filtering", HPG 2017) on top of the guided filter of
  * flx_denoise.h: the fixed colour stop is replaced by a luminance stop scaled by a per-pixel estimate of the standard deviation of the
  * pixel mean, which the integrators supply as luminance moments (option "moments", flx_read_pixels which = 7), and the variance is
- * carried through the passes.  The kernels (csrc/denoise.hip) and the CPU counterpart (tests/denoise_vg_cpu.cpp) include this header;
+ * carried through the passes.  The kernels (csrc/denoise.hip) and the CPU counterpart (tests/denoise_cpu.cpp) include this header;
  * their results are BIT-IDENTICAL.  tests/denoise_vg_reference.py restates every formula in float64.
  *
  * Per local pixel i (flat index, W x H image, context unpartitioned), with l(v) = flx_lum(v) (Rec. 709, flx_denoise.h):
@@ -61,6 +61,10 @@ FLX_HD dn_pix vg_prepare(const float px[4], const float alb[4], const float nrm[
 /* one pixel of the working set: the guided filter's pixel and its variance */
 struct vg_pix { dn_pix d; float v; };
 
+/* the guided filter's part of a pixel, for code shared by both filters (flx_denoise.h: dn_part of a dn_pix) */
+FLX_HD const dn_pix &dn_part(const vg_pix &p) { return p.d; }
+FLX_HD dn_pix &dn_part(vg_pix &p) { return p.d; }
+
 FLX_HD float vg_cap(float v) { return v == v ? clampf(v, 0.0f, FLX_VG_VAR_MAX) : FLX_VG_VAR_MAX; }
 
 /* the per-pixel estimate from the moments; false when it does not exist (m < 2, or a non-finite term) */
@@ -84,27 +88,21 @@ FLX_HD float vg_guide_weight(const dn_pix &pi, const dn_pix &pj, float in_, floa
 }
 
 /* the initial variance of a valid centre pi at (x, y): the per-pixel estimate, else the spatial fallback over the valid 3 x 3 neighbours
- * (row-major, the centre included: its weight is 1, so the sum never vanishes).  fetch(xj, yj) -> dn_pix as prepared. */
+ * (the 3 x 3 taps of dn_taps, the centre included: its weight is 1, so the sum never vanishes).  fetch(xj, yj) -> dn_pix as prepared. */
 template <class Fetch>
 FLX_HD float vg_initial_variance(int x, int y, int W, int H, const dn_pix &pi, const float mom[4], float in_, float ia, Fetch fetch)
 {
     float v;
     if (vg_pixel_variance(mom, pi.a, &v)) return v;
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-    for (int dy = -1; dy <= 1; dy++) {
-        const int yj = y + dy;
-        if (yj < 0 || yj >= H) continue;
-        for (int dx = -1; dx <= 1; dx++) {
-            const int xj = x + dx;
-            if (xj < 0 || xj >= W) continue;
-            const dn_pix pj = fetch(xj, yj);
-            if (!pj.valid) continue;
-            const float u = vg_guide_weight(pi, pj, in_, ia), l = flx_lum(pj.e);
-            s0 = s0 + u;
-            s1 = s1 + u * l;
-            s2 = s2 + u * (l * l);
-        }
-    }
+    dn_taps<1>(x, y, W, H, 1, [&](int xj, int yj, int, int) {
+        const dn_pix pj = fetch(xj, yj);
+        if (!pj.valid) return;
+        const float u = vg_guide_weight(pi, pj, in_, ia), l = flx_lum(pj.e);
+        s0 = s0 + u;
+        s1 = s1 + u * l;
+        s2 = s2 + u * (l * l);
+    });
     const float mean = s1 / s0;
     return vg_cap(fmaxf_(s2 / s0 - mean * mean, 0.0f));
 }
@@ -117,19 +115,13 @@ template <class Fetch>
 FLX_HD float vg_prefilter(int x, int y, int W, int H, Fetch fetch)
 {
     float acc = 0.0f, ws = 0.0f;
-    for (int dy = -1; dy <= 1; dy++) {
-        const int yj = y + dy;
-        if (yj < 0 || yj >= H) continue;
-        for (int dx = -1; dx <= 1; dx++) {
-            const int xj = x + dx;
-            if (xj < 0 || xj >= W) continue;
-            const vg_pix pj = fetch(xj, yj);
-            if (!pj.d.valid) continue;
-            const float g = vg_g(dx) * vg_g(dy);
-            acc = acc + g * pj.v;
-            ws = ws + g;
-        }
-    }
+    dn_taps<1>(x, y, W, H, 1, [&](int xj, int yj, int dx, int dy) {
+        const vg_pix pj = fetch(xj, yj);
+        if (!pj.d.valid) return;
+        const float g = vg_g(dx) * vg_g(dy);
+        acc = acc + g * pj.v;
+        ws = ws + g;
+    });
     return acc / ws;
 }
 
@@ -142,32 +134,37 @@ FLX_HD float vg_weight(const dn_pix &pi, float li, const dn_pix &pj, int dx, int
     return q < FLX_DN_EXP_CUT ? hw * expf_(-q) : 0.0f;
 }
 
-/* one pass at a valid centre pi at (x, y), step s, prefiltered variance gv (clamped here by the centre's): the taps, skipping and
- * renormalisation of dn_atrous.
+/* one pass at a valid centre pi at (x, y), step s, prefiltered variance gv (clamped here by the centre's): the 5 x 5 taps, skipping and
+ * renormalisation of the guided dn_atrous, whose overload for a vg_pix this is.  fetch(xj, yj) -> vg_pix.
  * -> the filtered e; *vout the propagated variance.  The centre weighs h[0]^2 > 0, so the sums never vanish. */
 template <class Fetch>
-FLX_HD f3 vg_atrous(int x, int y, int W, int H, int s, const vg_pix &pi, float gv, float sigma_l, float in_, float ia, Fetch fetch, float *vout)
+FLX_HD f3 dn_atrous(int x, int y, int W, int H, int s, const vg_pix &pi, float gv, float sigma_l, float in_, float ia, Fetch fetch, float *vout)
 {
     const float li = flx_lum(pi.d.e), den = sigma_l * sqrtf(fminf_(gv, pi.v)) + FLX_VG_EPS;
     f3 acc = mk3(0.0f);
     float ws = 0.0f, vs = 0.0f;
-    for (int dy = -2; dy <= 2; dy++) {
-        const int yj = y + dy * s;
-        if (yj < 0 || yj >= H) continue;
-        for (int dx = -2; dx <= 2; dx++) {
-            const int xj = x + dx * s;
-            if (xj < 0 || xj >= W) continue;
-            const vg_pix pj = fetch(xj, yj);
-            if (!pj.d.valid) continue;
-            const float w = vg_weight(pi.d, li, pj.d, dx, dy, den, in_, ia);
-            acc = acc + pj.d.e * w;
-            ws = ws + w;
-            vs = vs + (w * w) * pj.v;
-        }
-    }
+    dn_taps<2>(x, y, W, H, s, [&](int xj, int yj, int dx, int dy) {
+        const vg_pix pj = fetch(xj, yj);
+        if (!pj.d.valid) return;
+        const float w = vg_weight(pi.d, li, pj.d, dx, dy, den, in_, ia);
+        acc = acc + pj.d.e * w;
+        ws = ws + w;
+        vs = vs + (w * w) * pj.v;
+    });
     *vout = vg_cap(vs / (ws * ws));
     return acc / ws;
 }
+
+/* the variance-guided pass under its own name */
+template <class Fetch>
+FLX_HD f3 vg_atrous(int x, int y, int W, int H, int s, const vg_pix &pi, float gv, float sigma_l, float in_, float ia, Fetch fetch, float *vout)
+{
+    return dn_atrous(x, y, W, H, s, pi, gv, sigma_l, in_, ia, fetch, vout);
+}
+
+/* the prefilter as the overload of dn_prefilter (flx_denoise.h) for a vg_pix centre */
+template <class Fetch>
+FLX_HD float dn_prefilter(int x, int y, int W, int H, const vg_pix &, Fetch fetch) { return vg_prefilter(x, y, W, H, fetch); }
 
 } /* namespace flx */
 

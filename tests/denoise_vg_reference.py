@@ -1,21 +1,17 @@
 """The variance-guided a-trous denoiser (fluctus_amd/csrc/flx_denoise_vg.h) restated formula by formula in numpy float64,
-the luminance moments the integrators accumulate (option "moments", which = 7), and the helpers the variance-guided tests share: building and
-running the CPU counterpart (tests/denoise_vg_cpu.cpp) and heavy-tailed inputs.
+the luminance moments the integrators accumulate (option "moments", which = 7), and the inputs of the variance-guided tests.  The CPU
+counterpart (tests/denoise_cpu.cpp) is run by denoise_reference.run_cpu with mom=.
 
 The device and the CPU counterpart share one header, so comparing them proves the kernels run the header; comparing the counterpart with
 this restatement proves the header computes what DESIGN.md says."""
-import os
-import subprocess
 import numpy as np
 import denoise_reference as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLT_MAX = float(np.finfo(np.float32).max)
 VAR_MAX = 1e30                  # FLX_VG_VAR_MAX
 EPS = 1e-10                     # FLX_VG_EPS
 EXP_CUT = 87.0                  # FLX_DN_EXP_CUT
 LUM_W = (0.2126, 0.7152, 0.0722)
-DEFAULTS = dict(iterations=5, sigma_luminance=4.0, sigma_normal=0.3, sigma_albedo=0.1, blend=0.0)     # = FLX_VG_DEFAULT_*
 G3 = np.array([0.25, 0.5, 0.25])
 
 
@@ -138,43 +134,6 @@ def denoise_vg64(px, alb, nrm, mom, W, H, iterations, sigma_luminance, sigma_nor
     out[valid, :3] = blend * c[valid] + (1.0 - blend) * d[valid]
     out[valid, 3] = 1.0
     return out
-
-
-# ---- the CPU counterpart
-def build_cpu(outdir):
-    """g++ -O2 -ffp-contract=off tests/denoise_vg_cpu.cpp -> <outdir>/denoise_vg_cpu.  A failed compile raises."""
-    exe = os.path.join(str(outdir), "denoise_vg_cpu")
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tests", "denoise_vg_cpu.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, "denoise_vg_cpu.cpp does not compile:\n" + r.stdout
-    return exe
-
-
-def run_cpu(exe, px, alb, nrm, mom, W, H, iterations=None, sigma_luminance=None, sigma_normal=None, sigma_albedo=None, blend=None,
-            exposure=1.0, tm_operator=0, with_variance=False):
-    """-> (which = 6, preview) of the counterpart, float32 (W*H, 4) each [, initial variance (W*H,)].  None = the library's default."""
-    P = dict(DEFAULTS)
-    for k, v in dict(iterations=iterations, sigma_luminance=sigma_luminance, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo,
-                     blend=blend).items():
-        if v is not None:
-            P[k] = v
-    d = os.path.dirname(exe)
-    fin, fout = os.path.join(d, "vg_in.bin"), os.path.join(d, "vg_out.bin")
-    with open(fin, "wb") as f:
-        f.write(np.array([W, H, P["iterations"]], np.int32).tobytes())
-        f.write(np.array([P["sigma_luminance"], P["sigma_normal"], P["sigma_albedo"], P["blend"], exposure], np.float32).tobytes())
-        f.write(np.array([tm_operator], np.uint32).tobytes())
-        for a in (px, alb, nrm, mom):
-            a = np.ascontiguousarray(a, np.float32).reshape(-1, 4)
-            assert a.shape[0] == W * H
-            f.write(a.tobytes())
-    r = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    raw = np.fromfile(fout, np.float32)
-    o = raw[:W * H * 8].reshape(2, W * H, 4)
-    if with_variance:
-        return o[0].copy(), o[1].copy(), raw[W * H * 8:].copy()
-    return o[0].copy(), o[1].copy()
 
 
 # ---- inputs

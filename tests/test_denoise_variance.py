@@ -1,4 +1,4 @@
-"""The variance-guided a-trous denoiser on the CPU: the CPU counterpart of the kernels (tests/denoise_vg_cpu.cpp, which runs
+"""The variance-guided a-trous denoiser on the CPU: the CPU counterpart of the kernels (tests/denoise_cpu.cpp, which runs
 fluctus_amd/csrc/flx_denoise_vg.h) against the float64 restatement (tests/denoise_vg_reference.py), its edge semantics, and its quality on
 heavy-tailed noise, where the guided filter (flx_denoise) fails.  tests/test_gpu_denoise_variance.py holds the device to the counterpart bit
 for bit and checks the moments the integrators accumulate."""
@@ -10,17 +10,12 @@ import denoise_vg_reference as V
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    return V.build_cpu(tmp_path_factory.mktemp("denoise_vg_cpu"))
-
-
-@pytest.fixture(scope="module")
-def gexe(tmp_path_factory):
-    return R.build_cpu(tmp_path_factory.mktemp("denoise_cpu_for_vg"))
+    return R.build_cpu(tmp_path_factory.mktemp("denoise_cpu"))
 
 
 def _check64(exe, px, alb, nrm, mom, W, H, **kw):
-    got, _, var = V.run_cpu(exe, px, alb, nrm, mom, W, H, with_variance=True, **kw)
-    P = dict(V.DEFAULTS, **kw)
+    got, _, var = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom, with_variance=True, **kw)
+    P = dict(R.VG_DEFAULTS, **kw)
     ref = V.denoise_vg64(px, alb, nrm, mom, W, H, **P)
     var64, _, guided, scale = V.initial_variance64(px, alb, nrm, mom, W, H, P["sigma_normal"], P["sigma_albedo"], with_scale=True)
     valid = R.prepare64(px, alb, nrm)[4]
@@ -85,7 +80,7 @@ def test_initial_variance_cases(exe):
     mom[2] = (0.5, 0.25, 0.0, 1.0)                                  # n = 1: fallback
     mom[12] = (1.0, np.inf, 0.0, 2.0)                               # non-finite: fallback
     mom[13] = (2.0, 1.5, 0.0, 8.0)                                  # n disagrees with pixels.w: the moments' own n
-    _, _, var = V.run_cpu(exe, px, alb, nrm, mom, W, H, iterations=1, with_variance=True)
+    _, _, var = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom, iterations=1, with_variance=True)
     var64, per, _ = V.initial_variance64(px, alb, nrm, mom, W, H, 0.3, 0.1)
     assert np.allclose(var, var64, rtol=1e-5, atol=0)
     la = 0.5
@@ -105,7 +100,7 @@ def test_identity_is_exact(exe, kw):
     px, alb, nrm, mom = _edge_inputs(W, H, 11)
     px[5] = (1.0, 2.0, 3.0, 0.0)                        # no samples: passed through
     alb[6] = (np.inf, 0.0, 0.0, 1.0)                    # non-finite guide: passed through
-    out, _ = V.run_cpu(exe, px, alb, nrm, mom, W, H, **kw)
+    out, _ = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom, **kw)
     with np.errstate(divide="ignore", invalid="ignore"):
         c = px[:, :3] / px[:, 3:4]
     keep = np.ones(W * H, bool); keep[[5, 6]] = False
@@ -119,7 +114,7 @@ def test_invalid_pixels_pass_through_and_do_not_contaminate(exe):
     bad = [3, 50, 51, 200, 201, 640]
     px[3, 3] = 0.0; px[50, 0] = np.nan; px[51, 1] = np.inf; alb[200, 2] = np.inf; nrm[201, 0] = np.nan; px[640, 3] = -1.0
     mom[bad, 0] = 1e30                                  # their moments would dominate any neighbour's variance
-    out, prev = V.run_cpu(exe, px, alb, nrm, mom, W, H, iterations=6)
+    out, prev = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom, iterations=6)
     idx = np.array(sorted(bad))
     assert np.array_equal(out[idx].view(np.uint32), px[idx].view(np.uint32))
     others = np.setdiff1d(np.arange(W * H), idx)
@@ -129,7 +124,7 @@ def test_invalid_pixels_pass_through_and_do_not_contaminate(exe):
     # other values on the (still invalid) bad pixels give the same output everywhere else: they are never neighbours
     px2, mom2 = px.copy(), mom.copy()
     px2[3, :3] = 99.0; px2[50, 1:3] = 55.0; px2[51, 0] = 77.0; px2[640, :3] = -5.0; mom2[bad] = (0.0, 0.0, 0.0, 0.0)
-    out2, _ = V.run_cpu(exe, px2, alb, nrm, mom2, W, H, iterations=6)
+    out2, _ = R.run_cpu(exe, px2, alb, nrm, W, H, mom=mom2, iterations=6)
     assert np.array_equal(out[others].view(np.uint32), out2[others].view(np.uint32))
 
 
@@ -141,11 +136,11 @@ def test_unguided_pixels_return_c_and_are_never_neighbours(exe):
     ung = np.zeros(W * H, bool); ung[[5, 6, 7, 45, 46, 47, 85, 86, 87, 300]] = True
     alb[ung] = (0.1, 0.1, 0.1, 0.0)                                # the resets' placeholder, count 0
     px[ung, :3] = 500.0 * px[ung, 3:4]                              # a bright light
-    out, _ = V.run_cpu(exe, px, alb, nrm, mom, W, H, iterations=5)
+    out, _ = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom, iterations=5)
     c = px[:, :3] / px[:, 3:4]
     assert np.array_equal(out[ung, :3].view(np.uint32), c[ung].view(np.uint32)) and (out[ung, 3] == 1.0).all()
     px2 = px.copy(); px2[ung, :3] = 0.5 * px2[ung, 3:4]
-    out2, _ = V.run_cpu(exe, px2, alb, nrm, mom, W, H, iterations=5)
+    out2, _ = R.run_cpu(exe, px2, alb, nrm, W, H, mom=mom, iterations=5)
     assert np.array_equal(out[~ung].view(np.uint32), out2[~ung].view(np.uint32))
     got, ref, valid, worst, _ = _check64(exe, px, alb, nrm, mom, W, H, iterations=5)
     assert valid.all() and worst <= 1.0, worst
@@ -158,7 +153,7 @@ def test_constant_image_zero_variance_stays_constant(exe):
     nrm = np.tile(np.array([0.0, 0.0, 1.0, 1.0], np.float32), (W * H, 1))
     l = V.lum32(np.array([[0.3, 0.6, 0.9]], np.float32))[0]
     mom = np.tile(np.array([8 * l, 8 * l * l, 0.0, 8.0], np.float32), (W * H, 1))
-    out, _, var = V.run_cpu(exe, px, alb, nrm, mom, W, H, iterations=8, with_variance=True)
+    out, _, var = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom, iterations=8, with_variance=True)
     c = px[0, :3] / px[0, 3]
     assert var.max() < 1e-12
     assert np.allclose(out[:, :3], c, rtol=4 * np.finfo(np.float32).eps, atol=0), np.abs(out[:, :3] - c).max()
@@ -173,7 +168,7 @@ def test_half_planes_stay_apart(exe):
     alb = np.tile(np.array([0.6, 0.6, 0.6, 1.0], np.float32), (W * H, 1))
     nrm = np.zeros((W * H, 4), np.float32); nrm[:, 3] = 1
     nrm[left, 0] = 1.0; nrm[~left, 2] = 1.0
-    out, _ = V.run_cpu(exe, px, alb, nrm, mom, W, H)
+    out, _ = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom)
     mL, mR = out[left, :3].mean(), out[~left, :3].mean()
     assert abs(mL - 0.2) <= 0.02 * (1.5 - 0.2) and abs(mR - 1.5) <= 0.02 * (1.5 - 0.2), (mL, mR)
     assert out[left, :3].std() < 0.5 * (px[left, :3] / 4).std()           # and it did filter
@@ -188,20 +183,20 @@ def test_albedo_checker_keeps_contrast(exe):
     alb = np.zeros((W * H, 4), np.float32); alb[:, :3] = a[:, None]; alb[:, 3] = 1
     nrm = np.tile(np.array([0.0, 1.0, 0.0, 1.0], np.float32), (W * H, 1))
     px, mom = V.accumulate((a[:, None, None] * (1.0 + 0.3 * rng.normal(size=(W * H, 4, 3)))).astype(np.float32))
-    out, _ = V.run_cpu(exe, px, alb, nrm, mom, W, H)
+    out, _ = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom)
     ratio_in = (px[~dark, :3] / 4).mean() / (px[dark, :3] / 4).mean()
     ratio_out = out[~dark, :3].mean() / out[dark, :3].mean()
     assert abs(ratio_out / ratio_in - 1.0) < 0.02, (ratio_in, ratio_out)
 
 
-def test_quality_heavy_tailed(exe, gexe):
+def test_quality_heavy_tailed(exe):
     """4 spp with a mean-1 multiplier that is 40 with probability 1 %: the guided filter keeps the outliers (ratio > 0.8), the
     variance-guided filter spreads them (ratio <= 0.5)"""
     W, H = 96, 64
     px, alb, nrm, mom, clean = V.heavy_tailed(W, H, 8)
     noisy = px[:, :3] / px[:, 3:4]
-    g, _ = R.run_cpu(gexe, px, alb, nrm, W, H)
-    v, _ = V.run_cpu(exe, px, alb, nrm, mom, W, H)
+    g, _ = R.run_cpu(exe, px, alb, nrm, W, H)
+    v, _ = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom)
     rg = R.rmse(g, clean) / R.rmse(noisy, clean)
     rv = R.rmse(v, clean) / R.rmse(noisy, clean)
     print(f"heavy-tailed 4 spp: RMSE ratio guided {rg:.3f}, variance-guided {rv:.3f}")
@@ -216,7 +211,7 @@ def test_sigma_luminance_sweep(exe):
     noisy = px[:, :3] / px[:, 3:4]
     rows = []
     for sl in (0.5, 1.0, 2.0, 4.0, 8.0, 16.0):
-        v, _ = V.run_cpu(exe, px, alb, nrm, mom, W, H, sigma_luminance=sl)
+        v, _ = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom, sigma_luminance=sl)
         rows.append((sl, R.rmse(v, clean) / R.rmse(noisy, clean)))
         print(f"sigma_l {sl:5.1f}: RMSE ratio {rows[-1][1]:.3f}")
     best = dict(rows)

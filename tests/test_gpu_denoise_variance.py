@@ -1,6 +1,6 @@
 """The luminance moments and flx_denoise_variance_guided on the MI355X: the moments the two integrators accumulate
 (exact where the order is fixed, within the atomic-order tolerance against the oracle's splats otherwise), the option changing nothing
-else, the resets, the filter bit-identical to the CPU counterpart (tests/denoise_vg_cpu.cpp), its quality on device renders, the errors
+else, the resets, the filter bit-identical to the CPU counterpart (tests/denoise_cpu.cpp), its quality on device renders, the errors
 and the Tracer's mode."""
 import numpy as np
 import pytest
@@ -8,36 +8,14 @@ import common
 from common import COL, Q
 import denoise_reference as R
 import denoise_vg_reference as V
-from fluctus_amd import host, wire, driver
+from fluctus_amd import host, driver
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    return V.build_cpu(tmp_path_factory.mktemp("denoise_vg_cpu_gpu"))
-
-
-def _same(a, b):
-    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
-
-
-def _tm(p):
-    return dict(exposure=float(p["exposure"]), tm_operator=int(p["tmOperator"]))
-
-
-def _ctx(d, W, H, n=None, denoiser=1, moments=1, env=None, **kw):
-    from fluctus_amd.device import HipContext
-    g = HipContext(n or max(W * H, 64))
-    if denoiser:
-        g.set_option("denoiser", 1)
-    if moments:
-        g.set_option("moments", 1)
-    g.upload_scene(d)
-    if env is not None:
-        g.upload_envmap(env)
-    g.set_params(common.scene_params(d, W, H, **kw))
-    return g
+    return R.build_cpu(tmp_path_factory.mktemp("denoise_vg_cpu_gpu"))
 
 
 # ---- the moments
@@ -45,7 +23,7 @@ def test_microkernel_moments_exact():
     """flx_mk_* step by step: before every splat export Ei; which = 7 equals the float32 sums of flx_lum(Ei) and its square in splat order"""
     d = common.mixed_material_scene()
     W, H = 48, 32
-    g = _ctx(d, W, H, env=host.synthetic_sky(64, 32), maxBounces=4, useAreaLight=1, useEnvMap=1)
+    g = R.ctx(d, W, H, moments=1, env=host.synthetic_sky(64, 32), maxBounces=4, useAreaLight=1, useEnvMap=1)
     p = common.scene_params(d, W, H, maxBounces=4, useAreaLight=1, useEnvMap=1, useRoulette=0)
     g.set_params(p)
     assert g.get_option("moments") == 1
@@ -66,10 +44,10 @@ def test_microkernel_moments_exact():
         ei = np.ascontiguousarray(s[COL.EI:COL.EI + 3, :W * H].T)
         l = V.lum32(ei[hit])
         want[hit, 0] += l; want[hit, 1] += l * l; want[hit, 3] += np.float32(1.0)
-        assert _same(g.read_pixels(7), want), it
+        assert R.same(g.read_pixels(7), want), it
         if it == 2:
             g.mk_splat_preview(); g.finish()                   # a preview splat adds nothing
-            assert _same(g.read_pixels(7), want)
+            assert R.same(g.read_pixels(7), want)
     assert want[:, 3].sum() > 0
 
 
@@ -81,7 +59,7 @@ def test_wavefront_moments_lockstep(sep, overlap):
     d = common.mixed_material_scene()
     w, h, n = 64, 48, 8192
     p = common.scene_params(d, w, h, maxBounces=5, useAreaLight=1, useEnvMap=1, wfSeparateQueues=sep)
-    g, o = _ctx(d, w, h, n=n, env=host.synthetic_sky(64, 32), maxBounces=5, useAreaLight=1, useEnvMap=1, wfSeparateQueues=sep), \
+    g, o = R.ctx(d, w, h, moments=1, n=n, env=host.synthetic_sky(64, 32), maxBounces=5, useAreaLight=1, useEnvMap=1, wfSeparateQueues=sep), \
         OracleContext(n, threads=8)
     g.set_option("extend_tree", 2); g.set_option("overlap", overlap)
     o.upload_scene(d); o.upload_envmap(host.synthetic_sky(64, 32)); o.set_params(p)
@@ -127,19 +105,19 @@ def test_moments_option_changes_nothing_else_wavefront(regroup, sep):
     W, H = 64, 48
     gs = []
     for mom in (0, 0, 1):
-        g = _ctx(d, W, H, n=256, moments=mom, env=host.synthetic_sky(64, 32), maxBounces=4, useAreaLight=1, useEnvMap=1, wfSeparateQueues=sep)
+        g = R.ctx(d, W, H, n=256, moments=mom, env=host.synthetic_sky(64, 32), maxBounces=4, useAreaLight=1, useEnvMap=1, wfSeparateQueues=sep)
         g.set_option("extend_tree", 2); g.set_option("regroup", regroup)
         driver.reset_renderer(g)
         cnts = [driver.benchmark_iteration(g, W * H) for _ in range(12)]
         gs.append((g, cnts))
     (a, ca), (a2, _), (b, cb) = gs
     for which in (0, 4, 5):
-        assert _same(a.read_pixels(which), a2.read_pixels(which)), f"the setup is not deterministic: which = {which} differs with moments off"
+        assert R.same(a.read_pixels(which), a2.read_pixels(which)), f"the setup is not deterministic: which = {which} differs with moments off"
     assert a.get_option("fuse") == 1 and b.get_option("regroup") == regroup
     assert all(np.array_equal(x, y) for x, y in zip(ca, cb))
     for which in (0, 4, 5):
-        assert _same(a.read_pixels(which), b.read_pixels(which)), which
-    assert _same(a.state_export(), b.state_export())
+        assert R.same(a.read_pixels(which), b.read_pixels(which)), which
+    assert R.same(a.state_export(), b.state_export())
     assert b.read_pixels(7)[:, 3].sum() == b.read_pixels(0)[:, 3].sum() > 0
     with pytest.raises(RuntimeError, match="moments"):
         a.read_pixels(7)
@@ -150,20 +128,20 @@ def test_moments_option_changes_nothing_else_microkernel():
     W, H = 64, 48
     gs = []
     for mom in (0, 1):
-        g = _ctx(d, W, H, moments=mom, env=host.synthetic_sky(64, 32), maxBounces=4, useAreaLight=1, useEnvMap=1)
+        g = R.ctx(d, W, H, moments=mom, env=host.synthetic_sky(64, 32), maxBounces=4, useAreaLight=1, useEnvMap=1)
         driver.render_single(g, common.scene_params(d, W, H, maxBounces=4, useAreaLight=1, useEnvMap=1), 4)
         gs.append(g)
     a, b = gs
     for which in (0, 1, 2, 3, 4, 5):
-        assert _same(a.read_pixels(which), b.read_pixels(which)), which
-    assert _same(a.state_export(), b.state_export())
+        assert R.same(a.read_pixels(which), b.read_pixels(which)), which
+    assert R.same(a.state_export(), b.state_export())
     assert (b.read_pixels(7)[:, 3] == 4).all()
 
 
 def test_resets_clear_the_moments():
     d = common.mixed_material_scene()
     W, H = 32, 24
-    g = _ctx(d, W, H, maxBounces=3)
+    g = R.ctx(d, W, H, moments=1, maxBounces=3)
     driver.render_single(g, common.scene_params(d, W, H, maxBounces=3), 2)
     assert g.read_pixels(7)[:, 3].sum() == 2 * W * H
     g.mk_reset(); g.finish()
@@ -177,87 +155,23 @@ def test_resets_clear_the_moments():
 
 
 # ---- the filter: device == CPU counterpart
-def _adversarial(W, H, seed):
-    px, alb, nrm, mom = V.random_inputs(W, H, seed)
-    N = W * H
-    rng = np.random.default_rng(seed + 100)
-    k = max(1, N // 50)
-    for col, vals in ((3, [0.0]), (0, [np.nan]), (1, [np.inf, -np.inf])):
-        idx = rng.choice(N, k, replace=True)
-        px[idx, col] = rng.choice(vals, k)
-    alb[rng.choice(N, k), :3] = 0.0
-    nrm[rng.choice(N, k), :4] = 0.0
-    alb[rng.choice(N, k), 3] = 0.0
-    mom[rng.choice(N, k), 3] = rng.choice([0.0, 1.0, 2.0, 9.0], k)      # n < 2 (fallback), n disagreeing with pixels.w
-    mom[rng.choice(N, k), 1] = np.inf                                   # a non-finite sum of squares
-    mom[rng.choice(N, k), 0] = 3e38
-    mom[rng.choice(N, k), :2] = 0.0                                     # zero variance
-    return px, alb, nrm, mom
-
-
-def _device_vg(g, px, alb, nrm, mom, **kw):
-    g.write_pixels(0, px); g.write_pixels(4, alb); g.write_pixels(5, nrm); g.write_pixels(7, mom)
-    assert _same(g.read_pixels(7), mom)
-    g.denoise_variance_guided(**kw)
-    g.finish()
-    return g.read_pixels(6), g.read_pixels(1)
-
-
 CASES = [(1, 1, 5, 0.0), (1, 37, 3, 0.5), (53, 1, 8, 0.0), (333, 217, 5, 0.0), (333, 217, 0, 0.0), (333, 217, 2, 1.0),
          (333, 217, 8, -0.5), (333, 217, 1, 0.5), (333, 217, 4, 0.0), (1920, 1080, 5, 0.0)]
 
 
 @pytest.mark.parametrize("W,H,K,blend", CASES)
 def test_bit_identical_to_cpu_adversarial(exe, W, H, K, blend):
-    g = _ctx(common.simple_scene(), W, H)
-    px, alb, nrm, mom = _adversarial(W, H, W + H + K)
-    out, prev = _device_vg(g, px, alb, nrm, mom, iterations=K, blend=blend)
-    cout, cprev = V.run_cpu(exe, px, alb, nrm, mom, W, H, iterations=K, blend=blend, **_tm(g.params))
-    assert _same(out, cout), int((out.view(np.uint32) != cout.view(np.uint32)).any(1).sum())
-    assert _same(prev, cprev)
+    R.check_device_vs_cpu_adversarial(exe, common.simple_scene(), W, H, K, blend, moments=True)
 
 
 def test_bit_identical_other_sigmas(exe):
-    W, H = 200, 120
-    for tm, sig in ((1, dict(sigma_luminance=0.5, sigma_normal=2.0, sigma_albedo=1e-3)), (2, dict(sigma_luminance=1e20, sigma_normal=1e-20, sigma_albedo=5.0))):
-        g = _ctx(common.simple_scene(), W, H, tmOperator=tm, exposure=1.7)
-        px, alb, nrm, mom = _adversarial(W, H, tm)
-        out, prev = _device_vg(g, px, alb, nrm, mom, iterations=5, **sig)
-        cout, cprev = V.run_cpu(exe, px, alb, nrm, mom, W, H, iterations=5, **_tm(g.params), **sig)
-        assert _same(out, cout) and _same(prev, cprev), tm
-
-
-def _mk_render(d, W, H, spp, env=None):
-    kw = dict(maxBounces=4, useAreaLight=1, useEnvMap=int(env is not None))
-    g = _ctx(d, W, H, n=W * H, env=env, **kw)
-    driver.render_single(g, common.scene_params(d, W, H, **kw), spp)
-    return g
-
-
-def _wf_render(d, W, H, iters, env=None):
-    g = _ctx(d, W, H, n=W * H, env=env, maxBounces=4, useAreaLight=1, useEnvMap=int(env is not None), wfSeparateQueues=1)
-    g.set_option("extend_tree", 2)
-    driver.reset_renderer(g)
-    for _ in range(iters):
-        driver.benchmark_iteration(g, W * H)
-    return g
+    R.check_device_vs_cpu_sigmas(exe, common.simple_scene(), ((1, dict(sigma_luminance=0.5, sigma_normal=2.0, sigma_albedo=1e-3)),
+                                                              (2, dict(sigma_luminance=1e20, sigma_normal=1e-20, sigma_albedo=5.0))), moments=True)
 
 
 @pytest.mark.parametrize("kind", ["microkernel", "wavefront", "egyptcat"])
 def test_bit_identical_to_cpu_on_device_renders(exe, kind):
-    W, H = 96, 72
-    if kind == "microkernel":
-        g = _mk_render(common.mixed_material_scene(), W, H, 4, env=host.synthetic_sky(64, 32))
-    elif kind == "wavefront":
-        g = _wf_render(common.mixed_material_scene(), W, H, 10, env=host.synthetic_sky(64, 32))
-    else:
-        g = _mk_render(common.egyptcat_scene(), W, H, 2)
-    px, alb, nrm, mom = g.read_pixels(0), g.read_pixels(4), g.read_pixels(5), g.read_pixels(7)
-    for kw in (dict(), dict(iterations=8, blend=0.3)):
-        g.denoise_variance_guided(**kw); g.finish()
-        cout, cprev = V.run_cpu(exe, px, alb, nrm, mom, W, H, **kw, **_tm(g.params))
-        assert _same(g.read_pixels(6), cout) and _same(g.read_pixels(1), cprev), (kind, kw)
-    assert _same(g.read_pixels(0), px) and _same(g.read_pixels(7), mom)
+    R.check_device_vs_cpu_on_render(exe, kind, moments=True)
 
 
 def _ratios(out, px, ref, sel):
@@ -277,11 +191,11 @@ def test_quality_on_device_renders():
     d = common.mixed_material_scene()
     W, H = 80, 60
     env = host.synthetic_sky(64, 32)
-    hig = _mk_render(d, W, H, 512, env=env)
+    hig = R.mk_render(d, W, H, 512, env=env, moments=1)
     hi, hialb = hig.read_pixels(0), hig.read_pixels(4)
     ref = hi[:, :3] / hi[:, 3:4]
     surf_ref = hialb[:, 3] == hi[:, 3]                          # every reference sample hit a surface (none saw the light or the sky)
-    for name, g in (("microkernel 4 spp", _mk_render(d, W, H, 4, env=env)), ("wavefront 10 iterations", _wf_render(d, W, H, 10, env=env))):
+    for name, g in (("microkernel 4 spp", R.mk_render(d, W, H, 4, env=env, moments=1)), ("wavefront 10 iterations", R.wf_render(d, W, H, 10, env=env, moments=1))):
         px = g.read_pixels(0)
         cov = px[:, 3] > 0
         surf = cov & surf_ref
@@ -309,17 +223,17 @@ def test_errors():
     d = common.simple_scene()
     W, H = 32, 16
     z = np.zeros((W * H, 4), np.float32)
-    g = _ctx(d, W, H, moments=0)
+    g = R.ctx(d, W, H, moments=0)
     assert g.get_option("moments") == 0
     for f in (lambda: g.read_pixels(7), lambda: g.write_pixels(7, z), lambda: g.denoise_variance_guided()):
         with pytest.raises(RuntimeError, match='"moments"'):
             f()
     with pytest.raises(RuntimeError, match="which must be 0, 4 or 5"):
         g.write_pixels(1, z)
-    g = _ctx(d, W, H, denoiser=0)
+    g = R.ctx(d, W, H, moments=1, denoiser=0)
     with pytest.raises(RuntimeError, match="denoiser"):
         g.denoise_variance_guided()
-    g = _ctx(d, W, H)
+    g = R.ctx(d, W, H, moments=1)
     for bad in (dict(iterations=-1), dict(iterations=9)):
         with pytest.raises(RuntimeError, match="iterations must be 0..8"):
             g.denoise_variance_guided(**bad)
@@ -341,20 +255,8 @@ def test_errors():
 
 
 # ---- the Tracer
-def _tracer(W=64, H=48):
-    from fluctus_amd.tracer import Tracer
-    t = Tracer(W, H, 0, 4096)
-    t.set_option("extend_tree", 2)
-    t.init(W, H, "proc:kitchen:3000:7")
-    p = t.params
-    wire.look_at(p, (0.0, 1.2, 2.6), (0.0, 0.2, 0.0))
-    p["maxBounces"] = 3
-    t.params = p
-    return t
-
-
 def test_tracer_variance_mode_denoises_at_10_and_20(exe):
-    t = _tracer()
+    t = R.tracer()
     W, H = 64, 48
     t.set_denoiser_mode("variance")
     t.set_denoiser(True)
@@ -364,11 +266,11 @@ def test_tracer_variance_mode_denoises_at_10_and_20(exe):
         t.update()
         px, alb, nrm, mom = t.read_pixels(0), t.read_pixels(4), t.read_pixels(5), t.read_pixels(7)
         assert mom[:, 3].sum() > 0
-        _, plain = V.run_cpu(exe, px, alb, nrm, mom, W, H, iterations=0, **_tm(t.params))
+        _, plain = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom, iterations=0, **R.tm(t.params))
         prev = t.read_pixels(1)
-        if not _same(prev, plain):
-            den, dprev = V.run_cpu(exe, px, alb, nrm, mom, W, H, blend=0.0, **_tm(t.params))
-            assert _same(prev, dprev) and _same(t.read_pixels(6), den), it
+        if not R.same(prev, plain):
+            den, dprev = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom, blend=0.0, **R.tm(t.params))
+            assert R.same(prev, dprev) and R.same(t.read_pixels(6), den), it
             hits.append(it)
     assert hits == [10, 20], hits
     with pytest.raises(ValueError):
@@ -385,16 +287,15 @@ def test_tracer_variance_mode_render_single(exe):
     t.render_single(4, denoise=True)
     px, alb, nrm, mom = t.read_pixels(0), t.read_pixels(4), t.read_pixels(5), t.read_pixels(7)
     assert (mom[:, 3] == 4).all()
-    out, prev = V.run_cpu(exe, px, alb, nrm, mom, W, H, blend=0.25, **_tm(t.params))
-    assert _same(t.read_pixels(6), out) and _same(t.read_pixels(1), prev)
+    out, prev = R.run_cpu(exe, px, alb, nrm, W, H, mom=mom, blend=0.25, **R.tm(t.params))
+    assert R.same(t.read_pixels(6), out) and R.same(t.read_pixels(1), prev)
 
 
-def test_tracer_guided_mode_unchanged(tmp_path):
+def test_tracer_guided_mode_unchanged(exe):
     """the default mode and a mode switched to "variance" and back to "guided" denoise at frames 10 and 20 with flx_denoise itself: which = 6
     and the preview equal the guided filter's CPU counterpart (tests/denoise_cpu.cpp) on the Tracer's own buffers; no moments are made"""
-    gexe = R.build_cpu(tmp_path)
     W, H = 64, 48
-    a, b = _tracer(W, H), _tracer(W, H)
+    a, b = R.tracer(W, H), R.tracer(W, H)
     b.set_denoiser_mode("variance"); b.set_denoiser_mode("guided")
     for t in (a, b):
         t.set_denoiser(True)
@@ -404,8 +305,8 @@ def test_tracer_guided_mode_unchanged(tmp_path):
             t.update()
             if it in (10, 20):
                 px, alb, nrm = t.read_pixels(0), t.read_pixels(4), t.read_pixels(5)
-                out, prev = R.run_cpu(gexe, px, alb, nrm, W, H, blend=0.0, **_tm(t.params))
-                assert _same(t.read_pixels(6), out) and _same(t.read_pixels(1), prev), it
+                out, prev = R.run_cpu(exe, px, alb, nrm, W, H, blend=0.0, **R.tm(t.params))
+                assert R.same(t.read_pixels(6), out) and R.same(t.read_pixels(1), prev), it
     for t in (a, b):
         with pytest.raises(RuntimeError, match="moments"):
             t.read_pixels(7)
