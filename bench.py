@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of the wavefront path-tracing hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, settles, times the K steps, writes --dump-outputs if asked and prints the headline line.  --full adds what
+takes runs of its own behind the timed steps: per-kernel times, the roofline and its untimed counting passes, the multi-GPU tile
+gather and its check, the reference's kernels on the same GPU and the CPU baselines.
 
 Workload (BASELINE.json configs[1]): the kitchen-class scene at 1920x1080, 8 bounces, env-map MIS, separate
 material queues.  Country-Kitchen.obj is a missing blob in the reference checkout, so the scene is the
@@ -75,9 +79,10 @@ def build_workload(width=None, height=None, name="kitchen"):
         d.texdesc = z["texdesc"].view(wire.TEXDESC).reshape(-1); d.texdata = z["texdata"]
     else:
         d = host.generate_scene(gen, tris, seed)
-    # hierarchy cache (the reference's on-disk format, host/bvh.hpp) so that the back-to-back N = 1, 2, 4, 8 runs and the N ranks of
-    # one run do not each spend 10-40 s in the SBVH builder; written atomically, keyed by the generator arguments
-    cache_dir = os.environ.get("FLX_BVH_CACHE", "/tmp/flx_bvh_cache")
+    # optional hierarchy cache (the reference's on-disk format, host/bvh.hpp) for experiments that start many runs on one scene: off
+    # unless FLX_BVH_CACHE names a directory, so a run builds its tree itself and reads nothing an earlier run wrote; written
+    # atomically, keyed by the generator arguments
+    cache_dir = os.environ.get("FLX_BVH_CACHE", "")
     cache = os.path.join(cache_dir, f"hierarchy_{gen.replace(':', '_')}_{tris}_{seed}_{bvh}_{d.tris.size}.bin")
     loaded = False
     if cache_dir and os.path.exists(cache):
@@ -387,8 +392,10 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what they computed as DIR/<name>.npy (float32 / float64, under 64 MB in all): the accumulation image, "
                          "the queue-counter totals of the timed steps and a fixed sample of the path state (rank 0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ref-gpu-baseline", action="store_true", help="skip the untimed leg that runs the reference's own gfx950 kernels on this GPU (ref_gpu_baseline)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure what the headline does not need: per-kernel times, the roofline, "
+                                                         "the multi-GPU tile gather, the reference's kernels on this GPU and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-ref-gpu-baseline", action="store_true", help="with --full: skip the untimed leg that runs the reference's own gfx950 kernels on this GPU (ref_gpu_baseline)")
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--workload", default="kitchen", choices=sorted(WORKLOADS))
@@ -542,6 +549,56 @@ def main():
     ctx.profile_enable(False)
     dumped = dump_outputs(args.dump_outputs, ctxs, np.sum(win_tot, axis=0)) if (args.dump_outputs and rank == 0) else None
 
+    # per window: elapsed = max over ranks, rays = sum over ranks
+    wins = np.array([[e, t[0], t[1], t[2]] for e, t in zip(win_elapsed, win_tot)], dtype=np.float64)      # [window][elapsed, primary, extension, shadow]
+    if use_dist:
+        te = torch.tensor(wins[:, 0].copy(), dtype=torch.float64, device="cuda")
+        dist.all_reduce(te, op=dist.ReduceOp.MAX)
+        tr = torch.tensor(wins[:, 1:].copy(), dtype=torch.float64, device="cuda")
+        dist.all_reduce(tr, op=dist.ReduceOp.SUM)
+        wins = np.concatenate([te.cpu().numpy()[:, None], tr.cpu().numpy()], axis=1)
+    win_mrays = (wins[:, 2] + wins[:, 3]) / wins[:, 0] / 1e6
+    elapsed = float(wins[:, 0].sum())                  # all timed steps
+    prim, ext, sh = float(wins[:, 1].sum()), float(wins[:, 2].sum()), float(wins[:, 3].sum())
+    rays_total = ext + sh
+    ext_all = ext                                      # extension rays of all windows and ranks
+
+    # the headline line: everything in it comes from the setup and the timed steps
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "Mrays/s (primary+shadow) at 1080p, 8 bounces" if args.workload == "kitchen" else f"Mrays/s (primary+shadow), {args.workload}",
+            "value": rays_total / elapsed / 1e6,
+            "unit": "Mrays/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_iterations": settle,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "windows": {"count": nwin, "headline": "all timed steps", "steps": win_steps, "Mrays_s": [float(x) for x in win_mrays],
+                        "ms_per_step": [float(e / n_ * 1e3) for e, n_ in zip(wins[:, 0], win_steps)],
+                        "spread_pct": float((win_mrays.max() - win_mrays.min()) / (rays_total / elapsed / 1e6) * 100.0)},
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "f32", "data": ("real (reference asset egyptcat.obj + .mtl + texture)" if args.workload == "egyptcat" else
+                                     "synthetic (procedural scene, deterministic); environment map: the reference's assets/env_maps/night.hdr" if int(p["useEnvMap"]) else "synthetic (procedural scene, deterministic)"),
+            "config": {"workload": ("kitchen-proc (procedural stand-in for Country Kitchen OBJ), 1920x1080, 8 bounces, env-map MIS under night.hdr, "
+                                    "separate material queues") if args.workload == "kitchen" else
+                                   ("egyptcat.obj (REAL reference asset, reference benchmark protocol: 1024x1024, start-up parameters, single material queue)" if args.workload == "egyptcat" else args.workload + "-proc"),
+                       "width": args.width, "height": args.height, "max_bounces": int(p["maxBounces"]), "triangles": int(d.tris.size),
+                       "bvh": WORKLOADS[args.workload][3], "bvh_nodes": int(d.nodes.size), "num_tasks_per_gpu": args.num_tasks, "num_tasks_whole_job": args.num_tasks * world, "scaling_mode": ("weak: --num-tasks paths in flight per rank" if args.scaling == "weak" else f"strong: {num_tasks_total} paths in flight over the whole job, {args.num_tasks} per rank"), "wavefronts_per_gpu": C, "fused_logic_materials": bool(args.fuse), "fused_bsdf_set": ctx.get_option("fuse_set_now") if args.fuse else 0, "ext_order": ctx.get_option("ext_order") if args.fuse else 0,
+                       "refill_extend": ctx.get_option("refill_extend"), "refill_shadow": ctx.get_option("refill_shadow"), "shadow_split": ctx.get_option("shadow_split"), "overlap": ctx.get_option("overlap"), "regroup": ctx.get_option("regroup"),
+                       "parallelism": f"pixel-interleaved x{world}, no collective in the timed region"},
+            "rays": {"primary": prim, "extension": ext, "shadow": sh,
+                     "reference_style_total_Mrays_s": (prim + ext + sh) / elapsed / 1e6},
+        }
+        if dumped:
+            line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": [n_ + ".npy" for n_ in dumped]}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below runs behind the timed steps, on the steady state they left
     tot = np.sum(win_tot, axis=0)                     # all windows: what the event-timed kernel averages cover
     prof = ctx.profile_get()
     # kernels not timed inside the timed region (--kernel-timing 2 times only the trace kernels there, 0 none): averages from
@@ -567,19 +624,6 @@ def main():
     alone_ms, alone_n = ctx.profile_get()["extend"]
     ctx.set_option("overlap", args.overlap)
     ctx.counter_totals(reset=True)
-    # per window: elapsed = max over ranks, rays = sum over ranks
-    wins = np.array([[e, t[0], t[1], t[2]] for e, t in zip(win_elapsed, win_tot)], dtype=np.float64)      # [window][elapsed, primary, extension, shadow]
-    if use_dist:
-        te = torch.tensor(wins[:, 0].copy(), dtype=torch.float64, device="cuda")
-        dist.all_reduce(te, op=dist.ReduceOp.MAX)
-        tr = torch.tensor(wins[:, 1:].copy(), dtype=torch.float64, device="cuda")
-        dist.all_reduce(tr, op=dist.ReduceOp.SUM)
-        wins = np.concatenate([te.cpu().numpy()[:, None], tr.cpu().numpy()], axis=1)
-    win_mrays = (wins[:, 2] + wins[:, 3]) / wins[:, 0] / 1e6
-    elapsed = float(wins[:, 0].sum())                  # all timed steps
-    prim, ext, sh = float(wins[:, 1].sum()), float(wins[:, 2].sum()), float(wins[:, 3].sum())
-    rays_total = ext + sh
-    ext_all = ext                                      # extension rays of all windows and ranks
 
     # ---- roofline of the dominant kernel (traceExtension): algorithmic bytes / HIP-event time
     # visit counts come from an UNTIMED pass of the counting kernel variants over the same steady state
@@ -841,33 +885,9 @@ def main():
                 "simd_efficiency_reference_traversal": simd,
                 "concurrent_traversal_span_ms": (span_ms / span_n) if span_n else None}
     if rank == 0:
-        line = {
-            "metric": "Mrays/s (primary+shadow) at 1080p, 8 bounces" if args.workload == "kitchen" else f"Mrays/s (primary+shadow), {args.workload}",
-            "value": rays_total / elapsed / 1e6,
-            "unit": "Mrays/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_iterations": settle,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "windows": {"count": nwin, "headline": "all timed steps", "steps": win_steps, "Mrays_s": [float(x) for x in win_mrays],
-                        "ms_per_step": [float(e / n_ * 1e3) for e, n_ in zip(wins[:, 0], win_steps)],
-                        "spread_pct": float((win_mrays.max() - win_mrays.min()) / (rays_total / elapsed / 1e6) * 100.0)},
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f32", "data": ("real (reference asset egyptcat.obj + .mtl + texture)" if args.workload == "egyptcat" else
-                                     "synthetic (procedural scene, deterministic); environment map: the reference's assets/env_maps/night.hdr" if int(p["useEnvMap"]) else "synthetic (procedural scene, deterministic)"),
-            "config": {"workload": ("kitchen-proc (procedural stand-in for Country Kitchen OBJ), 1920x1080, 8 bounces, env-map MIS under night.hdr, "
-                                    "separate material queues") if args.workload == "kitchen" else
-                                   ("egyptcat.obj (REAL reference asset, reference benchmark protocol: 1024x1024, start-up parameters, single material queue)" if args.workload == "egyptcat" else args.workload + "-proc"),
-                       "width": args.width, "height": args.height, "max_bounces": int(p["maxBounces"]), "triangles": int(d.tris.size),
-                       "bvh": WORKLOADS[args.workload][3], "bvh_nodes": int(d.nodes.size), "num_tasks_per_gpu": args.num_tasks, "num_tasks_whole_job": args.num_tasks * world, "scaling_mode": ("weak: --num-tasks paths in flight per rank" if args.scaling == "weak" else f"strong: {num_tasks_total} paths in flight over the whole job, {args.num_tasks} per rank"), "wavefronts_per_gpu": C, "fused_logic_materials": bool(args.fuse), "fused_bsdf_set": ctx.get_option("fuse_set_now") if args.fuse else 0, "ext_order": ctx.get_option("ext_order") if args.fuse else 0,
-                       "refill_extend": ctx.get_option("refill_extend"), "refill_shadow": ctx.get_option("refill_shadow"), "shadow_split": ctx.get_option("shadow_split"), "overlap": ctx.get_option("overlap"), "regroup": ctx.get_option("regroup"),
-                       "parallelism": f"pixel-interleaved x{world}, no collective in the timed region"},
-            "rays": {"primary": prim, "extension": ext, "shadow": sh,
-                     "reference_style_total_Mrays_s": (prim + ext + sh) / elapsed / 1e6},
-            "kernel_ms_avg": {k: (v[0] / v[1] if v[1] else None) for k, v in prof.items() if v[1]},
-            "kernel_ms_avg_source": {"timed_region": sorted(k for k, v in prof.items() if v[1] and k not in untimed), "extra_untimed_pass": sorted(untimed)},
-            "roofline": roofline,
-        }
-        if dumped:
-            line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": [n_ + ".npy" for n_ in dumped]}
+        line["kernel_ms_avg"] = {k: (v[0] / v[1] if v[1] else None) for k, v in prof.items() if v[1]}
+        line["kernel_ms_avg_source"] = {"timed_region": sorted(k for k, v in prof.items() if v[1] and k not in untimed), "extra_untimed_pass": sorted(untimed)}
+        line["roofline"] = roofline
         if gather_ms is not None:
             line["gather_ms"] = gather_ms
             line["gather_matches_read_pixels"] = gather_ok

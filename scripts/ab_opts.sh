@@ -4,7 +4,7 @@
 COMMON=$1; shift
 for rep in 1 2; do
 for o in "$@"; do
-  python bench.py --steps 30 --warmup 24 --windows 1 --no-cpu-baseline --kernel-timing 1 --overlap 0 $COMMON $o 2>/dev/null | python -c "
+  python bench.py --full --steps 30 --warmup 24 --windows 1 --no-cpu-baseline --kernel-timing 1 --overlap 0 $COMMON $o 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

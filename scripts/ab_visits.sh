@@ -2,7 +2,7 @@
 ARGS=$1; shift
 for n in "$@"; do
   if [ "$n" = shipped ]; then unset FLX_HIP_LIB; else export FLX_HIP_LIB=$PWD/variants/libfluctus_hip_$n.so; fi
-  python bench.py --steps 30 --warmup 24 --no-cpu-baseline --kernel-timing 1 --overlap 0 $ARGS 2>/dev/null | python -c "
+  python bench.py --full --steps 30 --warmup 24 --no-cpu-baseline --kernel-timing 1 --overlap 0 $ARGS 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,4 +1,4 @@
-run() { timeout 300 python bench.py --steps 40 --warmup 16 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+run() { timeout 300 python bench.py --full --steps 40 --warmup 16 --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys,json,os
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,5 +1,5 @@
 for t in 3000 30000 150000 495648; do
-  FLX_BENCH_TRIS=$t timeout 300 python bench.py --steps 40 --warmup 16 --no-cpu-baseline --overlap 0 2>/dev/null | python -c "
+  FLX_BENCH_TRIS=$t timeout 300 python bench.py --full --steps 40 --warmup 16 --no-cpu-baseline --overlap 0 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

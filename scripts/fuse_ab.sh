@@ -3,7 +3,7 @@ set -u
 mkdir -p gpurun_out
 run() {  # name args
   n=$1; shift
-  python bench.py --steps 30 --warmup 24 --no-cpu-baseline --kernel-timing 1 --overlap 0 "$@" 2>/dev/null | python -c "
+  python bench.py --full --steps 30 --warmup 24 --no-cpu-baseline --kernel-timing 1 --overlap 0 "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

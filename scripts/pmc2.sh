@@ -5,7 +5,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/pmc2_$TAG
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 12 --warmup 16 --windows 1 --no-cpu-baseline --kernel-timing 0 $*"
+CMD="python $REPO/bench.py --full --steps 12 --warmup 16 --windows 1 --no-cpu-baseline --kernel-timing 0 $*"
 cd /tmp
 i=0
 for set in "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAVES" \

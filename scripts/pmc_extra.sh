@@ -5,7 +5,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 12 --warmup 16 --no-cpu-baseline $*"
+CMD="python $REPO/bench.py --full --steps 12 --warmup 16 --no-cpu-baseline $*"
 cd /tmp
 i=0
 for set in "TA_TA_BUSY_sum TA_FLAT_READ_WAVEFRONTS_sum" \

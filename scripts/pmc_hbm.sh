@@ -5,7 +5,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/pmchbm_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 12 --warmup 16 --no-cpu-baseline $*"
+CMD="python $REPO/bench.py --full --steps 12 --warmup 16 --no-cpu-baseline $*"
 cd /tmp
 i=0
 for set in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum" "FETCH_SIZE" "WRITE_SIZE"; do

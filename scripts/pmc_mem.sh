@@ -5,7 +5,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/pmcmem_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 12 --warmup 16 --no-cpu-baseline $*"
+CMD="python $REPO/bench.py --full --steps 12 --warmup 16 --no-cpu-baseline $*"
 cd /tmp
 i=0
 for set in "TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum" \

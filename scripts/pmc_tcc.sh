@@ -5,7 +5,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/pmctcc_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 12 --warmup 16 --no-cpu-baseline $*"
+CMD="python $REPO/bench.py --full --steps 12 --warmup 16 --no-cpu-baseline $*"
 cd /tmp
 i=0
 for set in "TCC_IB_STALL_sum TCC_IB_REQ_sum" "TCC_SRC_FIFO_FULL_sum TCC_LATENCY_FIFO_FULL_sum" "TCC_BUBBLE_sum TCC_CYCLE_sum" "TCC_TAG_STALL_sum TCC_REQ_sum" \

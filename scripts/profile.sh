@@ -7,7 +7,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 20 --warmup 16 --no-cpu-baseline"
+CMD="python $REPO/bench.py --full --steps 20 --warmup 16 --no-cpu-baseline"
 cd /tmp
 timeout -k 5 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/trace.log 2>&1
 # counters: one pass each (TCC slot limits), kernel-trace only

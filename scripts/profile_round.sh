@@ -1,6 +1,6 @@
 #!/bin/bash
 # Capture for one workload: scripts/profile_round.sh <round tag, e.g. r04> <workload> [extra bench args]
-#   (1) rocprofv3 --kernel-trace --stats of `python bench.py --workload <w>` (the bench line is kept beside it)
+#   (1) rocprofv3 --kernel-trace --stats of `python bench.py --full --workload <w>` (the bench line is kept beside it)
 #   (2) fabric-side request counters of the traversal kernels, separate --pmc passes with --kernel-trace only (the guide's HBM recipe:
 #       request counts by size; = 2 x FETCH_SIZE + WRITE_SIZE with the gfx950 correction)  -> profiles/traffic_<workload>.json
 #   (3) SQ counters of the traversal kernels (instructions, lanes per instruction, waits)
@@ -12,7 +12,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/prof_${TAG}_$W
 rm -rf $OUT; mkdir -p $OUT $REPO/profiles
 export TMPDIR=/tmp
-CMD="python $REPO/bench.py --workload $W --steps 20 --warmup 16 --windows 1 --no-cpu-baseline --no-ref-gpu-baseline $*"      # (the reference's OpenCL kernels are not what is profiled here)
+CMD="python $REPO/bench.py --full --workload $W --steps 20 --warmup 16 --windows 1 --no-cpu-baseline --no-ref-gpu-baseline $*"      # (the reference's OpenCL kernels are not what is profiled here)
 cd /tmp
 timeout -k 5 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/trace.log 2>&1
 grep '^{' $OUT/trace.log > $REPO/profiles/${TAG}_${W}_bench.json

@@ -1,7 +1,7 @@
 #!/bin/bash
 # quick A/B of bench variants on the GPU box: scripts/sweep.sh "<args1>" "<args2>" ...
 for a in "$@"; do
-  python bench.py --steps 40 --warmup 20 --no-cpu-baseline $a 2>/dev/null | python -c "
+  python bench.py --full --steps 40 --warmup 20 --no-cpu-baseline $a 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -126,7 +126,7 @@ def test_bench_rccl_path_single_rank(tmp_path):
     port = 29600 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "3",
-           "--num-tasks", "262144", "--width", "640", "--height", "360", "--no-cpu-baseline", "--scaling", "strong"]
+           "--num-tasks", "262144", "--width", "640", "--height", "360", "--no-cpu-baseline", "--scaling", "strong", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -80,7 +80,7 @@ def test_bench_exits_nonzero_when_the_native_gather_fails(tmp_path):
                FLX_RCCL_LIB=FAKE, FLX_ALLOW_RCCL_OVERRIDE="1", FAKE_RCCL_BREAK="4", FLX_NO_BUILD="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29571", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--width", "320",
-           "--height", "180", "--num-tasks", "65536", "--no-cpu-baseline"]
+           "--height", "180", "--num-tasks", "65536", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert lines, r.stdout[-2000:] + r.stderr[-2000:]
