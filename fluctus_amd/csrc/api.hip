@@ -6,6 +6,7 @@
 #include "flx_trace4.h"
 #include "flx_denoise.h"
 #include "flx_denoise_vg.h"
+#include "flx_reproject.h"
 #include "../../include/fluctus_hip.h"
 #include <string>
 #include <vector>
@@ -52,6 +53,8 @@ void launch_deinterleave(hipStream_t, const float *, float *, uint32_t, uint32_t
 struct DnGuided; struct DnVg;     // the two filters of denoise.hip
 template <class F> void launch_denoise(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float,
                                        float, const flx_render_params &);
+void launch_gbuffer(hipStream_t, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, float4 *, uint32_t);
+void launch_reproject(hipStream_t, const rp_view &, const rp_params &, const float4 *, const float4 *, const float4 *, const float4 *, float4 *, float4 *);
 }
 
 using namespace flxd;
@@ -146,6 +149,12 @@ struct flx_ctx {
     bool dnHave = false;
     int moments = 0;            // option "moments": the splats accumulate the luminance moments (Frame::moments, which = 7)
     std::vector<void *> momAllocs;
+    // temporal reprojection (reproject.hip).  Two G-buffer slots of 2 float4 per pixel, [0] current, [1] previous, each with the
+    // camera and the size it was traced with; allocated by the first flx_gbuffer / flx_gbuffer_write, freed with the framebuffers.
+    // hist / histMom: the accumulation and the moments as flx_history_capture copied them (histMom null: "moments" was off then)
+    std::vector<void *> gbAllocs;
+    float4 *gb[2] = {nullptr, nullptr}; flx_camera gbCam[2] = {}; uint32_t gbW[2] = {0, 0}, gbH[2] = {0, 0}; bool gbTraced[2] = {false, false};
+    float4 *hist = nullptr, *histMomBuf = nullptr; bool histHave = false, histHasMom = false;
     int nodeLayout = 1;         // 1 = sibling-pair record numbering (see flx_upload_scene), 0 = DFS
     int numCUs = 256;
     // multi-GPU group (flx_group_*): RCCL communicator of this rank, root-side staging
@@ -239,12 +248,21 @@ static int allocAov(flx_ctx *c)
     return 0;
 }
 
+// the G-buffer slots and the captured history go with the framebuffers
+static void freeTemporal(flx_ctx *c)
+{
+    freeAll(c->gbAllocs);
+    c->gb[0] = c->gb[1] = nullptr; c->hist = c->histMomBuf = nullptr;
+    c->gbTraced[0] = c->gbTraced[1] = false; c->histHave = c->histHasMom = false;
+}
+
 static int allocFrame(flx_ctx *c)
 {
     uint32_t lp = localPixels(c);
     if (lp == c->fr.localPixels && c->fr.pixels) return 0;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     freeDenoise(c);
+    freeTemporal(c);
     freeAll(c->frameAllocs);
     HIPCHK(c, dalloc(c, c->frameAllocs, &c->fr.pixels, (size_t)lp * 4) ? hipErrorOutOfMemory : hipSuccess);
     HIPCHK(c, dalloc(c, c->frameAllocs, &c->fr.preview, (size_t)lp * 4) ? hipErrorOutOfMemory : hipSuccess);
@@ -412,7 +430,7 @@ int flx_destroy(flx_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) { flx_group_destroy(c); }
     freeAll(c->gatherAllocs);
-    freeAll(c->sceneAllocs); freeAll(c->spillAllocs); freeAll(c->envAllocs); freeAll(c->frameAllocs); freeAll(c->aovAllocs); freeAll(c->dnAllocs); freeAll(c->momAllocs); freeAll(c->fixedAllocs);
+    freeAll(c->sceneAllocs); freeAll(c->spillAllocs); freeAll(c->envAllocs); freeAll(c->frameAllocs); freeAll(c->aovAllocs); freeAll(c->dnAllocs); freeAll(c->momAllocs); freeAll(c->gbAllocs); freeAll(c->fixedAllocs);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pinnedIdx) (void)hipHostFree(c->pinnedIdx);
     if (c->pinnedMk) (void)hipHostFree(c->pinnedMk);
@@ -1010,6 +1028,102 @@ int flx_denoise_variance_guided(flx_ctx *c, const flx_denoise_vg_params *pp)
     if (pp) p = *pp;
     return denoiseCall(c, "flx_denoise_variance_guided", launch_denoise<DnVg>, true, "sigma_luminance", p.iterations, p.sigma_luminance,
                        p.sigma_normal, p.sigma_albedo, p.blend);
+}
+
+// ---- temporal reprojection (csrc/flx_reproject.h, reproject.hip).  All of it needs an unpartitioned context: a pixel's
+// neighbours must be local.  Every entry point flushes deferred and fused launches first (CALL_OBSERVE) and touches no path state, queue or counter.
+static int temporalReady(flx_ctx *c, const char *fn)
+{
+    NEED(c, c->haveParams && c->fr.pixels, std::string(fn) + ": set params first (flx_set_params)");
+    NEED(c, c->fr.nranks == 1, std::string(fn) + ": the context is partitioned (nranks > 1): a pixel's neighbours are on other ranks -- single-GPU only");
+    NEED(c, (uint64_t)c->params.width * c->params.height == c->fr.localPixels, std::string(fn) + ": framebuffer does not match width x height");
+    return 0;
+}
+static int gbufferSlots(flx_ctx *c)
+{
+    if (c->gb[0]) return 0;
+    const size_t n = (size_t)c->fr.localPixels * 2;
+    if (dalloc(c, c->gbAllocs, &c->gb[0], n) || dalloc(c, c->gbAllocs, &c->gb[1], n)) { freeTemporal(c); return 1; }
+    return 0;
+}
+int flx_gbuffer(flx_ctx *c)
+{
+    READY(c, CALL_OBSERVE);
+    if (temporalReady(c, "flx_gbuffer") || gbufferSlots(c)) return 1;
+    { ScopedTimer t(c, FLX_K_GBUFFER);
+      launch_gbuffer(c->stream, c->sc, c->params, c->spill, c->numTasks, (c->extendTree == 4 && c->wideOK) ? 4 : 2, c->gb[0], c->fr.localPixels); }
+    LAUNCHED(c);
+    c->gbCam[0] = c->params.camera; c->gbW[0] = c->params.width; c->gbH[0] = c->params.height; c->gbTraced[0] = true;
+    return 0;
+}
+int flx_history_capture(flx_ctx *c)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (temporalReady(c, "flx_history_capture")) return 1;
+    NEED(c, c->gb[0] && c->gbTraced[0], "flx_history_capture: no G-buffer has been traced for the current slot (flx_gbuffer first)");
+    NEED(c, c->gbW[0] == c->params.width && c->gbH[0] == c->params.height, "flx_history_capture: the image size differs from the G-buffer's");
+    const size_t n = c->fr.localPixels;
+    const bool withMom = c->moments && c->fr.moments;
+    // (the moments' copy is allocated when first needed; a failed allocation releases slots and history together, so a retry starts clean)
+    if ((!c->hist && dalloc(c, c->gbAllocs, &c->hist, n)) || (withMom && !c->histMomBuf && dalloc(c, c->gbAllocs, &c->histMomBuf, n))) {
+        const std::string why = c->err; freeTemporal(c); c->err = "flx_history_capture: " + why; return 1;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->hist, c->fr.pixels, n * 16, hipMemcpyDeviceToDevice, c->stream));
+    c->histHasMom = withMom;
+    if (c->histHasMom) HIPCHK(c, hipMemcpyAsync(c->histMomBuf, c->fr.moments, n * 16, hipMemcpyDeviceToDevice, c->stream));
+    std::swap(c->gb[0], c->gb[1]);
+    c->gbCam[1] = c->gbCam[0]; c->gbW[1] = c->gbW[0]; c->gbH[1] = c->gbH[0]; c->gbTraced[1] = true;
+    c->gbTraced[0] = false;
+    c->histHave = true;
+    return 0;
+}
+int flx_reproject(flx_ctx *c, const flx_reproject_params *pp)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (temporalReady(c, "flx_reproject")) return 1;
+    rp_params rp = {FLX_RP_DEFAULT_MAX_HISTORY, FLX_RP_DEFAULT_PLANE_TOLERANCE_PX, FLX_RP_DEFAULT_NORMAL_COS, FLX_RP_DEFAULT_MIN_WEIGHT};
+    if (pp) { rp.max_history = pp->max_history; rp.plane_tolerance_px = pp->plane_tolerance_px; rp.normal_cos = pp->normal_cos; rp.min_weight = pp->min_weight; }
+    NEED(c, rp_params_ok(rp), "flx_reproject: parameters must be finite with max_history >= 1, plane_tolerance_px > 0, normal_cos in [-1, 1], min_weight in (0, 1]");
+    NEED(c, c->histHave && c->gbTraced[1], "flx_reproject: no captured history (flx_history_capture first)");
+    NEED(c, c->gbTraced[0], "flx_reproject: no G-buffer has been traced for the current camera (flx_gbuffer first)");
+    NEED(c, c->gbW[0] == c->params.width && c->gbH[0] == c->params.height && c->gbW[1] == c->gbW[0] && c->gbH[1] == c->gbH[0],
+         "flx_reproject: the image size changed between the capture and the reprojection");
+    const flx_camera &pc = c->gbCam[1];
+    const rp_view vw = rp_make_view(mk3(pc.pos.x, pc.pos.y, pc.pos.z), mk3(pc.dir.x, pc.dir.y, pc.dir.z), mk3(pc.up.x, pc.up.y, pc.up.z), mk3(pc.right.x, pc.right.y, pc.right.z), pc.fov, c->gbCam[0].fov, (int)c->params.width, (int)c->params.height);
+    const bool mom = c->moments && c->fr.moments && c->histHasMom;
+    { ScopedTimer t(c, FLX_K_REPROJECT);
+      launch_reproject(c->stream, vw, rp, c->gb[0], c->gb[1], c->hist, c->histMomBuf, reinterpret_cast<float4 *>(c->fr.pixels),
+                       mom ? reinterpret_cast<float4 *>(c->fr.moments) : nullptr); }
+    LAUNCHED(c);
+    return 0;
+}
+// test hooks in the spirit of flx_state_import: slot 0 = current, 1 = previous; 8 floats per pixel (G0, G1) and the slot's 80-byte camera.  Blocking.
+int flx_gbuffer_read(flx_ctx *c, int slot, float *out8, void *camera80)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, slot == 0 || slot == 1, "flx_gbuffer_read: slot must be 0 (current) or 1 (previous)");
+    NEED(c, out8, "flx_gbuffer_read: null output");
+    NEED(c, c->gb[slot] && c->gbTraced[slot], "flx_gbuffer_read: the slot holds no G-buffer");
+    HIPCHK(c, hipMemcpyAsync(out8, c->gb[slot], (size_t)c->gbW[slot] * c->gbH[slot] * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (camera80) memcpy(camera80, &c->gbCam[slot], sizeof(flx_camera));
+    return 0;
+}
+int flx_gbuffer_write(flx_ctx *c, int slot, const float *in8, const void *camera80)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, slot == 0 || slot == 1, "flx_gbuffer_write: slot must be 0 (current) or 1 (previous)");
+    NEED(c, in8 && camera80, "flx_gbuffer_write: null G-buffer or camera");
+    if (temporalReady(c, "flx_gbuffer_write") || gbufferSlots(c)) return 1;
+    HIPCHK(c, hipMemcpyAsync(c->gb[slot], in8, (size_t)c->fr.localPixels * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(&c->gbCam[slot], camera80, sizeof(flx_camera));
+    c->gbW[slot] = c->params.width; c->gbH[slot] = c->params.height; c->gbTraced[slot] = true;
+    return 0;
 }
 
 // ---- microkernel integrator.  One path per pixel, framebuffers indexed by the path id: single-GPU only, the pixel

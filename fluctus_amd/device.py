@@ -22,10 +22,11 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_trace_stats_enable", "flx_trace_stats_get", "flx_trace_stats_get_ex", "flx_trace_stats_get_all", "flx_scene_info", "flx_trace_stats_reset", "flx_state_export", "flx_state_import", "flx_math_probe", "flx_env_sample_table",
            "flx_queue_read", "flx_queue_write", "flx_set_counters", "flx_set_option", "flx_get_option", "flx_mk_reset", "flx_mk_raygen", "flx_mk_next_vertex",
            "flx_mk_sample_bsdf", "flx_mk_splat", "flx_mk_splat_preview", "flx_mk_stats_async", "flx_mk_stats_reset", "flx_write_pixels", "flx_denoise",
-           "flx_denoise_variance_guided"]
+           "flx_denoise_variance_guided", "flx_gbuffer", "flx_history_capture", "flx_reproject", "flx_gbuffer_read", "flx_gbuffer_write"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
 K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with HipContext.denoise_profile (not part of profile_get)
+K_GBUFFER, K_REPROJECT = 10, 11      # FLX_K_GBUFFER / FLX_K_REPROJECT: profile level 1, read with HipContext.kernel_profile
 
 
 class DenoiseParams(C.Structure):
@@ -44,6 +45,15 @@ class DenoiseVgParams(C.Structure):
 
 # the library's defaults (FLX_VG_DEFAULT_*, csrc/flx_denoise_vg.h)
 DENOISE_VG_DEFAULTS = dict(iterations=5, sigma_luminance=4.0, sigma_normal=0.3, sigma_albedo=0.1, blend=0.0)
+
+
+class ReprojectParams(C.Structure):
+    """flx_reproject_params (include/fluctus_hip.h)"""
+    _fields_ = [("max_history", C.c_float), ("plane_tolerance_px", C.c_float), ("normal_cos", C.c_float), ("min_weight", C.c_float)]
+
+
+# the library's defaults (FLX_RP_DEFAULT_*, csrc/flx_reproject.h; DESIGN.md 4.3.3)
+REPROJECT_DEFAULTS = dict(max_history=32.0, plane_tolerance_px=2.0, normal_cos=0.9, min_weight=0.01)
 
 
 def _preload_torch_runtime():
@@ -216,6 +226,51 @@ class HipContext:
         P = dict(DENOISE_VG_DEFAULTS, **params)
         dp = DenoiseVgParams(int(P["iterations"]), float(P["sigma_luminance"]), float(P["sigma_normal"]), float(P["sigma_albedo"]), float(P["blend"]))
         self._chk(self.L.flx_denoise_variance_guided(self.h, C.byref(dp)))
+
+    # temporal reprojection (include/fluctus_hip.h)
+    def gbuffer(self):
+        """flx_gbuffer (asynchronous): the primary-visibility G-buffer of the current camera into the current slot"""
+        self._chk(self.L.flx_gbuffer(self.h))
+
+    def history_capture(self):
+        """flx_history_capture: copies of which = 0 (and 7); the current G-buffer slot becomes the previous one"""
+        self._chk(self.L.flx_history_capture(self.h))
+
+    def reproject(self, **params):
+        """flx_reproject (asynchronous): max_history, plane_tolerance_px, normal_cos, min_weight; missing ones take the defaults, no keyword at
+        all passes NULL.  Overwrites which = 0 (and 7) with the captured history resampled into the current view."""
+        unknown = set(params) - set(REPROJECT_DEFAULTS)
+        if unknown:
+            raise TypeError(f"reproject: unknown parameters {sorted(unknown)}")
+        if not params:
+            self._chk(self.L.flx_reproject(self.h, None))
+            return
+        P = dict(REPROJECT_DEFAULTS, **params)
+        rp = ReprojectParams(float(P["max_history"]), float(P["plane_tolerance_px"]), float(P["normal_cos"]), float(P["min_weight"]))
+        self._chk(self.L.flx_reproject(self.h, C.byref(rp)))
+
+    def gbuffer_read(self, slot=0):
+        """test hook -> ((pixels, 8) float32: G0 = (P, hit index bits), G1 = (Ng, t); the slot's camera as a wire.CAMERA record)"""
+        from . import wire
+        out = np.zeros((self.local_pixels(), 8), np.float32)
+        cam = np.zeros(1, wire.CAMERA)
+        self._chk(self.L.flx_gbuffer_read(self.h, int(slot), _p(out), _p(cam)))
+        return out, cam.reshape(())
+
+    def gbuffer_write(self, slot, g, camera):
+        """test hook: (pixels, 8) float32 and a wire.CAMERA record into slot 0 (current) or 1 (previous)"""
+        from . import wire
+        g = np.ascontiguousarray(g, np.float32).reshape(-1, 8)
+        assert g.shape[0] == self.local_pixels(), (g.shape, self.local_pixels())
+        cam = np.frombuffer(np.asarray(camera).tobytes(), wire.CAMERA).copy()      # any 80-byte flx_camera record
+        assert cam.size == 1
+        self._chk(self.L.flx_gbuffer_write(self.h, int(slot), _p(g), _p(cam)))
+
+    def kernel_profile(self, kernel):
+        """(milliseconds, launches) of one FLX_K_* id accumulated while profiling (level 1) since the last profile_reset; after finish()"""
+        ms, n = C.c_double(), C.c_uint64()
+        self._chk(self.L.flx_profile_get(self.h, int(kernel), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def denoise_profile(self):
         """(milliseconds, launches) of flx_denoise accumulated while profiling (level 1) since the last profile_reset; after finish()"""

@@ -16,7 +16,7 @@ struct HipContext::Api {
     FN(flx_num_tasks) FN(flx_postprocess) FN(flx_read_pixels) FN(flx_set_partition) FN(flx_local_pixels)
     FN(flx_mk_reset) FN(flx_mk_raygen) FN(flx_mk_next_vertex) FN(flx_mk_sample_bsdf) FN(flx_mk_splat) FN(flx_mk_splat_preview)
     FN(flx_mk_stats_async) FN(flx_mk_stats_reset) FN(flx_set_option) FN(flx_get_option) FN(flx_group_init_local) FN(flx_gather_local)
-    FN(flx_denoise) FN(flx_denoise_variance_guided)
+    FN(flx_denoise) FN(flx_denoise_variance_guided) FN(flx_gbuffer) FN(flx_history_capture) FN(flx_reproject)
 #undef FN
 };
 
@@ -44,7 +44,7 @@ HipContext::HipContext(int device, uint32_t numTasks, const std::string &libPath
     BIND(flx_num_tasks) BIND(flx_postprocess) BIND(flx_read_pixels) BIND(flx_set_partition) BIND(flx_local_pixels)
     BIND(flx_mk_reset) BIND(flx_mk_raygen) BIND(flx_mk_next_vertex) BIND(flx_mk_sample_bsdf) BIND(flx_mk_splat) BIND(flx_mk_splat_preview)
     BIND(flx_mk_stats_async) BIND(flx_mk_stats_reset) BIND(flx_set_option) BIND(flx_get_option) BIND(flx_group_init_local) BIND(flx_gather_local)
-    BIND(flx_denoise) BIND(flx_denoise_variance_guided)
+    BIND(flx_denoise) BIND(flx_denoise_variance_guided) BIND(flx_gbuffer) BIND(flx_history_capture) BIND(flx_reproject)
 #undef BIND
     if (api->flx_create(device, numTasks, &ctx) != 0)
         throw std::runtime_error(std::string("HipContext: ") + api->flx_last_error(nullptr));
@@ -130,6 +130,13 @@ void HipContext::denoiseVarianceGuided(const DenoiseVgParams &p)
 {
     const flx_denoise_vg_params dp = {p.iterations, p.sigmaLuminance, p.sigmaNormal, p.sigmaAlbedo, p.blend};
     check(api->flx_denoise_variance_guided(ctx, &dp), "denoiseVarianceGuided");
+}
+void HipContext::gbuffer() { check(api->flx_gbuffer(ctx), "gbuffer"); }
+void HipContext::historyCapture() { check(api->flx_history_capture(ctx), "historyCapture"); }
+void HipContext::reproject(const ReprojectParams &p)
+{
+    const flx_reproject_params rp = {p.maxHistory, p.planeTolerancePx, p.normalCos, p.minWeight};
+    check(api->flx_reproject(ctx, &rp), "reproject");
 }
 void HipContext::finishQueue() { check(api->flx_finish(ctx), "finish"); foldMkStats(); }
 void HipContext::updatePixelIndex(uint32_t n, uint32_t nnew) { check(api->flx_pixel_index_update(ctx, n, nnew), "updatePixelIndex"); }

@@ -58,6 +58,13 @@ public:
     // the variance-guided filter (flx_denoise_variance_guided): needs the options "denoiser" and "moments"; otherwise as denoise()
     struct DenoiseVgParams { int iterations = 5; float sigmaLuminance = 4.0f, sigmaNormal = 0.3f, sigmaAlbedo = 0.1f, blend = 0.0f; };
     void denoiseVarianceGuided(const DenoiseVgParams &params);
+    // temporal reprojection (flx_gbuffer / flx_history_capture / flx_reproject): the primary-visibility G-buffer of the current
+    // camera; the snapshot of the accumulation (and moments) with that G-buffer as the previous one; the snapshot resampled into the current
+    // view over the freshly reset accumulation.  Single-GPU, asynchronous.
+    struct ReprojectParams { float maxHistory = 32.0f, planeTolerancePx = 2.0f, normalCos = 0.9f, minWeight = 0.01f; };
+    void gbuffer();
+    void historyCapture();
+    void reproject(const ReprojectParams &params);
     void finishQueue();
     void updatePixelIndex(uint32_t numPixels, uint32_t numNewPaths);
     void resetPixelIndex();

@@ -296,6 +296,9 @@ int fh_tracer_set_option(void *t, const char *name, int value) { FH_TRY ((Tracer
 int fh_tracer_set_denoiser(void *t, int on) { FH_TRY ((Tracer *)t)->setDenoiser(on != 0); FH_CATCH }
 int fh_tracer_set_denoiser_strength(void *t, float s) { FH_TRY ((Tracer *)t)->setDenoiserStrength(s); FH_CATCH }
 int fh_tracer_set_denoiser_mode(void *t, int mode) { FH_TRY ((Tracer *)t)->setDenoiserMode((Tracer::DenoiserMode)mode); FH_CATCH }
+int fh_tracer_set_temporal_reprojection(void *t, int on) { FH_TRY ((Tracer *)t)->setTemporalReprojection(on != 0); FH_CATCH }
+int fh_tracer_get_temporal_reprojection(void *t) { return ((Tracer *)t)->getTemporalReprojection() ? 1 : 0; }
+int fh_tracer_set_max_history(void *t, float n) { FH_TRY ((Tracer *)t)->setMaxHistory(n); FH_CATCH }
 int fh_tracer_toggle_renderer(void *t) { FH_TRY ((Tracer *)t)->toggleRenderer(); FH_CATCH }
 int fh_tracer_uses_wavefront(void *t) { return ((Tracer *)t)->usesWavefront() ? 1 : 0; }
 int fh_tracer_stats(void *t, uint64_t *out4)

@@ -4,6 +4,7 @@
 #include <sstream>
 #include <fstream>
 #include <cstring>
+#include <cstddef>
 #include <cmath>
 #include <algorithm>
 #include <stdexcept>
@@ -102,6 +103,7 @@ void Tracer::init(int width, int height, const std::string &sceneFile)
     delete bvh; bvh = nullptr;                               // :72-73 data lives on the GPU now
     paramsUpdatePending = true;
     iteration = 0;
+    haveGbuffer = false;                                     // a new scene: no history
 }
 
 void Tracer::setEnvMap(const std::string &hdrFile)
@@ -110,6 +112,7 @@ void Tracer::setEnvMap(const std::string &hdrFile)
     for (auto *c : ranks()) c->createEnvMap(envMap.get());
     params.useEnvMap = 1;
     paramsUpdatePending = true;
+    dropHistory();                                           // another light: the accumulated radiance is stale
 }
 
 // reference: src/tracer.cpp:625-684 (iterateStateItems): one item after the other in native byte order
@@ -155,6 +158,25 @@ void Tracer::setDenoiserStrength(float s)
     if (s > 0.0f && !peers.empty()) throw std::runtime_error("setDenoiserStrength: the denoiser is single-GPU (a pixel's neighbours are on other ranks)");
     denoiserStrength = s;
 }
+void Tracer::setTemporalReprojection(bool on)
+{
+    if (on && !peers.empty()) throw std::runtime_error("setTemporalReprojection: temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
+    temporalOn = on;
+    haveGbuffer = false; temporalFrames = 0;
+}
+// everything of RenderParams that shapes the radiance of a point, i.e. all but the camera (bytes 96..175) and the post-process (exposure,
+// tmOperator: 176..183), equals what the G-buffer's frames were rendered with
+bool Tracer::onlyCameraChanged() const
+{
+    const char *a = (const char *)&params, *b = (const char *)&gbParams;
+    return std::memcmp(a, b, offsetof(RenderParams, camera)) == 0 &&
+           std::memcmp(a + offsetof(RenderParams, width), b + offsetof(RenderParams, width), sizeof(RenderParams) - offsetof(RenderParams, width)) == 0;
+}
+void Tracer::setMaxHistory(float n)
+{
+    if (!(n >= 1.0f) || !std::isfinite(n)) throw std::runtime_error("setMaxHistory: must be finite and >= 1");
+    maxHistory = n;
+}
 // DenoiserOptix::setBlend(1 - strength) + denoise (src/tracer.cpp:310-328): behind the post-process, on the stream
 void Tracer::denoiseStep()
 {
@@ -195,6 +217,7 @@ void Tracer::renderSingle(int spp, bool denoise)
     params.useRoulette = 0;                                              // :104-108
     if (denoise) setDenoiser(true);                                      // :110-114
     clctx->updateParams(params); paramsUpdatePending = false;
+    dropHistory();                                                       // parameters reach the device without a G-buffer
     clctx->enqueueResetKernel(params);
     for (int sample = 0; sample < spp; sample++) {
         clctx->enqueueRayGenKernel(params);
@@ -240,7 +263,22 @@ void Tracer::updateMicrokernel()
 void Tracer::update()
 {
     auto R = ranks();
-    if (paramsUpdatePending) { for (auto *c : R) c->updateParams(params); paramsUpdatePending = false; iteration = 0; }
+    bool reprojectNow = false;
+    if (paramsUpdatePending) {
+        const bool temporal = temporalOn && useWavefront;
+        // a history exists: at least one frame rendered since the last G-buffer, at the same size (a resize frees the device's slots)
+        // and with nothing but the camera changed since (lights, bounces, sampling switches: the kept radiance would be stale)
+        const bool history = temporal && haveGbuffer && framesSinceGbuffer > 0 && gbWidth == params.width && gbHeight == params.height && onlyCameraChanged();
+        if (history) clctx->historyCapture();                            // under the old camera's slot
+        for (auto *c : R) c->updateParams(params);
+        paramsUpdatePending = false; iteration = 0;
+        if (temporal) {
+            clctx->gbuffer();
+            haveGbuffer = true; gbParams = params; gbWidth = params.width; gbHeight = params.height; framesSinceGbuffer = 0;
+            reprojectNow = history;
+        } else dropHistory();                                            // the update was consumed without a G-buffer: the slot is another camera's
+    }
+    if (iteration == 0 && !reprojectNow) temporalFrames = 0;             // the accumulation restarts from nothing
     if (!useWavefront) {
         if (!peers.empty()) throw std::runtime_error("update: the microkernel integrator is single-GPU");
         updateMicrokernel(); return;
@@ -256,6 +294,7 @@ void Tracer::update()
             c->updateParams(params);
             c->resetPixelIndex();
             c->enqueueWfResetKernel(params);
+            if (reprojectNow) { HipContext::ReprojectParams rp; rp.maxHistory = maxHistory; c->reproject(rp); }      // (single rank: setTemporalReprojection)
             c->enqueueWfRaygenKernel(params);
             c->enqueueWfExtRayKernel(params);
             c->enqueueClearWfQueues();
@@ -275,7 +314,8 @@ void Tracer::update()
     }
     if (iteration == 0) { params.maxBounces = maxBounces; for (auto *c : R) c->updateParams(params); }
     for (auto *c : R) c->enqueuePostprocessKernel(params);
-    if (useDenoiser && denoiserStrength > 0.0f && iteration >= 10 && iteration % 10 == 0) denoiseStep();   // :310-328 (single-GPU: setDenoiserStrength)
+    const uint32_t sched = temporalOn ? temporalFrames : iteration;      // temporal reprojection: frames since the last discarded history
+    if (useDenoiser && denoiserStrength > 0.0f && sched >= 10 && sched % 10 == 0) denoiseStep();   // :310-328 (single-GPU: setDenoiserStrength)
     for (auto *c : R) c->finishQueue();
     QueueCounters sum; std::memset(&sum, 0, sizeof(sum));
     for (size_t r = 0; r < R.size(); r++) {
@@ -289,7 +329,7 @@ void Tracer::update()
     clctx->statsAsync.primaryRays += sum.raygenQueue;
     clctx->statsAsync.samples += (iteration > 0) ? sum.raygenQueue : 0;
     lastCnt = sum;
-    iteration++;
+    iteration++; framesSinceGbuffer++; temporalFrames++;
 }
 
 // reference: src/tracer.cpp:362-528, wavefront body
@@ -304,6 +344,7 @@ std::string Tracer::runBenchmark(double seconds, int iterations)
     // resetRenderer (:372-382)
     iteration = 0;
     paramsUpdatePending = false;
+    dropHistory();
     for (auto *c : R) {
         c->updateParams(params);
         c->resetPixelIndex();

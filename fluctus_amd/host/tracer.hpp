@@ -46,7 +46,21 @@ public:
     enum DenoiserMode { Guided = 0, VarianceGuided = 1 };
     void setDenoiserMode(DenoiserMode m);
     DenoiserMode getDenoiserMode() const { return denoiserMode; }
-    void toggleRenderer() { useWavefront = !useWavefront; iteration = 0; }        // src/tracer.cpp:881-886
+    // Temporal reprojection, default off.  On: a parameter update (camera move) on the WAVEFRONT integrator no longer throws the
+    // accumulation away -- update() captures it with the old camera's G-buffer, traces the new camera's, runs today's reset sequence unchanged and
+    // reprojects the capture into the new view before the first logic pass.  Without a history (first frame, new scene, resize) only the
+    // G-buffer is traced.  The denoiser schedule then counts frames since the last DISCARDED history instead of since the last move, so the filter
+    // also runs on frames after a move.  The history is kept only when NOTHING BUT THE CAMERA changed since the G-buffer it belongs to was traced:
+    // an update that changes the lights, the environment map, the bounce count or the sampling switches, a frame on the other integrator,
+    // renderSingle and runBenchmark all discard it, and the next frame restarts as on the default path.  The frame after a move is still the
+    // 2-bounce preview (three passes), now added onto the kept image: under continuous motion the image drifts towards the 2-bounce estimate
+    // until the camera rests.  The interactive microkernel branch overwrites the pixel with its preview splat and keeps today's reset;
+    // renderSingle is unaffected.  Single-GPU: throws on a multi-rank Tracer.
+    void setTemporalReprojection(bool on);
+    bool getTemporalReprojection() const { return temporalOn; }
+    void setMaxHistory(float n);                                                  // flx_reproject's max_history (>= 1; default 32)
+    float getMaxHistory() const { return maxHistory; }
+    void toggleRenderer() { useWavefront = !useWavefront; iteration = 0; haveGbuffer = false; }   // src/tracer.cpp:881-886 (no history across integrators)
     void setOption(const std::string &name, int value) { for (auto *c : ranks()) c->setOption(name, value); }   // every rank (HipContext::setOption)
     bool usesWavefront() const { return useWavefront; }
     void saveImage(const std::string &filename) { clctx->saveImage(filename, params); }
@@ -90,6 +104,17 @@ private:
     bool momentsOn = false;                                                       // the ranks' option "moments" as applyMoments left it
     void applyMoments();                                                          // "moments" on iff the denoiser is on in VarianceGuided mode
     void denoiseStep();                                                           // the mode's filter with blend = 1 - strength (rank 0; single-GPU)
+    bool temporalOn = false;
+    float maxHistory = 32.0f;
+    // the context's current slot holds the G-buffer of the camera the accumulation is being rendered under, traced under gbParams; cleared
+    // wherever parameters reach the device without flx_gbuffer (dropHistory)
+    bool haveGbuffer = false;
+    RenderParams gbParams {};
+    void dropHistory() { haveGbuffer = false; }
+    bool onlyCameraChanged() const;                                               // params against gbParams, the camera and the post-process aside
+    uint32_t gbWidth = 0, gbHeight = 0;                                           // ... traced at this size
+    uint32_t framesSinceGbuffer = 0;                                              // > 0: there is an accumulation worth capturing
+    uint32_t temporalFrames = 0;                                                  // frames since the last discarded history (the denoiser schedule while temporalOn)
     bool useWavefront = true;                                                     // this library's default; the reference starts on MK (src/tracer.cpp:11)
     QueueCounters lastCnt {};
     std::string sceneName;

@@ -83,6 +83,19 @@ class Tracer:
             raise ValueError(f"set_denoiser_mode: mode must be one of {sorted(modes)}, not {mode!r}")
         host._chk(self.L.fh_tracer_set_denoiser_mode(self.h, modes[mode]))
 
+    def set_temporal_reprojection(self, on):
+        """Tracer::setTemporalReprojection (default off): a camera move on the wavefront integrator keeps the accumulated image by
+        reprojecting it into the new view instead of restarting from nothing.  Single-GPU."""
+        host._chk(self.L.fh_tracer_set_temporal_reprojection(self.h, int(bool(on))))
+
+    @property
+    def temporal_reprojection(self):
+        return bool(self.L.fh_tracer_get_temporal_reprojection(self.h))
+
+    def set_max_history(self, n):
+        """Tracer::setMaxHistory: the sample count a reprojected pixel may keep (flx_reproject's max_history, >= 1; default 32)"""
+        host._chk(self.L.fh_tracer_set_max_history(self.h, C.c_float(float(n))))
+
     def set_option(self, name, value):
         """HipContext::setOption -> flx_set_option (e.g. "extend_tree", 2 for the reference's bit-exact visit order)."""
         host._chk(self.L.fh_tracer_set_option(self.h, name.encode(), int(value)))

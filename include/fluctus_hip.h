@@ -125,6 +125,40 @@ int flx_denoise(flx_ctx *ctx, const flx_denoise_params *params);
 typedef struct { int iterations; float sigma_luminance, sigma_normal, sigma_albedo, blend; } flx_denoise_vg_params;
 int flx_denoise_variance_guided(flx_ctx *ctx, const flx_denoise_vg_params *params);
 
+/* ---- temporal reprojection (no counterpart in the reference, which restarts the accumulation at every camera change, src/tracer.cpp:189-207;
+ * csrc/flx_reproject.h): keep the accumulated image across a camera move of a static scene.  Opt-in; the sequence is
+ *     ... render under camera A ...   flx_gbuffer            (any time after flx_set_params(A))
+ *     flx_history_capture                                    (copies which = 0 / 7; the current G-buffer slot becomes the previous one)
+ *     flx_set_params(B); flx_gbuffer; flx_wf_reset or flx_mk_reset (unchanged: they zero the accumulation); flx_reproject; ... render on ...
+ * All five calls need an unpartitioned context and fail with a message otherwise; all flush deferred and fused launches first and touch no
+ * path state, queue or counter.  The slots and the history exist from the first call on and are freed with the framebuffers (a
+ * flx_set_params that changes width * height, flx_set_partition).
+ *
+ * flx_gbuffer: one un-jittered pinhole ray through the centre of every pixel of the current camera (no lens draws), closest hit with the
+ * traversal flx_wf_extend uses (honours "extend_tree"; with 2 the hit index and t equal flx_wf_extend's bit for bit for the same ray).  Per
+ * pixel G0 = (P.xyz, bits(hit index)), P as the logic pass computes it from a raw hit (the implicit area-light quad included), index -1 on a
+ * miss; G1 = (Ng.xyz, t), Ng the triangle's unit geometric normal facing the ray origin (the light's N on the quad); a miss is (0, 0, 0, -1).
+ * Asynchronous.
+ * flx_history_capture: on the stream, copies of the accumulation (which = 0) and, with option "moments" on, of the moments (which = 7); the
+ * current G-buffer slot with its camera becomes the previous slot (pointer swap) and the current slot is marked not traced.  Fails when the
+ * current slot was not traced or the image size differs from the slot's.
+ * flx_reproject: overwrites which = 0 for EVERY pixel -- and which = 7 when "moments" is on now and was on at the capture -- with the history
+ * resampled into the new view (four bilinear taps, each accepted by a plane-distance and a normal test against the current G-buffer; the
+ * weights renormalise; the count is capped at max_history, so a new sample weighs at least 1 / (max_history + 1) and view-dependent radiance
+ * recovers); a pixel without history is (0, 0, 0, 0).  Writes nothing else.  Needs a captured history and a traced current slot of the same
+ * size.  params NULL = the defaults {32, 2, 0.9, 0.01}; fails unless they are finite with max_history >= 1, plane_tolerance_px > 0,
+ * normal_cos in [-1, 1], min_weight in (0, 1].  Asynchronous.
+ * The sample count it leaves is FRACTIONAL, which is legal for every consumer of which = 0 / 7: flx_postprocess divides by it, flx_mk_splat and
+ * the wavefront splat add 1 to it, the denoisers only compare it with 0 and 2.
+ * flx_gbuffer_read / flx_gbuffer_write: test hooks in the spirit of flx_state_import -- slot 0 = current, 1 = previous; 8 floats per pixel
+ * (G0, G1) and the 80-byte camera of the slot; the write marks the slot traced at the current image size.  Blocking. */
+typedef struct { float max_history, plane_tolerance_px, normal_cos, min_weight; } flx_reproject_params;
+int flx_gbuffer(flx_ctx *ctx);
+int flx_history_capture(flx_ctx *ctx);
+int flx_reproject(flx_ctx *ctx, const flx_reproject_params *params);
+int flx_gbuffer_read(flx_ctx *ctx, int slot, float *out_8_floats_per_pixel, void *camera80);
+int flx_gbuffer_write(flx_ctx *ctx, int slot, const float *in_8_floats_per_pixel, const void *camera80);
+
 /* ---- microkernel integrator (the reference's second integrator).  One path per pixel (needs
  * num_tasks >= width*height to cover the image), `phase` state machine, exactly one sample per pixel per pass.
  * enqueueResetKernel / RayGenKernel / NextVertexKernel / BsdfSampleKernel / SplatKernel / SplatPreviewKernel
@@ -180,7 +214,9 @@ enum { FLX_K_RESET = 0, FLX_K_RAYGEN = 1, FLX_K_EXTEND = 2, FLX_K_SHADOW = 3, FL
        FLX_K_TRACE_SPAN = 7,   /* start of the extension kernel .. end of the (concurrent) shadow kernel */
        FLX_K_LOGIC_FUSED = 8,  /* logic + the inlined material step as one pass (option "fuse"); FLX_K_MATERIALS then covers the rest */
        FLX_K_DENOISE = 9,      /* the whole of one flx_denoise or flx_denoise_variance_guided */
-       FLX_K_COUNT = 10 };
+       FLX_K_GBUFFER = 10,     /* flx_gbuffer */
+       FLX_K_REPROJECT = 11,   /* flx_reproject */
+       FLX_K_COUNT = 12 };
 /* on: 0 off | 1 time every kernel | 2 time only the two trace kernels (+ their span), as the reference does | 3 only the
  * extension kernel | 4 the three kernels bench.py prices against a roof: extension, logic (the fused pass incl. its queue scan + scatter), shadow.
  * Each event pair costs a few microseconds of stream time, which shows at ~11 launches per 0.7 ms
