@@ -7,6 +7,7 @@
 #include "flx_denoise.h"
 #include "flx_denoise_vg.h"
 #include "flx_reproject.h"
+#include "flx_adaptive.h"
 #include "../../include/fluctus_hip.h"
 #include <string>
 #include <vector>
@@ -47,6 +48,12 @@ void launch_mk_raygen(hipStream_t, const State &, const flx_render_params &);
 void launch_mk_next_vertex(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *);
 void launch_mk_sample_bsdf(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *);
 void launch_mk_splat(hipStream_t, const State &, const Frame &, const flx_render_params &, uint32_t *, int);
+void launch_mk_raygen_list(hipStream_t, const State &, const flx_render_params &, const uint32_t *, uint32_t);
+void launch_mk_next_vertex_list(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const uint32_t *, uint32_t);
+void launch_mk_sample_bsdf_list(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const uint32_t *, uint32_t);
+void launch_mk_splat_list(hipStream_t, const State &, const Frame &, const flx_render_params &, uint32_t *, const uint32_t *, uint32_t);
+uint32_t adaptive_blocks(uint32_t);
+void launch_adaptive_update(hipStream_t, const float4 *, int, int, const ad_params &, uint8_t *, uint32_t *, uint32_t *, uint32_t *);
 void launch_end_iteration(hipStream_t, uint32_t *, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t *);
 void launch_bump_extension(hipStream_t, uint32_t *, uint32_t);
 void launch_deinterleave(hipStream_t, const float *, float *, uint32_t, uint32_t, uint32_t);
@@ -155,6 +162,11 @@ struct flx_ctx {
     std::vector<void *> gbAllocs;
     float4 *gb[2] = {nullptr, nullptr}; flx_camera gbCam[2] = {}; uint32_t gbW[2] = {0, 0}, gbH[2] = {0, 0}; bool gbTraced[2] = {false, false};
     float4 *hist = nullptr, *histMomBuf = nullptr; bool histHave = false, histHasMom = false;
+    // the adaptive microkernel render (adaptive.hip): the list of active pixels the sample pass's four kernels run over while
+    // adHave (adCount entries, ascending; 0 = the calls are no-ops); flag bytes, block counts and the list are allocated by the first
+    // flx_mk_adaptive_update / flx_mk_active_write for adPix pixels and freed with the framebuffers.  adHave false = every pixel.
+    std::vector<void *> adAllocs;
+    uint8_t *adFlags = nullptr; uint32_t *adScratch = nullptr, *adList = nullptr, *adCountDev = nullptr; uint32_t adPix = 0, adCount = 0; bool adHave = false;
     int nodeLayout = 1;         // 1 = sibling-pair record numbering (see flx_upload_scene), 0 = DFS
     int numCUs = 256;
     // multi-GPU group (flx_group_*): RCCL communicator of this rank, root-side staging
@@ -256,6 +268,13 @@ static void freeTemporal(flx_ctx *c)
     c->gbTraced[0] = c->gbTraced[1] = false; c->histHave = c->histHasMom = false;
 }
 
+// the list of active pixels and its working buffers go with the framebuffers
+static void freeAdaptive(flx_ctx *c)
+{
+    freeAll(c->adAllocs);
+    c->adFlags = nullptr; c->adScratch = c->adList = c->adCountDev = nullptr; c->adPix = c->adCount = 0; c->adHave = false;
+}
+
 static int allocFrame(flx_ctx *c)
 {
     uint32_t lp = localPixels(c);
@@ -263,6 +282,7 @@ static int allocFrame(flx_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     freeDenoise(c);
     freeTemporal(c);
+    freeAdaptive(c);
     freeAll(c->frameAllocs);
     HIPCHK(c, dalloc(c, c->frameAllocs, &c->fr.pixels, (size_t)lp * 4) ? hipErrorOutOfMemory : hipSuccess);
     HIPCHK(c, dalloc(c, c->frameAllocs, &c->fr.preview, (size_t)lp * 4) ? hipErrorOutOfMemory : hipSuccess);
@@ -430,7 +450,7 @@ int flx_destroy(flx_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) { flx_group_destroy(c); }
     freeAll(c->gatherAllocs);
-    freeAll(c->sceneAllocs); freeAll(c->spillAllocs); freeAll(c->envAllocs); freeAll(c->frameAllocs); freeAll(c->aovAllocs); freeAll(c->dnAllocs); freeAll(c->momAllocs); freeAll(c->gbAllocs); freeAll(c->fixedAllocs);
+    freeAll(c->sceneAllocs); freeAll(c->spillAllocs); freeAll(c->envAllocs); freeAll(c->frameAllocs); freeAll(c->aovAllocs); freeAll(c->dnAllocs); freeAll(c->momAllocs); freeAll(c->gbAllocs); freeAll(c->adAllocs); freeAll(c->fixedAllocs);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pinnedIdx) (void)hipHostFree(c->pinnedIdx);
     if (c->pinnedMk) (void)hipHostFree(c->pinnedMk);
@@ -489,6 +509,7 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
                      const void *texdesc, size_t ntex, const uint8_t *texdata, size_t texbytes)
 {
     ENTER(c, CALL_OBSERVE);
+    c->adHave = false;                                   // a list of active pixels belongs to the render of one scene (flx_mk_adaptive_clear)
     NEED(c, trisv && ntris && indices && nidx && nodesv && nnodes, "flx_upload_scene: empty scene");
     NEED(c, materials && nmat, "flx_upload_scene: at least the default material is required");
     HIPCHK(c, hipSetDevice(c->device));
@@ -738,8 +759,10 @@ int flx_set_params(flx_ctx *c, const void *p240)
     ENTER(c, CALL_OBSERVE);
     NEED(c, p240, "flx_set_params: null");
     HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t oldW = c->params.width, oldH = c->params.height;
     memcpy(&c->params, p240, sizeof(flx_render_params));   // kernels receive the struct by value at launch = in-order semantics
     NEED(c, c->params.width > 0 && c->params.height > 0, "flx_set_params: zero-sized framebuffer");
+    if (c->params.width != oldW || c->params.height != oldH) c->adHave = false;      // the list of active pixels indexes the old image
     c->haveParams = true;
     return allocFrame(c);
 }
@@ -749,6 +772,7 @@ int flx_set_partition(flx_ctx *c, uint32_t rank, uint32_t nranks)
     ENTER(c, CALL_OBSERVE);
     NEED(c, nranks >= 1 && rank < nranks, "flx_set_partition: bad rank");
     c->fr.rank = rank; c->fr.nranks = nranks;
+    c->adHave = false;
     return c->haveParams ? allocFrame(c) : 0;
 }
 uint32_t flx_local_pixels(flx_ctx *c) { return c->fr.localPixels; }
@@ -1129,12 +1153,106 @@ int flx_gbuffer_write(flx_ctx *c, int slot, const float *in8, const void *camera
 // ---- microkernel integrator.  One path per pixel, framebuffers indexed by the path id: single-GPU only, the pixel
 // partition belongs to the wavefront path (allocFrame sizes the buffers for the rank's LOCAL pixels).
 #define MK_READY(c) do { READY(c, CALL_OBSERVE); NEED(c, (c)->fr.nranks == 1, "the microkernel integrator is single-GPU: flx_set_partition(ctx, 0, 1) first"); } while (0)
-int flx_mk_reset(flx_ctx *c) { MK_READY(c); launch_mk_reset(c->stream, c->st, c->fr, c->params); LAUNCHED(c); return 0; }
-int flx_mk_raygen(flx_ctx *c) { MK_READY(c); launch_mk_raygen(c->stream, c->st, c->params); LAUNCHED(c); return 0; }
-int flx_mk_next_vertex(flx_ctx *c) { MK_READY(c); launch_mk_next_vertex(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats); LAUNCHED(c); return 0; }
-int flx_mk_sample_bsdf(flx_ctx *c) { MK_READY(c); launch_mk_sample_bsdf(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats); LAUNCHED(c); return 0; }
-int flx_mk_splat(flx_ctx *c) { MK_READY(c); launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 0); LAUNCHED(c); return 0; }
+int flx_mk_reset(flx_ctx *c) { MK_READY(c); c->adHave = false; launch_mk_reset(c->stream, c->st, c->fr, c->params); LAUNCHED(c); return 0; }
+// with a list of active pixels installed (flx_mk_adaptive_update / flx_mk_active_write) the four kernels of a sample pass run their list-driven
+// instances over it; an empty list makes them no-ops
+int flx_mk_raygen(flx_ctx *c)
+{
+    MK_READY(c);
+    if (!c->adHave) launch_mk_raygen(c->stream, c->st, c->params);
+    else if (c->adCount) launch_mk_raygen_list(c->stream, c->st, c->params, c->adList, c->adCount);
+    LAUNCHED(c); return 0;
+}
+int flx_mk_next_vertex(flx_ctx *c)
+{
+    MK_READY(c);
+    if (!c->adHave) launch_mk_next_vertex(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
+    else if (c->adCount) launch_mk_next_vertex_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->adList, c->adCount);
+    LAUNCHED(c); return 0;
+}
+int flx_mk_sample_bsdf(flx_ctx *c)
+{
+    MK_READY(c);
+    if (!c->adHave) launch_mk_sample_bsdf(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
+    else if (c->adCount) launch_mk_sample_bsdf_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->adList, c->adCount);
+    LAUNCHED(c); return 0;
+}
+int flx_mk_splat(flx_ctx *c)
+{
+    MK_READY(c);
+    if (!c->adHave) launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 0);
+    else if (c->adCount) launch_mk_splat_list(c->stream, c->st, c->fr, c->params, c->mkStats, c->adList, c->adCount);
+    LAUNCHED(c); return 0;
+}
 int flx_mk_splat_preview(flx_ctx *c) { MK_READY(c); launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 1); LAUNCHED(c); return 0; }
+
+// ---- adaptive sampling (adaptive.hip, csrc/flx_adaptive.h)
+static int adaptiveReady(flx_ctx *c, const char *fn)
+{
+    NEED(c, c->fr.nranks == 1, std::string(fn) + ": the microkernel integrator is single-GPU: flx_set_partition(ctx, 0, 1) first");
+    const uint64_t npix = (uint64_t)c->params.width * c->params.height;
+    NEED(c, npix <= c->numTasks, std::string(fn) + ": needs one path per pixel: width * height <= num_tasks");
+    if (c->adPix != (uint32_t)npix || !c->adList) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        freeAdaptive(c);
+        if (dalloc(c, c->adAllocs, &c->adFlags, (size_t)npix) || dalloc(c, c->adAllocs, &c->adScratch, (size_t)adaptive_blocks((uint32_t)npix)) ||
+            dalloc(c, c->adAllocs, &c->adList, (size_t)npix) || dalloc(c, c->adAllocs, &c->adCountDev, 1)) { freeAdaptive(c); return 1; }
+        c->adPix = (uint32_t)npix;
+    }
+    return 0;
+}
+int flx_mk_adaptive_update(flx_ctx *c, const flx_adaptive_params *pp, uint32_t *out_active)
+{
+    READY(c, CALL_OBSERVE);
+    NEED(c, c->moments && c->fr.moments, "flx_mk_adaptive_update: needs the luminance moments: flx_set_option(ctx, \"moments\", 1)");
+    NEED(c, out_active, "flx_mk_adaptive_update: null output");
+    ad_params ap = {FLX_AD_DEFAULT_THRESHOLD, FLX_AD_DEFAULT_MIN_SAMPLES, FLX_AD_DEFAULT_MAX_SAMPLES, FLX_AD_DEFAULT_LUM_FLOOR, FLX_AD_DEFAULT_DILATE};
+    if (pp) { ap.threshold = pp->threshold; ap.min_samples = pp->min_samples; ap.max_samples = pp->max_samples; ap.lum_floor = pp->lum_floor; ap.dilate = pp->dilate; }
+    NEED(c, ad_params_ok(ap), "flx_mk_adaptive_update: threshold and lum_floor must be finite and >= 0, 1 <= max_samples <= 2^24, min_samples <= max_samples, dilate 0 or 1");
+    if (adaptiveReady(c, "flx_mk_adaptive_update")) return 1;
+    launch_adaptive_update(c->stream, reinterpret_cast<const float4 *>(c->fr.moments), (int)c->params.width, (int)c->params.height, ap, c->adFlags, c->adScratch,
+                           c->adList, c->adCountDev);
+    LAUNCHED(c);
+    uint32_t n = 0;
+    HIPCHK(c, hipMemcpyAsync(&n, c->adCountDev, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    NEED(c, n <= c->adPix, "flx_mk_adaptive_update: the device returned an impossible count");
+    c->adCount = n; c->adHave = true;
+    *out_active = n;
+    return 0;
+}
+int flx_mk_adaptive_clear(flx_ctx *c) { ENTER(c, CALL_OBSERVE); c->adHave = false; return 0; }
+// test hooks in the spirit of flx_gbuffer_read / flx_gbuffer_write.  Blocking.
+int flx_mk_active_read(flx_ctx *c, uint32_t *out_list, uint32_t *out_count, uint8_t *out_flags)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, out_count, "flx_mk_active_read: null count");
+    NEED(c, c->adHave, "flx_mk_active_read: no list of active pixels is installed");
+    *out_count = c->adCount;
+    if (out_list && c->adCount) HIPCHK(c, hipMemcpyAsync(out_list, c->adList, (size_t)c->adCount * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_flags) HIPCHK(c, hipMemcpyAsync(out_flags, c->adFlags, (size_t)c->adPix, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+int flx_mk_active_write(flx_ctx *c, const uint32_t *in_list, uint32_t n)
+{
+    READY(c, CALL_OBSERVE);
+    NEED(c, in_list || !n, "flx_mk_active_write: null list");
+    const uint64_t npix = (uint64_t)c->params.width * c->params.height;
+    NEED(c, n <= npix, "flx_mk_active_write: more entries than pixels");
+    for (uint32_t i = 0; i < n; i++) {
+        NEED(c, in_list[i] < npix, "flx_mk_active_write: pixel index out of range");
+        NEED(c, i == 0 || in_list[i] > in_list[i - 1], "flx_mk_active_write: the list must be strictly ascending");
+    }
+    if (adaptiveReady(c, "flx_mk_active_write")) return 1;
+    HIPCHK(c, hipMemsetAsync(c->adFlags, 0, c->adPix, c->stream));       // (the flags describe a classification; a written list has none)
+    if (n) HIPCHK(c, hipMemcpyAsync(c->adList, in_list, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->adCount = n; c->adHave = true;
+    return 0;
+}
+
 int flx_mk_stats_async(flx_ctx *c, void *out16)
 {
     ENTER(c, CALL_OBSERVE);
@@ -1658,6 +1776,7 @@ int flx_set_option(flx_ctx *c, const char *name, int value)
     }
     if (name && strcmp(name, "moments") == 0 && (value == 0 || value == 1)) {
         ENTER(c, CALL_OBSERVE);
+        if (!value) c->adHave = false;                    // the list of active pixels is derived from the moments
         if (c->moments != value) { c->moments = value; HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipStreamSynchronize(c->stream)); return allocMoments(c); }
         return 0;
     }

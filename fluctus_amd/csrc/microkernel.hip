@@ -47,10 +47,23 @@ __global__ __launch_bounds__(256) void k_mk_reset(State st, Frame fr, flx_render
     st.firstDiffuse[gid] = 0u;
 }
 
-__global__ __launch_bounds__(256) void k_mk_raygen(State st, flx_render_params p)
+// The four kernels of a sample pass exist twice: over every pixel (LIST false: thread = pixel, the instances under the
+// reference's names) and over a compacted ascending list of ACTIVE pixels (LIST true, k_mk_*_list: thread tid < count serves pixel
+// list[tid]; flx_mk_adaptive_update, adaptive.hip).  `gid` below is the pixel = the state slot either way; only the traversal stack's LDS
+// column and spill column belong to the THREAD (tid).  One body per kernel, so the two cannot drift apart.
+template <bool LIST>
+__device__ __forceinline__ bool mk_map(const State &st, const flx_render_params &p, uint32_t tid, const uint32_t *list, uint32_t count, uint32_t *gid)
 {
-    const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
-    if (gid >= mk_limit(st, p) || st.phase[gid] != MK_GENERATE_CAMERA_RAY) return;
+    if (LIST) { const bool in = tid < count; *gid = in ? list[tid] : 0u; return in; }
+    *gid = tid;
+    return tid < mk_limit(st, p);
+}
+
+template <bool LIST>
+__device__ __forceinline__ void mk_raygen(State st, flx_render_params p, const uint32_t *list, uint32_t count)
+{
+    uint32_t gid;
+    if (!mk_map<LIST>(st, p, blockIdx.x * 256 + threadIdx.x, list, count, &gid) || st.phase[gid] != MK_GENERATE_CAMERA_RAY) return;
     const float4 thr = rd4(st.at(S_THR, gid));
     uint32_t seed = __float_as_uint(thr.w);
     float x = (float)(gid % p.width), y = (float)(gid / p.width);
@@ -77,17 +90,21 @@ __global__ __launch_bounds__(256) void k_mk_raygen(State st, flx_render_params p
     wr4(st.at(S_THR, gid), mk4u(ld3(thr), seed));
     st.phase[gid] = MK_RT_NEXT_VERTEX;
 }
+__global__ __launch_bounds__(256) void k_mk_raygen(State st, flx_render_params p) { mk_raygen<false>(st, p, nullptr, 0u); }
+__global__ __launch_bounds__(256) void k_mk_raygen_list(State st, flx_render_params p, const uint32_t *list, uint32_t count) { mk_raygen<true>(st, p, list, count); }
 
-__global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats)
+template <bool LIST>
+__device__ __forceinline__ void mk_next_vertex(uint32_t *s_stack, State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill,
+                                               uint32_t totalThreads, uint32_t *stats, const uint32_t *list, uint32_t count)
 {
-    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    const uint32_t gid = blockIdx.x * MK_BLOCK + threadIdx.x;
-    const bool active = gid < mk_limit(st, p) && st.phase[gid] == MK_RT_NEXT_VERTEX;
+    const uint32_t tid = blockIdx.x * MK_BLOCK + threadIdx.x;
+    uint32_t gid;
+    const bool active = mk_map<LIST>(st, p, tid, list, count, &gid) && st.phase[gid] == MK_RT_NEXT_VERTEX;
     bool primary = false;
     if (active) {
         const float4 o4 = rd4(st.at(S_ORIG, gid)), d4 = rd4(st.at(S_DIR, gid));
         const f3 orig = ld3(o4), dir = ld3(d4);
-        Stack stk; stk.lds = s_stack + threadIdx.x; stk.stride = totalThreads; stk.spill = spill + gid;
+        Stack stk; stk.lds = s_stack + threadIdx.x; stk.stride = totalThreads; stk.spill = spill + tid;
         float t = FLX_FLT_MAX, u = 0.0f, v = 0.0f; int tri = -1; uint32_t a = 0, b = 0;
         traverse<false, false>(sc, stk, orig, dir, t, u, v, tri, a, b);
         f3 P = mk3(0.0f), N = mk3(0.0f); float tu = 0.0f, tv = 0.0f; int matId = -1; uint32_t flags = 0;
@@ -149,12 +166,25 @@ __global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex(State st, Scene sc,
     wave_count(&stats[0], active && primary);
     wave_count(&stats[1], active && !primary);
 }
-
-__global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats)
+__global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats)
 {
     __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    const uint32_t gid = blockIdx.x * MK_BLOCK + threadIdx.x;
-    const bool active = gid < mk_limit(st, p) && st.phase[gid] == MK_SAMPLE_BSDF;
+    mk_next_vertex<false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, nullptr, 0u);
+}
+__global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex_list(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
+                                                                  const uint32_t *list, uint32_t count)
+{
+    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
+    mk_next_vertex<true>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count);
+}
+
+template <bool LIST>
+__device__ __forceinline__ void mk_sample_bsdf(uint32_t *s_stack, State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill,
+                                               uint32_t totalThreads, uint32_t *stats, const uint32_t *list, uint32_t count)
+{
+    const uint32_t tid = blockIdx.x * MK_BLOCK + threadIdx.x;
+    uint32_t gid;
+    const bool active = mk_map<LIST>(st, p, tid, list, count, &gid) && st.phase[gid] == MK_SAMPLE_BSDF;
     uint32_t nShadow = 0;
     if (active) {
         const float4 thr = rd4(st.at(S_THR, gid));
@@ -178,7 +208,7 @@ __global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf(State st, Scene sc,
         f3 Ei = ld3(rd4(st.at(S_EI, gid)));
         const float eiw = rd4(st.at(S_EI, gid)).w;
         const f3 T = ld3(thr);
-        Stack stk; stk.lds = s_stack + threadIdx.x; stk.stride = totalThreads; stk.spill = spill + gid;
+        Stack stk; stk.lds = s_stack + threadIdx.x; stk.stride = totalThreads; stk.spill = spill + tid;
         if (p.sampleExpl && !FLX_BXDF_IS_SINGULAR(m.type)) {         // next event estimation, both lights (src/mk_sample_bsdf.cl:62-141)
             const float lightPickProb = 1.0f;
             if (p.useEnvMap) {
@@ -249,11 +279,24 @@ __global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf(State st, Scene sc,
     for (int o = 32; o > 0; o >>= 1) nShadow += __shfl_xor(nShadow, o, 64);
     if (lane_id() == 0u && nShadow) atomicAdd(&stats[2], nShadow);
 }
-
-__global__ __launch_bounds__(256) void k_mk_splat(State st, Frame fr, flx_render_params p, uint32_t *stats, int preview)
+__global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats)
 {
-    const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
-    const bool inRange = gid < mk_limit(st, p);
+    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
+    mk_sample_bsdf<false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, nullptr, 0u);
+}
+__global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf_list(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
+                                                                  const uint32_t *list, uint32_t count)
+{
+    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
+    mk_sample_bsdf<true>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count);
+}
+
+// (the list-driven instance is never a preview: flx_mk_splat_preview covers every pixel)
+template <bool LIST>
+__device__ __forceinline__ void mk_splat(State st, Frame fr, flx_render_params p, uint32_t *stats, int preview, const uint32_t *list, uint32_t count)
+{
+    uint32_t gid;
+    const bool inRange = mk_map<LIST>(st, p, blockIdx.x * 256 + threadIdx.x, list, count, &gid);
     const bool active = inRange && (preview || st.phase[gid] == MK_SPLAT_SAMPLE);
     if (active) {
         const float4 ei = rd4(st.at(S_EI, gid));
@@ -280,6 +323,8 @@ __global__ __launch_bounds__(256) void k_mk_splat(State st, Frame fr, flx_render
     }
     if (!preview) wave_count(&stats[3], active);
 }
+__global__ __launch_bounds__(256) void k_mk_splat(State st, Frame fr, flx_render_params p, uint32_t *stats, int preview) { mk_splat<false>(st, fr, p, stats, preview, nullptr, 0u); }
+__global__ __launch_bounds__(256) void k_mk_splat_list(State st, Frame fr, flx_render_params p, uint32_t *stats, const uint32_t *list, uint32_t count) { mk_splat<true>(st, fr, p, stats, 0, list, count); }
 
 static uint32_t mkThreads(const State &st, const flx_render_params &p) { uint32_t n = p.width * p.height; return n < st.numTasks ? n : st.numTasks; }
 
@@ -299,5 +344,22 @@ void launch_mk_sample_bsdf(hipStream_t s, const State &st, const Scene &sc, cons
 }
 void launch_mk_splat(hipStream_t s, const State &st, const Frame &fr, const flx_render_params &p, uint32_t *stats, int preview)
 { hipLaunchKernelGGL(k_mk_splat, dim3((mkThreads(st, p) + 255) / 256), dim3(256), 0, s, st, fr, p, stats, preview); }
+
+// the list-driven pass: count > 0 threads, pixel list[tid]; the caller guarantees ascending entries < min(width * height, numTasks) and count <= that bound,
+// so the spill columns (one per thread) stay inside the allocation the unlisted launches use
+void launch_mk_raygen_list(hipStream_t s, const State &st, const flx_render_params &p, const uint32_t *list, uint32_t count)
+{ hipLaunchKernelGGL(k_mk_raygen_list, dim3((count + 255) / 256), dim3(256), 0, s, st, p, list, count); }
+void launch_mk_next_vertex_list(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats, const uint32_t *list, uint32_t count)
+{
+    uint32_t blocks = (count + MK_BLOCK - 1) / MK_BLOCK;
+    hipLaunchKernelGGL(k_mk_next_vertex_list, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, count);
+}
+void launch_mk_sample_bsdf_list(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats, const uint32_t *list, uint32_t count)
+{
+    uint32_t blocks = (count + MK_BLOCK - 1) / MK_BLOCK;
+    hipLaunchKernelGGL(k_mk_sample_bsdf_list, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, count);
+}
+void launch_mk_splat_list(hipStream_t s, const State &st, const Frame &fr, const flx_render_params &p, uint32_t *stats, const uint32_t *list, uint32_t count)
+{ hipLaunchKernelGGL(k_mk_splat_list, dim3((count + 255) / 256), dim3(256), 0, s, st, fr, p, stats, list, count); }
 
 } // namespace flxd

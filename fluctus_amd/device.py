@@ -22,7 +22,8 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_trace_stats_enable", "flx_trace_stats_get", "flx_trace_stats_get_ex", "flx_trace_stats_get_all", "flx_scene_info", "flx_trace_stats_reset", "flx_state_export", "flx_state_import", "flx_math_probe", "flx_env_sample_table",
            "flx_queue_read", "flx_queue_write", "flx_set_counters", "flx_set_option", "flx_get_option", "flx_mk_reset", "flx_mk_raygen", "flx_mk_next_vertex",
            "flx_mk_sample_bsdf", "flx_mk_splat", "flx_mk_splat_preview", "flx_mk_stats_async", "flx_mk_stats_reset", "flx_write_pixels", "flx_denoise",
-           "flx_denoise_variance_guided", "flx_gbuffer", "flx_history_capture", "flx_reproject", "flx_gbuffer_read", "flx_gbuffer_write"]
+           "flx_denoise_variance_guided", "flx_gbuffer", "flx_history_capture", "flx_reproject", "flx_gbuffer_read", "flx_gbuffer_write",
+           "flx_mk_adaptive_update", "flx_mk_adaptive_clear", "flx_mk_active_read", "flx_mk_active_write"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
 K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with HipContext.denoise_profile (not part of profile_get)
@@ -54,6 +55,15 @@ class ReprojectParams(C.Structure):
 
 # the library's defaults (FLX_RP_DEFAULT_*, csrc/flx_reproject.h)
 REPROJECT_DEFAULTS = dict(max_history=32.0, plane_tolerance_px=2.0, normal_cos=0.9, min_weight=0.01)
+
+
+class AdaptiveParams(C.Structure):
+    """flx_adaptive_params (include/fluctus_hip.h)"""
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("lum_floor", C.c_float), ("dilate", C.c_uint32)]
+
+
+# the library's defaults (FLX_AD_DEFAULT_*, csrc/flx_adaptive.h; DESIGN.md 4.2.1)
+ADAPTIVE_DEFAULTS = dict(threshold=0.05, min_samples=4, max_samples=32, lum_floor=0.01, dilate=1)
 
 
 def _preload_torch_runtime():
@@ -155,6 +165,34 @@ class HipContext:
     def mk_sample_bsdf(self): self._chk(self.L.flx_mk_sample_bsdf(self.h))
     def mk_splat(self): self._chk(self.L.flx_mk_splat(self.h))
     def mk_splat_preview(self): self._chk(self.L.flx_mk_splat_preview(self.h))
+
+    def mk_adaptive_update(self, **params):
+        """flx_mk_adaptive_update (blocking; option "moments"): threshold, min_samples, max_samples, lum_floor, dilate -- any left out takes its
+        default (ADAPTIVE_DEFAULTS).  Classifies the pixels, installs the ascending list of active ones for the following mk_raygen ... mk_splat
+        and returns its length."""
+        unknown = set(params) - set(ADAPTIVE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"mk_adaptive_update: unknown parameters {sorted(unknown)}")
+        v = dict(ADAPTIVE_DEFAULTS, **params)
+        ap = AdaptiveParams(float(v["threshold"]), int(v["min_samples"]), int(v["max_samples"]), float(v["lum_floor"]), int(v["dilate"]))
+        n = C.c_uint32()
+        self._chk(self.L.flx_mk_adaptive_update(self.h, C.byref(ap) if params else None, C.byref(n)))
+        return int(n.value)
+
+    def mk_adaptive_clear(self): self._chk(self.L.flx_mk_adaptive_clear(self.h))
+
+    def mk_active_read(self):
+        """test hook: (list, flags) -- the installed ascending list of active pixels (uint32) and the flag byte of every pixel as the last update
+        left it (bit 0 own, 1 active, 2 done, 3 converged)"""
+        npix = int(self.params["width"]) * int(self.params["height"])
+        lst, flags, n = np.zeros(npix, np.uint32), np.zeros(npix, np.uint8), C.c_uint32()
+        self._chk(self.L.flx_mk_active_read(self.h, _p(lst), C.byref(n), _p(flags)))
+        return lst[:n.value].copy(), flags
+
+    def mk_active_write(self, lst):
+        """test hook: install an arbitrary list of active pixels (strictly ascending, every entry < width * height)"""
+        lst = np.ascontiguousarray(lst, np.uint32).reshape(-1)
+        self._chk(self.L.flx_mk_active_write(self.h, _p(lst), C.c_uint32(lst.size)))
 
     def mk_stats(self, reset=False):
         out = np.zeros(4, np.uint32)

@@ -63,6 +63,31 @@ def render_single_pass(ctx, max_bounces):
     ctx.mk_splat()
 
 
+def render_adaptive(ctx, params, min_spp, max_spp, on_pass=None, **adaptive):
+    """Tracer::renderAdaptive as the C-ABI sequence (DESIGN.md 4.2.1; the context's option "moments" must be on): roulette off, reset, min_spp
+    uniform passes, then update -> pass over the listed pixels -> update ... until no pixel is listed or max_spp passes ran; the list is cleared
+    at the end.  on_pass(sample index, active count) is called before every pass.  Returns (params used, samples taken)."""
+    p = params.copy()
+    p["useRoulette"] = 0
+    ctx.set_params(p)
+    ctx.mk_reset()
+    npix = int(p["width"]) * int(p["height"])
+    total, active = 0, npix
+    for s in range(max_spp):
+        if s >= min_spp:
+            active = ctx.mk_adaptive_update(min_samples=min_spp, max_samples=max_spp, **adaptive)
+            if active == 0:
+                break
+        if on_pass is not None:
+            on_pass(s, active)
+        render_single_pass(ctx, p["maxBounces"])
+        total += active
+    ctx.mk_adaptive_clear()
+    ctx.postprocess()
+    ctx.finish()
+    return p, total
+
+
 def render_single(ctx, params, spp):
     """Tracer::renderSingle (src/tracer.cpp:95-169): roulette off, reset, spp passes, post-process."""
     p = params.copy()

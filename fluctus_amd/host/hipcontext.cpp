@@ -17,6 +17,7 @@ struct HipContext::Api {
     FN(flx_mk_reset) FN(flx_mk_raygen) FN(flx_mk_next_vertex) FN(flx_mk_sample_bsdf) FN(flx_mk_splat) FN(flx_mk_splat_preview)
     FN(flx_mk_stats_async) FN(flx_mk_stats_reset) FN(flx_set_option) FN(flx_get_option) FN(flx_group_init_local) FN(flx_gather_local)
     FN(flx_denoise) FN(flx_denoise_variance_guided) FN(flx_gbuffer) FN(flx_history_capture) FN(flx_reproject)
+    FN(flx_mk_adaptive_update) FN(flx_mk_adaptive_clear)
 #undef FN
 };
 
@@ -45,6 +46,7 @@ HipContext::HipContext(int device, uint32_t numTasks, const std::string &libPath
     BIND(flx_mk_reset) BIND(flx_mk_raygen) BIND(flx_mk_next_vertex) BIND(flx_mk_sample_bsdf) BIND(flx_mk_splat) BIND(flx_mk_splat_preview)
     BIND(flx_mk_stats_async) BIND(flx_mk_stats_reset) BIND(flx_set_option) BIND(flx_get_option) BIND(flx_group_init_local) BIND(flx_gather_local)
     BIND(flx_denoise) BIND(flx_denoise_variance_guided) BIND(flx_gbuffer) BIND(flx_history_capture) BIND(flx_reproject)
+    BIND(flx_mk_adaptive_update) BIND(flx_mk_adaptive_clear)
 #undef BIND
     if (api->flx_create(device, numTasks, &ctx) != 0)
         throw std::runtime_error(std::string("HipContext: ") + api->flx_last_error(nullptr));
@@ -133,6 +135,14 @@ void HipContext::denoiseVarianceGuided(const DenoiseVgParams &p)
 }
 void HipContext::gbuffer() { check(api->flx_gbuffer(ctx), "gbuffer"); }
 void HipContext::historyCapture() { check(api->flx_history_capture(ctx), "historyCapture"); }
+uint32_t HipContext::adaptiveUpdate(const AdaptiveParams &p)
+{
+    const flx_adaptive_params ap = {p.threshold, p.minSamples, p.maxSamples, p.lumFloor, p.dilate ? 1u : 0u};
+    uint32_t n = 0;
+    check(api->flx_mk_adaptive_update(ctx, &ap, &n), "adaptiveUpdate");
+    return n;
+}
+void HipContext::adaptiveClear() { check(api->flx_mk_adaptive_clear(ctx), "adaptiveClear"); }
 void HipContext::reproject(const ReprojectParams &p)
 {
     const flx_reproject_params rp = {p.maxHistory, p.planeTolerancePx, p.normalCos, p.minWeight};

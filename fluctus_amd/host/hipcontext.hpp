@@ -9,6 +9,7 @@
 #include <vector>
 #include <cstdint>
 #include "../../include/fluctus_hip.h"
+#include "../csrc/flx_adaptive.h"       // FLX_AD_DEFAULT_*
 #include "scene.hpp"
 #include "bvh.hpp"
 #include "envmap.hpp"
@@ -58,6 +59,15 @@ public:
     // the variance-guided filter (flx_denoise_variance_guided): needs the options "denoiser" and "moments"; otherwise as denoise()
     struct DenoiseVgParams { int iterations = 5; float sigmaLuminance = 4.0f, sigmaNormal = 0.3f, sigmaAlbedo = 0.1f, blend = 0.0f; };
     void denoiseVarianceGuided(const DenoiseVgParams &params);
+    // adaptive sampling on the microkernel integrator (flx_mk_adaptive_update / _clear): classify the pixels by the luminance
+    // moments, install the list of active ones for the following enqueueRayGenKernel ... enqueueSplatKernel, return its length (blocking)
+    // (defaults: the library's own, csrc/flx_adaptive.h)
+    struct AdaptiveParams {
+        float threshold = FLX_AD_DEFAULT_THRESHOLD; uint32_t minSamples = FLX_AD_DEFAULT_MIN_SAMPLES, maxSamples = FLX_AD_DEFAULT_MAX_SAMPLES;
+        float lumFloor = FLX_AD_DEFAULT_LUM_FLOOR; bool dilate = FLX_AD_DEFAULT_DILATE != 0u;
+    };
+    uint32_t adaptiveUpdate(const AdaptiveParams &params);
+    void adaptiveClear();
     // temporal reprojection (flx_gbuffer / flx_history_capture / flx_reproject): the primary-visibility G-buffer of the current
     // camera; the snapshot of the accumulation (and moments) with that G-buffer as the previous one; the snapshot resampled into the current
     // view over the freshly reset accumulation.  Single-GPU, asynchronous.

@@ -234,6 +234,54 @@ void Tracer::renderSingle(int spp, bool denoise)
     if (denoise && denoiserStrength > 0.0f) { denoiseStep(); clctx->finishQueue(); }   // :160-165 (output_<spp>_denoised)
 }
 
+// renderSingle to a noise threshold (no counterpart in the reference): minSpp uniform passes, then every pass runs over the
+// pixels flx_mk_adaptive_update still lists, until none is left or maxSpp passes ran.  Returns the samples taken.
+uint64_t Tracer::renderAdaptive(int minSpp, int maxSpp, float threshold, bool denoise)
+{
+    if (!peers.empty()) throw std::runtime_error("renderAdaptive: the microkernel integrator is single-GPU");
+    if (minSpp < 1 || maxSpp < minSpp || maxSpp > (1 << 24)) throw std::runtime_error("renderAdaptive: needs 1 <= minSpp <= maxSpp <= 2^24");
+    if (!(threshold >= 0.0f) || std::isinf(threshold)) throw std::runtime_error("renderAdaptive: the threshold must be finite and >= 0");
+    if (useWavefront) toggleRenderer();
+    if ((uint64_t)params.width * params.height > clctx->getNumTasks())
+        throw std::runtime_error("renderAdaptive: width*height exceeds the context's numTasks (one path per pixel)");
+    params.useRoulette = 0;
+    if (denoise) setDenoiser(true);
+    const bool hadMoments = momentsOn;
+    // whatever happens below, the context is left without a list of active pixels and with "moments" as it was
+    auto restore = [&] { clctx->adaptiveClear(); if (!hadMoments) clctx->setOption("moments", 0); };
+    uint64_t total = 0;
+    try {
+    if (!hadMoments) clctx->setOption("moments", 1);                     // for this render only
+    clctx->updateParams(params); paramsUpdatePending = false;
+    dropHistory();
+    clctx->enqueueResetKernel(params);                                   // (also clears a list of active pixels)
+    HipContext::AdaptiveParams ap;
+    ap.threshold = threshold; ap.minSamples = (uint32_t)minSpp; ap.maxSamples = (uint32_t)maxSpp;
+    uint64_t active = (uint64_t)params.width * params.height;
+    for (int sample = 0; sample < maxSpp && active > 0; sample++) {
+        if (sample >= minSpp && (active = clctx->adaptiveUpdate(ap)) == 0) break;
+        clctx->enqueueRayGenKernel(params);
+        for (uint32_t bounce = 0; bounce < params.maxBounces + 1; bounce++) {
+            clctx->enqueueNextVertexKernel(params);
+            clctx->enqueueBsdfSampleKernel(params);
+        }
+        clctx->enqueueSplatKernel(params);
+        clctx->enqueuePostprocessKernel(params);
+        clctx->fetchStatsAsync();
+        clctx->finishQueue();
+        total += active;
+        iteration++;
+    }
+    clctx->adaptiveClear();
+    if (denoise && denoiserStrength > 0.0f) { denoiseStep(); clctx->finishQueue(); }
+    } catch (...) {
+        try { restore(); } catch (...) {}                                // (the first error is the one to report)
+        throw;
+    }
+    restore();
+    return total;
+}
+
 // reference: src/tracer.cpp:268-299, microkernel branch of update()
 void Tracer::updateMicrokernel()
 {

@@ -35,6 +35,11 @@ public:
     // final-frame render: exactly `spp` samples in every pixel (reference: src/tracer.cpp:95-187).  Switches to the
     // microkernel integrator and turns Russian roulette off, as the reference does; needs numTasks >= width*height.
     void renderSingle(int spp, bool denoise = false);                             // denoise: also fill the denoiser feature buffers (and denoise, strength > 0)
+    // renderSingle to a noise threshold: every pixel takes minSpp samples, then only the pixels whose relative standard error of the
+    // mean luminance is still above `threshold` (and their 3 x 3 neighbours) go on, to at most maxSpp.  Same set-up as renderSingle (roulette off,
+    // single GPU, throws like it); turns the option "moments" on for the render when it is off and restores it.  Returns the samples taken;
+    // the per-pixel count is the accumulation's w.
+    uint64_t renderAdaptive(int minSpp, int maxSpp, float threshold, bool denoise = false);
     // the reference's denoiser strength slider (src/tracer_ui.cpp:359): blend = 1 - strength.  0 (this library's default; the reference's is 1,
     // INTEGRATION.md) only fills the feature buffers; > 0 denoises the preview every 10th frame from frame 10 on, and renderSingle's final frame.
     // Single-GPU: throws on a multi-rank Tracer.

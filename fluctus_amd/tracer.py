@@ -66,6 +66,14 @@ class Tracer:
         denoise=True also fills the denoiser feature buffers (read_pixels(2) albedo, read_pixels(3) normals)."""
         host._chk(self.L.fh_tracer_render_single(self.h, int(spp), int(bool(denoise))))
 
+    def render_adaptive(self, min_spp, max_spp, threshold, denoise=False):
+        """Tracer::renderAdaptive (DESIGN.md 4.2.1): render_single to a noise threshold -- min_spp samples everywhere, then only the pixels whose
+        relative standard error of the mean luminance is above `threshold` (and their 3 x 3 neighbours) go on, to at most max_spp.  Returns the
+        samples taken; read_pixels(0)[:, 3] is the count of every pixel."""
+        n = C.c_uint64()
+        host._chk(self.L.fh_tracer_render_adaptive(self.h, int(min_spp), int(max_spp), C.c_float(float(threshold)), int(bool(denoise)), C.byref(n)))
+        return int(n.value)
+
     def set_denoiser(self, on):
         host._chk(self.L.fh_tracer_set_denoiser(self.h, int(bool(on))))
 

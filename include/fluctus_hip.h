@@ -170,6 +170,30 @@ int flx_mk_next_vertex(flx_ctx *ctx);
 int flx_mk_sample_bsdf(flx_ctx *ctx);
 int flx_mk_splat(flx_ctx *ctx);
 int flx_mk_splat_preview(flx_ctx *ctx);
+/* ---- adaptive sampling for the microkernel integrator (no counterpart in the reference, which gives every pixel the same sample count,
+ * src/tracer.cpp:95-169; csrc/flx_adaptive.h, csrc/adaptive.hip): stop sampling a pixel when it is converged.
+ * Per pixel, from the luminance moments (which = 7; only their own n enters): mu = S1 / n, v = max(0, S2 / n - mu^2) / n (the variance of the
+ * MEAN), r = sqrt(v) / (mu + lum_floor);  done: n >= max_samples;  converged: n >= min_samples, n >= 2 and r <= threshold (a NaN or a non-finite
+ * sum never converges: such a pixel runs to max_samples);  own = !done && !converged;  active = !done && (own || (dilate && a 3 x 3
+ * neighbour inside the image has own)).
+ * flx_mk_adaptive_update classifies every pixel, compacts the active ones into an ASCENDING list (reproducible: no atomics) and INSTALLS it:
+ * the following flx_mk_raygen / flx_mk_next_vertex / flx_mk_sample_bsdf / flx_mk_splat run over the listed pixels only -- a listed pixel advances
+ * exactly as in an unlisted pass, bit for bit (the integrator's state, seed chain included, is per pixel), an unlisted pixel is not touched, and
+ * flx_mk_stats counts the listed samples only.  *out_active = the length of the list (one blocking 4-byte read); 0 installs an empty list: the
+ * four calls are no-ops.  flx_mk_splat_preview ignores the list.  Needs option "moments", an unpartitioned context and
+ * width * height <= num_tasks; params NULL = the defaults {0.05, 4, 32, 0.01, 1}.  Fails when threshold or lum_floor is not
+ * finite or < 0, max_samples is 0 or > 2^24, min_samples > max_samples, or dilate is not 0 / 1.
+ * flx_mk_adaptive_clear: back to "every pixel".  flx_mk_reset, a flx_set_params that changes the image size, flx_set_partition,
+ * flx_upload_scene and flx_set_option(ctx, "moments", 0) clear it too, so no call sequence written before these entry points meets a list.
+ * flx_mk_active_read / flx_mk_active_write: test hooks like flx_gbuffer_read / _write.  read: *out_count and, where not NULL, the installed list
+ * (out_list: room for width * height entries) and the flag byte of every pixel as the last update left it (bit 0 own, 1 active, 2 done,
+ * 3 converged; zeros after a write); fails when no list is installed.  write: installs an arbitrary list; fails unless every entry is
+ * < width * height and the list is strictly ascending.  Blocking. */
+typedef struct { float threshold; uint32_t min_samples, max_samples; float lum_floor; uint32_t dilate; } flx_adaptive_params;
+int flx_mk_adaptive_update(flx_ctx *ctx, const flx_adaptive_params *params, uint32_t *out_active);
+int flx_mk_adaptive_clear(flx_ctx *ctx);
+int flx_mk_active_read(flx_ctx *ctx, uint32_t *out_list, uint32_t *out_count, uint8_t *out_flags);
+int flx_mk_active_write(flx_ctx *ctx, const uint32_t *in_list, uint32_t n);
 /* fetchStatsAsync / resetStats (src/clcontext.cpp:634-646): RenderStats {primaryRays, extensionRays, shadowRays, samples}
  * (4 x u32, src/geom.h:254-260) accumulated on the device by the microkernels; *out16 valid after flx_finish() */
 int flx_mk_stats_async(flx_ctx *ctx, void *out16);
