@@ -9,7 +9,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fluctus_amd")
 
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-             "-munsafe-fp-atomics", "-fgpu-rdc" if False else "-fno-gpu-rdc"]
+             "-munsafe-fp-atomics", "-fgpu-rdc" if False else "-fno-gpu-rdc",
+             # a launcher whose definition drifted from csrc/flx_launch.h is an undefined symbol: fail here, not when Python dlopens the library
+             "-Wl,--no-undefined"]
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared"]
 
 

@@ -11,6 +11,7 @@
 // Every flag comes from ad_pixel in its order, so it equals the counterpart's bit for bit.
 #include "flx_device.h"
 #include "flx_adaptive.h"
+#include "flx_launch.h"
 
 namespace flxd {
 

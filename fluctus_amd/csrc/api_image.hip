@@ -1,0 +1,276 @@
+// api_image.hip -- what works on the image rather than on the wavefront queues: flx_postprocess, the two a-trous denoisers, temporal
+// reprojection (G-buffer slots, history capture), and the microkernel integrator with its adaptive render and statistics.
+#include "flx_ctx.h"
+#include "flx_denoise.h"
+#include "flx_denoise_vg.h"
+#include "flx_reproject.h"
+#include "flx_adaptive.h"
+#include <cstring>
+
+extern "C" {
+
+int flx_postprocess(flx_ctx *c) { READY(c, CALL_OBSERVE); { ScopedTimer t(c, FLX_K_POSTPROCESS); launch_postprocess(c->stream, c->fr, c->params); } LAUNCHED(c); return 0; }
+
+// flx_denoise and flx_denoise_variance_guided: the checks, the working set (allocated by the first call), the timer and dnHave.  fn names the
+// entry point in the messages, sigma0 its first sigma; the variance-guided filter needs the luminance moments.
+typedef void (*DenoiseLaunch)(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float, float,
+                              const flx_render_params &);
+static int denoiseCall(flx_ctx *c, const char *fn, DenoiseLaunch launch, bool moments, const char *sigma0, int iterations, float s0, float sigma_n,
+                       float sigma_a, float blend)
+{
+    READY(c, CALL_OBSERVE);
+    NEED(c, c->denoiser && c->fr.aovAlbedo && c->fr.aovNormal, std::string(fn) + ": needs the feature buffers: flx_set_option(ctx, \"denoiser\", 1)");
+    if (moments)
+        NEED(c, c->moments && c->fr.moments, std::string(fn) + ": needs the luminance moments: flx_set_option(ctx, \"moments\", 1)");
+    NEED(c, c->fr.nranks == 1, std::string(fn) + ": the context is partitioned (nranks > 1): a pixel's neighbours are on other ranks -- single-GPU only");
+    NEED(c, iterations >= 0 && iterations <= FLX_DN_MAX_ITERATIONS, std::string(fn) + ": iterations must be 0..8");
+    NEED(c, dn_finite(s0) && s0 > 0.0f && dn_finite(sigma_n) && sigma_n > 0.0f && dn_finite(sigma_a) && sigma_a > 0.0f,
+         std::string(fn) + ": " + sigma0 + ", sigma_normal and sigma_albedo must be finite and > 0");
+    NEED(c, blend == blend, std::string(fn) + ": blend is NaN");
+    const int W = (int)c->params.width, H = (int)c->params.height;
+    NEED(c, (uint64_t)W * H == c->fr.localPixels, std::string(fn) + ": framebuffer does not match width x height");
+    if (!c->dn.out) {
+        const size_t n = c->fr.localPixels;
+        if (dalloc(c, c->dn.allocs, &c->dn.e[0], n) || dalloc(c, c->dn.allocs, &c->dn.e[1], n) || dalloc(c, c->dn.allocs, &c->dn.g, n) ||
+            dalloc(c, c->dn.allocs, &c->dn.g2, n) || dalloc(c, c->dn.allocs, &c->dn.out, n * 4)) { c->dn.release(); return 1; }
+    }
+    { ScopedTimer t(c, FLX_K_DENOISE);
+      launch(c->stream, c->fr, c->dn.e[0], c->dn.e[1], c->dn.g, c->dn.g2, c->dn.out, W, H, iterations, s0, sigma_n, sigma_a, dn_blend(blend), c->params); }
+    LAUNCHED(c);
+    c->dn.have = true;
+    return 0;
+}
+
+// DenoiserOptix::denoise (reference: src/denoiser/OptixDenoiser.cpp) as the guided a-trous filter of csrc/flx_denoise.h: reads which = 0 / 4 / 5,
+// writes which = 6 and the preview (which = 1).  Asynchronous; deferred and fused launches are flushed first (CALL_OBSERVE).
+int flx_denoise(flx_ctx *c, const flx_denoise_params *pp)
+{
+    flx_denoise_params p = {FLX_DN_DEFAULT_ITERATIONS, FLX_DN_DEFAULT_SIGMA_COLOR, FLX_DN_DEFAULT_SIGMA_NORMAL, FLX_DN_DEFAULT_SIGMA_ALBEDO, 0.0f};
+    if (pp) p = *pp;
+    return denoiseCall(c, "flx_denoise", launch_denoise<DnGuided>, false, "sigma_color", p.iterations, p.sigma_color, p.sigma_normal, p.sigma_albedo,
+                       p.blend);
+}
+
+// the variance-guided filter of csrc/flx_denoise_vg.h: flx_denoise's inputs plus the luminance moments (which = 7); the same
+// outputs, working set (the variance rides in e.w), timer and flushing.
+int flx_denoise_variance_guided(flx_ctx *c, const flx_denoise_vg_params *pp)
+{
+    flx_denoise_vg_params p = {FLX_VG_DEFAULT_ITERATIONS, FLX_VG_DEFAULT_SIGMA_LUMINANCE, FLX_VG_DEFAULT_SIGMA_NORMAL, FLX_VG_DEFAULT_SIGMA_ALBEDO, 0.0f};
+    if (pp) p = *pp;
+    return denoiseCall(c, "flx_denoise_variance_guided", launch_denoise<DnVg>, true, "sigma_luminance", p.iterations, p.sigma_luminance,
+                       p.sigma_normal, p.sigma_albedo, p.blend);
+}
+
+// ---- temporal reprojection (csrc/flx_reproject.h, reproject.hip).  All of it needs an unpartitioned context: a pixel's
+// neighbours must be local.  Every entry point flushes deferred and fused launches first (CALL_OBSERVE) and touches no path state, queue or counter.
+static int temporalReady(flx_ctx *c, const char *fn)
+{
+    NEED(c, c->haveParams && c->fr.pixels, std::string(fn) + ": set params first (flx_set_params)");
+    NEED(c, c->fr.nranks == 1, std::string(fn) + ": the context is partitioned (nranks > 1): a pixel's neighbours are on other ranks -- single-GPU only");
+    NEED(c, (uint64_t)c->params.width * c->params.height == c->fr.localPixels, std::string(fn) + ": framebuffer does not match width x height");
+    return 0;
+}
+static int gbufferSlots(flx_ctx *c)
+{
+    if (c->temporal.gb[0]) return 0;
+    const size_t n = (size_t)c->fr.localPixels * 2;
+    if (dalloc(c, c->temporal.allocs, &c->temporal.gb[0], n) || dalloc(c, c->temporal.allocs, &c->temporal.gb[1], n)) { c->temporal.release(); return 1; }
+    return 0;
+}
+int flx_gbuffer(flx_ctx *c)
+{
+    READY(c, CALL_OBSERVE);
+    if (temporalReady(c, "flx_gbuffer") || gbufferSlots(c)) return 1;
+    { ScopedTimer t(c, FLX_K_GBUFFER);
+      launch_gbuffer(c->stream, c->sc, c->params, c->spill, c->numTasks, (c->extendTree == 4 && c->wideOK) ? 4 : 2, c->temporal.gb[0], c->fr.localPixels); }
+    LAUNCHED(c);
+    c->temporal.gbCam[0] = c->params.camera; c->temporal.gbW[0] = c->params.width; c->temporal.gbH[0] = c->params.height; c->temporal.gbTraced[0] = true;
+    return 0;
+}
+int flx_history_capture(flx_ctx *c)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (temporalReady(c, "flx_history_capture")) return 1;
+    NEED(c, c->temporal.gb[0] && c->temporal.gbTraced[0], "flx_history_capture: no G-buffer has been traced for the current slot (flx_gbuffer first)");
+    NEED(c, c->temporal.gbW[0] == c->params.width && c->temporal.gbH[0] == c->params.height, "flx_history_capture: the image size differs from the G-buffer's");
+    const size_t n = c->fr.localPixels;
+    const bool withMom = c->moments && c->fr.moments;
+    // (the moments' copy is allocated when first needed; a failed allocation releases slots and history together, so a retry starts clean)
+    if ((!c->temporal.hist && dalloc(c, c->temporal.allocs, &c->temporal.hist, n)) || (withMom && !c->temporal.histMomBuf && dalloc(c, c->temporal.allocs, &c->temporal.histMomBuf, n))) {
+        const std::string why = c->err; c->temporal.release(); c->err = "flx_history_capture: " + why; return 1;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->temporal.hist, c->fr.pixels, n * 16, hipMemcpyDeviceToDevice, c->stream));
+    c->temporal.histHasMom = withMom;
+    if (c->temporal.histHasMom) HIPCHK(c, hipMemcpyAsync(c->temporal.histMomBuf, c->fr.moments, n * 16, hipMemcpyDeviceToDevice, c->stream));
+    std::swap(c->temporal.gb[0], c->temporal.gb[1]);
+    c->temporal.gbCam[1] = c->temporal.gbCam[0]; c->temporal.gbW[1] = c->temporal.gbW[0]; c->temporal.gbH[1] = c->temporal.gbH[0]; c->temporal.gbTraced[1] = true;
+    c->temporal.gbTraced[0] = false;
+    c->temporal.histHave = true;
+    return 0;
+}
+int flx_reproject(flx_ctx *c, const flx_reproject_params *pp)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (temporalReady(c, "flx_reproject")) return 1;
+    rp_params rp = {FLX_RP_DEFAULT_MAX_HISTORY, FLX_RP_DEFAULT_PLANE_TOLERANCE_PX, FLX_RP_DEFAULT_NORMAL_COS, FLX_RP_DEFAULT_MIN_WEIGHT};
+    if (pp) { rp.max_history = pp->max_history; rp.plane_tolerance_px = pp->plane_tolerance_px; rp.normal_cos = pp->normal_cos; rp.min_weight = pp->min_weight; }
+    NEED(c, rp_params_ok(rp), "flx_reproject: parameters must be finite with max_history >= 1, plane_tolerance_px > 0, normal_cos in [-1, 1], min_weight in (0, 1]");
+    NEED(c, c->temporal.histHave && c->temporal.gbTraced[1], "flx_reproject: no captured history (flx_history_capture first)");
+    NEED(c, c->temporal.gbTraced[0], "flx_reproject: no G-buffer has been traced for the current camera (flx_gbuffer first)");
+    NEED(c, c->temporal.gbW[0] == c->params.width && c->temporal.gbH[0] == c->params.height && c->temporal.gbW[1] == c->temporal.gbW[0] && c->temporal.gbH[1] == c->temporal.gbH[0],
+         "flx_reproject: the image size changed between the capture and the reprojection");
+    const flx_camera &pc = c->temporal.gbCam[1];
+    const rp_view vw = rp_make_view(mk3(pc.pos.x, pc.pos.y, pc.pos.z), mk3(pc.dir.x, pc.dir.y, pc.dir.z), mk3(pc.up.x, pc.up.y, pc.up.z), mk3(pc.right.x, pc.right.y, pc.right.z), pc.fov, c->temporal.gbCam[0].fov, (int)c->params.width, (int)c->params.height);
+    const bool mom = c->moments && c->fr.moments && c->temporal.histHasMom;
+    { ScopedTimer t(c, FLX_K_REPROJECT);
+      launch_reproject(c->stream, vw, rp, c->temporal.gb[0], c->temporal.gb[1], c->temporal.hist, c->temporal.histMomBuf, reinterpret_cast<float4 *>(c->fr.pixels),
+                       mom ? reinterpret_cast<float4 *>(c->fr.moments) : nullptr); }
+    LAUNCHED(c);
+    return 0;
+}
+// test hooks in the spirit of flx_state_import: slot 0 = current, 1 = previous; 8 floats per pixel (G0, G1) and the slot's 80-byte camera.  Blocking.
+int flx_gbuffer_read(flx_ctx *c, int slot, float *out8, void *camera80)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, slot == 0 || slot == 1, "flx_gbuffer_read: slot must be 0 (current) or 1 (previous)");
+    NEED(c, out8, "flx_gbuffer_read: null output");
+    NEED(c, c->temporal.gb[slot] && c->temporal.gbTraced[slot], "flx_gbuffer_read: the slot holds no G-buffer");
+    HIPCHK(c, hipMemcpyAsync(out8, c->temporal.gb[slot], (size_t)c->temporal.gbW[slot] * c->temporal.gbH[slot] * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (camera80) memcpy(camera80, &c->temporal.gbCam[slot], sizeof(flx_camera));
+    return 0;
+}
+int flx_gbuffer_write(flx_ctx *c, int slot, const float *in8, const void *camera80)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, slot == 0 || slot == 1, "flx_gbuffer_write: slot must be 0 (current) or 1 (previous)");
+    NEED(c, in8 && camera80, "flx_gbuffer_write: null G-buffer or camera");
+    if (temporalReady(c, "flx_gbuffer_write") || gbufferSlots(c)) return 1;
+    HIPCHK(c, hipMemcpyAsync(c->temporal.gb[slot], in8, (size_t)c->fr.localPixels * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(&c->temporal.gbCam[slot], camera80, sizeof(flx_camera));
+    c->temporal.gbW[slot] = c->params.width; c->temporal.gbH[slot] = c->params.height; c->temporal.gbTraced[slot] = true;
+    return 0;
+}
+
+// ---- microkernel integrator.  One path per pixel, framebuffers indexed by the path id: single-GPU only, the pixel
+// partition belongs to the wavefront path (allocFrame sizes the buffers for the rank's LOCAL pixels).
+#define MK_READY(c) do { READY(c, CALL_OBSERVE); NEED(c, (c)->fr.nranks == 1, "the microkernel integrator is single-GPU: flx_set_partition(ctx, 0, 1) first"); } while (0)
+int flx_mk_reset(flx_ctx *c) { MK_READY(c); c->ad.have = false; launch_mk_reset(c->stream, c->st, c->fr, c->params); LAUNCHED(c); return 0; }
+// with a list of active pixels installed (flx_mk_adaptive_update / flx_mk_active_write) the four kernels of a sample pass run their list-driven
+// instances over it; an empty list makes them no-ops
+int flx_mk_raygen(flx_ctx *c)
+{
+    MK_READY(c);
+    if (!c->ad.have) launch_mk_raygen(c->stream, c->st, c->params);
+    else if (c->ad.count) launch_mk_raygen_list(c->stream, c->st, c->params, c->ad.list, c->ad.count);
+    LAUNCHED(c); return 0;
+}
+int flx_mk_next_vertex(flx_ctx *c)
+{
+    MK_READY(c);
+    if (!c->ad.have) launch_mk_next_vertex(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
+    else if (c->ad.count) launch_mk_next_vertex_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ad.list, c->ad.count);
+    LAUNCHED(c); return 0;
+}
+int flx_mk_sample_bsdf(flx_ctx *c)
+{
+    MK_READY(c);
+    if (!c->ad.have) launch_mk_sample_bsdf(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
+    else if (c->ad.count) launch_mk_sample_bsdf_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ad.list, c->ad.count);
+    LAUNCHED(c); return 0;
+}
+int flx_mk_splat(flx_ctx *c)
+{
+    MK_READY(c);
+    if (!c->ad.have) launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 0);
+    else if (c->ad.count) launch_mk_splat_list(c->stream, c->st, c->fr, c->params, c->mkStats, c->ad.list, c->ad.count);
+    LAUNCHED(c); return 0;
+}
+int flx_mk_splat_preview(flx_ctx *c) { MK_READY(c); launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 1); LAUNCHED(c); return 0; }
+
+// ---- adaptive sampling (adaptive.hip, csrc/flx_adaptive.h)
+static int adaptiveReady(flx_ctx *c, const char *fn)
+{
+    NEED(c, c->fr.nranks == 1, std::string(fn) + ": the microkernel integrator is single-GPU: flx_set_partition(ctx, 0, 1) first");
+    const uint64_t npix = (uint64_t)c->params.width * c->params.height;
+    NEED(c, npix <= c->numTasks, std::string(fn) + ": needs one path per pixel: width * height <= num_tasks");
+    if (c->ad.pix != (uint32_t)npix || !c->ad.list) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->ad.release();
+        if (dalloc(c, c->ad.allocs, &c->ad.flags, (size_t)npix) || dalloc(c, c->ad.allocs, &c->ad.scratch, (size_t)adaptive_blocks((uint32_t)npix)) ||
+            dalloc(c, c->ad.allocs, &c->ad.list, (size_t)npix) || dalloc(c, c->ad.allocs, &c->ad.countDev, 1)) { c->ad.release(); return 1; }
+        c->ad.pix = (uint32_t)npix;
+    }
+    return 0;
+}
+int flx_mk_adaptive_update(flx_ctx *c, const flx_adaptive_params *pp, uint32_t *out_active)
+{
+    READY(c, CALL_OBSERVE);
+    NEED(c, c->moments && c->fr.moments, "flx_mk_adaptive_update: needs the luminance moments: flx_set_option(ctx, \"moments\", 1)");
+    NEED(c, out_active, "flx_mk_adaptive_update: null output");
+    ad_params ap = {FLX_AD_DEFAULT_THRESHOLD, FLX_AD_DEFAULT_MIN_SAMPLES, FLX_AD_DEFAULT_MAX_SAMPLES, FLX_AD_DEFAULT_LUM_FLOOR, FLX_AD_DEFAULT_DILATE};
+    if (pp) { ap.threshold = pp->threshold; ap.min_samples = pp->min_samples; ap.max_samples = pp->max_samples; ap.lum_floor = pp->lum_floor; ap.dilate = pp->dilate; }
+    NEED(c, ad_params_ok(ap), "flx_mk_adaptive_update: threshold and lum_floor must be finite and >= 0, 1 <= max_samples <= 2^24, min_samples <= max_samples, dilate 0 or 1");
+    if (adaptiveReady(c, "flx_mk_adaptive_update")) return 1;
+    launch_adaptive_update(c->stream, reinterpret_cast<const float4 *>(c->fr.moments), (int)c->params.width, (int)c->params.height, ap, c->ad.flags, c->ad.scratch,
+                           c->ad.list, c->ad.countDev);
+    LAUNCHED(c);
+    uint32_t n = 0;
+    HIPCHK(c, hipMemcpyAsync(&n, c->ad.countDev, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    NEED(c, n <= c->ad.pix, "flx_mk_adaptive_update: the device returned an impossible count");
+    c->ad.count = n; c->ad.have = true;
+    *out_active = n;
+    return 0;
+}
+int flx_mk_adaptive_clear(flx_ctx *c) { ENTER(c, CALL_OBSERVE); c->ad.have = false; return 0; }
+// test hooks in the spirit of flx_gbuffer_read / flx_gbuffer_write.  Blocking.
+int flx_mk_active_read(flx_ctx *c, uint32_t *out_list, uint32_t *out_count, uint8_t *out_flags)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, out_count, "flx_mk_active_read: null count");
+    NEED(c, c->ad.have, "flx_mk_active_read: no list of active pixels is installed");
+    *out_count = c->ad.count;
+    if (out_list && c->ad.count) HIPCHK(c, hipMemcpyAsync(out_list, c->ad.list, (size_t)c->ad.count * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_flags) HIPCHK(c, hipMemcpyAsync(out_flags, c->ad.flags, (size_t)c->ad.pix, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+int flx_mk_active_write(flx_ctx *c, const uint32_t *in_list, uint32_t n)
+{
+    READY(c, CALL_OBSERVE);
+    NEED(c, in_list || !n, "flx_mk_active_write: null list");
+    const uint64_t npix = (uint64_t)c->params.width * c->params.height;
+    NEED(c, n <= npix, "flx_mk_active_write: more entries than pixels");
+    for (uint32_t i = 0; i < n; i++) {
+        NEED(c, in_list[i] < npix, "flx_mk_active_write: pixel index out of range");
+        NEED(c, i == 0 || in_list[i] > in_list[i - 1], "flx_mk_active_write: the list must be strictly ascending");
+    }
+    if (adaptiveReady(c, "flx_mk_active_write")) return 1;
+    HIPCHK(c, hipMemsetAsync(c->ad.flags, 0, c->ad.pix, c->stream));       // (the flags describe a classification; a written list has none)
+    if (n) HIPCHK(c, hipMemcpyAsync(c->ad.list, in_list, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ad.count = n; c->ad.have = true;
+    return 0;
+}
+
+int flx_mk_stats_async(flx_ctx *c, void *out16)
+{
+    ENTER(c, CALL_OBSERVE);
+    NEED(c, out16, "flx_mk_stats_async: null");
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((int)c->pendingMk.size() >= c->pinnedSlots) { c->err = "too many outstanding stats reads; call flx_finish"; return 1; }
+    int slot = c->nextMkSlot; c->nextMkSlot = (c->nextMkSlot + 1) % c->pinnedSlots;
+    HIPCHK(c, hipMemcpyAsync(c->pinnedMk + 4 * slot, c->mkStats, 16, hipMemcpyDeviceToHost, c->stream));
+    c->pendingMk.push_back({out16, slot});
+    return 0;
+}
+int flx_mk_stats_reset(flx_ctx *c) { ENTER(c, CALL_OBSERVE); HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipMemsetAsync(c->mkStats, 0, 16, c->stream)); return 0; }
+
+} // extern "C"

@@ -16,6 +16,7 @@
 #include "flx_device.h"
 #include "flx_denoise.h"
 #include "flx_denoise_vg.h"
+#include "flx_launch.h"
 
 namespace flxd {
 

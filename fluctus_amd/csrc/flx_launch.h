@@ -1,0 +1,56 @@
+// flx_launch.h -- the host-side launchers and helpers of the kernel files, declared ONCE: every .hip file that defines one of them includes
+// this header and so does every file that calls one, so a definition that drifts from its declaration is an error of the build (an overload the
+// caller cannot reach is left undefined, and the library is linked with -Wl,--no-undefined: fluctus_amd/build.py).
+#pragma once
+#include "flx_device.h"
+
+namespace flx { struct ad_params; struct rp_view; struct rp_params; }     // flx_adaptive.h, flx_reproject.h: passed by reference only
+
+namespace flxd {
+void launch_extend(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *, int);
+void launch_shadow(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *, int);
+void launch_extend4(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *);
+void launch_shadow4(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *);
+void launch_shadow4_split(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, uint32_t *, uint32_t, uint4 *, uint32_t, uint4 *, uint32_t, int, int, uint32_t);
+uint32_t shadow_split_lists(); uint32_t shadow_split_count_words();
+void launch_extend4r(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, uint32_t *);
+void launch_shadow4r(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, uint32_t *);
+void launch_logic(hipStream_t, const State &, const Queues &, const Scene &, const Frame &, const flx_render_params &, uint8_t *, uint32_t *, uint32_t *, int, int, int, int, int,
+                  unsigned long long *, uint32_t, int, int, uint32_t *, int);
+void launch_env_nee_table(hipStream_t, const Scene &, float4 *, uint32_t);
+int logic_can_regenerate();
+uint32_t logic_lookback_words(uint32_t numTasks);
+void launch_materialise(hipStream_t, const State &, const Scene &, const flx_render_params &, uint32_t);
+void launch_materials(hipStream_t, const State &, const Queues &, const Scene &, uint32_t);
+void launch_materials_after_fused(hipStream_t, const State &, const Queues &, const Scene &, uint32_t, int);
+uint32_t fused_queue_mask(int);
+uint32_t logic_aux_stride(uint32_t);
+void launch_reset(hipStream_t, const State &, const Queues &, const Frame &, const flx_render_params &);
+void launch_raygen(hipStream_t, const State &, const Queues &, const Frame &, const flx_render_params &, int, int);
+void launch_postprocess(hipStream_t, const Frame &, const flx_render_params &);
+void launch_state_export(hipStream_t, const State &, float *, float);
+void launch_state_import(hipStream_t, const State &, const float *);
+void launch_math_probe(hipStream_t, int, const float *, const float *, uint32_t, uint32_t *);
+void launch_mk_reset(hipStream_t, const State &, const Frame &, const flx_render_params &);
+void launch_mk_raygen(hipStream_t, const State &, const flx_render_params &);
+void launch_mk_next_vertex(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *);
+void launch_mk_sample_bsdf(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *);
+void launch_mk_splat(hipStream_t, const State &, const Frame &, const flx_render_params &, uint32_t *, int);
+void launch_mk_raygen_list(hipStream_t, const State &, const flx_render_params &, const uint32_t *, uint32_t);
+void launch_mk_next_vertex_list(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const uint32_t *, uint32_t);
+void launch_mk_sample_bsdf_list(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const uint32_t *, uint32_t);
+void launch_mk_splat_list(hipStream_t, const State &, const Frame &, const flx_render_params &, uint32_t *, const uint32_t *, uint32_t);
+uint32_t adaptive_blocks(uint32_t);
+void launch_adaptive_update(hipStream_t, const float4 *, int, int, const ad_params &, uint8_t *, uint32_t *, uint32_t *, uint32_t *);
+void launch_end_iteration(hipStream_t, uint32_t *, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t *);
+void launch_bump_extension(hipStream_t, uint32_t *, uint32_t);
+void launch_deinterleave(hipStream_t, const float *, float *, uint32_t, uint32_t, uint32_t);
+struct DnGuided; struct DnVg;     // the two filters of denoise.hip
+template <class F> void launch_denoise(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float,
+                                       float, const flx_render_params &);
+void launch_gbuffer(hipStream_t, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, float4 *, uint32_t);
+void launch_reproject(hipStream_t, const rp_view &, const rp_params &, const float4 *, const float4 *, const float4 *, const float4 *, float4 *, float4 *);
+#ifdef FLX_LAB_RSTATS
+extern unsigned long long *g_lab_rstats;
+#endif
+}

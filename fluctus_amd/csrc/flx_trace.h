@@ -138,7 +138,7 @@ __device__ __forceinline__ void commit_hit(const State &st, const Scene &sc, con
 //     HITUV = {u, v, FLX_RAW | (triangle + 1), t}
 // and the commit -- implicit area-light quad included -- happens where the record is consumed anyway: in the fused logic pass of the next
 // iteration (logic.hip: k_logic<FUSE, RAW>), which has the ray in registers and needs the shading attributes next -- or, when anything else
-// wants to look first (a read-back, the separate kernels, the microkernels ...), in k_materialise (api.hip: settle).  A committed record
+// wants to look first (a read-back, the separate kernels, the microkernels ...), in k_materialise (api_wavefront.hip: enter, materialise).  A committed record
 // holds the hit index there (>= -1), so bits 31:30 == 01 marks a raw one unambiguously for scenes below 2^30 triangles.
 #define FLX_RAW       0x40000000u
 #define FLX_RAW_TRI   0x3FFFFFFFu

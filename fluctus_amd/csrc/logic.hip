@@ -25,6 +25,7 @@
 #include "flx_bsdf.h"
 #include "flx_trace.h"          // hit_values_raw: the commit of traceExtension for RAW hit records
 #include "flx_denoise.h"        // flx_lum: the luminance moments (option "moments")
+#include "flx_launch.h"
 
 namespace flxd {
 

@@ -12,6 +12,7 @@
 // the extension queue at a COMPUTED slot (extension base + lengths of the source queues appended earlier
 // + own index; no atomic -- see flx_device.h).
 #include "flx_bsdf.h"
+#include "flx_launch.h"
 
 namespace flxd {
 

@@ -9,6 +9,7 @@
 #include "flx_trace.h"
 #include "flx_bsdf.h"
 #include "flx_denoise.h"        // flx_lum: the luminance moments (option "moments")
+#include "flx_launch.h"
 
 namespace flxd {
 

@@ -4,6 +4,7 @@
 // process (src/mk_postprocess.cl:7-55, src/tonemap.cl:3-26).
 #include "flx_shading.h"
 #include "flx_denoise.h"
+#include "flx_launch.h"
 
 namespace flxd {
 

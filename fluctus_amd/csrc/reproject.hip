@@ -13,6 +13,7 @@
 #include "flx_trace4.h"
 #include "flx_shading.h"
 #include "flx_reproject.h"
+#include "flx_launch.h"
 
 namespace flxd {
 

@@ -18,6 +18,7 @@
 //  * arithmetic is the contract of include/flx_math.h: slab test as (box - orig) * (1/dir),
 //    Moller-Trumbore with EPSILON 1e-12, no FMA contraction -> bit-identical to the oracle.
 #include "flx_trace.h"
+#include "flx_launch.h"
 
 namespace flxd {
 

@@ -8,6 +8,7 @@
 //    for box-vs-triangle rounding near-ties; tests/test_gpu_wide.py counts those flips against the oracle.
 // One wave per block, traversal stack in LDS [level][lane] as in trace.hip.
 #include "flx_trace4.h"
+#include "flx_launch.h"
 
 namespace flxd {
 

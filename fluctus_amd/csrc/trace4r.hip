@@ -28,6 +28,7 @@
 // Replaces reference kernels traceExtension (src/wf_extrays.cl:5-36) and traceShadow (src/wf_shadowrays.cl:6-38).
 #include "flx_trace4.h"
 #include <cstdlib>
+#include "flx_launch.h"
 
 namespace flxd {
 

@@ -289,7 +289,7 @@ int flx_set_counters(flx_ctx *ctx, const void *in32);
  *                     DESIGN.md 4.1) | 2: the reference's binary tree in the reference's visit order (bit-exact)
  *   overlap           0 serial | 1 flx_wf_shadow directly after flx_wf_extend runs concurrently with it on a second stream |
  *                     2 as 1, and it starts as soon as `logic` is done when only raygen / materials / extend
- *                     were enqueued since flx_wf_logic (see flx_wf_shadow in api.hip) | -1 (default) = 2; flx_get_option returns the
+ *                     were enqueued since flx_wf_logic (see flx_wf_shadow in api_wavefront.hip) | -1 (default) = 2; flx_get_option returns the
  *                     effective value
  *   refill_extend     the closest-hit query on the 4-wide tree as a PERSISTENT kernel (csrc/trace4r.hip): value = refillMin | waitMax << 8
  *                     -- lanes that finished take new rays when refillMin lanes are idle; a descent round ends when waitMax lanes
@@ -335,7 +335,7 @@ int flx_set_counters(flx_ctx *ctx, const void *in32);
 int flx_set_option(flx_ctx *ctx, const char *name, int value);
 /* current value of an option above, or of the read-only "fused_queue_mask" (bit q set = the fused pass inlines the material step of
  * queue q's paths, flx_queue_counters order), or of the read-only "phase": the state of the call-sequence state machine behind the
- * deferred / fused / early-started kernels (api.hip: enum Phase) -- bits 0-2: 0 idle, 1 flx_wf_logic deferred, 2 flx_wf_logic +
+ * deferred / fused / early-started kernels (flx_ctx.h: enum Phase) -- bits 0-2: 0 idle, 1 flx_wf_logic deferred, 2 flx_wf_logic +
  * flx_wf_raygen deferred, 3 only genRays / material kernels enqueued since logic, 4 ... and the extension kernel last, 5 the extension
  * kernel last with the chain since logic broken; bit 3: the hit records of the last extension launch are still RAW; bit 4: the material
  * queues are known to be empty.  Never changes any state (tests/test_gpu_fuzz.py reports its coverage with it). */

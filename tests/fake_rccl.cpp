@@ -1,4 +1,4 @@
-// fake_rccl.cpp -- TEST INFRASTRUCTURE: a stand-in for librccl with the entry points libfluctus_hip.so binds (api.hip: rccl_load),
+// fake_rccl.cpp -- TEST INFRASTRUCTURE: a stand-in for librccl with the entry points libfluctus_hip.so binds (api_group.hip: rccl_load),
 // selected with FLX_RCCL_LIB=<this library>.  RCCL refuses communicators with duplicate devices, so on the 1-GPU test box the
 // ncclSend / ncclRecv branches of flx_gather / flx_gather_local could never run with more than one rank.  Here the "ranks" are host
 // THREADS of one process (or several comms driven by one thread, ncclCommInitAll style) whose contexts may all sit on device 0:
@@ -10,7 +10,7 @@
 //     device) on its own stream; the sender's stream then waits for the copy, so the send buffer may be reused in stream order --
 //     the ordering contract of the real library, minus the xGMI transport.
 // FAKE_RCCL_BREAK=1 corrupts the first float of every received message (a transport that delivers wrong bytes); =2 drops every
-// send (the receiver times out); =3 makes ncclRecv fail inside the group (the error path of api.hip's always-closed groups); =4 makes ncclCommInitRank fail.
+// send (the receiver times out); =3 makes ncclRecv fail inside the group (the error path of api_group.hip's always-closed groups); =4 makes ncclCommInitRank fail.
 // It contains no product code and the product never loads it unless FLX_RCCL_LIB says so.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>

@@ -3,7 +3,7 @@ libfluctus_hip.so first binds its RCCL entry points, and other tests of the suit
 
   python tests/rccl_fake_driver.py <nranks> <root> <mode>
     mode threads : one host thread per rank, each with its own context on device 0: flx_group_unique_id / flx_group_init / flx_gather
-                   -- the one-process-per-GPU code path of api.hip (ncclCommInitRank, grouped ncclSend on the peers, ncclRecv on the root)
+                   -- the one-process-per-GPU code path of api_group.hip (ncclCommInitRank, grouped ncclSend on the peers, ncclRecv on the root)
     mode local   : one thread, flx_group_init_local / flx_gather_local -- the single-process path (ncclCommInitAll, sends and receives
                    of all ranks inside one group)
 Prints one JSON line: {"ok": bool, "errors": [...], "counters": [...], "info": [[count, rank], ...], "depth": group depth after the calls}.

@@ -1,4 +1,4 @@
-"""Fuzzing the call-sequence state machine of the boundary (csrc/api.hip).
+"""Fuzzing the call-sequence state machine of the boundary (csrc/api_wavefront.hip).
 
 The library defers and fuses behind the reference's entry points: flx_wf_logic is deferred until the next call shows whether the fused
 logic + material pass can run, flx_wf_raygen is deferred along, the persistent extension kernel leaves RAW hit records that the next fused
@@ -244,7 +244,7 @@ def test_call_sequence_fuzz(separate_queues, seed, n):
     for call in ("logic", "raygen", "materials", "extend", "shadow", "clear", "export", "counters", "params"):
         assert len(by_call.get(call, ())) >= 3, (call, by_call.get(call))
     # ... and the chain calls under every extension-queue order, each from at least two phases (ext_order 2 couples the fused scatter with the
-    # deferred genRays: api.hip extOrderFor / runRaygen)
+    # deferred genRays: api_wavefront.hip extOrderFor / runRaygen)
     for order in (0, 1, 2):
         for call in ("logic", "raygen", "materials", "extend", "clear", "end_iter"):
             phs = {ph for (eo, ph, c_) in covered_order if eo == order and c_ == call}

@@ -22,7 +22,7 @@ TRACE_MODE = {"ext": 2, "shadow": 4, "xcd": 0, "overlap": 2, "fuse": 1, "fuse_se
 # extend_tree is 2 throughout (the reference's visit order); the 4-wide closest-hit kernel is order-dependent in exact ties and
 # has its own tests with a flip count (tests/test_gpu_wide.py).  shadow_tree 4 (the default) is exact by construction.
 # fuse: logic + material kernels as one pass whenever flx_wf_materials follows flx_wf_logic with at most genRays between them (the
-# default; api.hip) vs always the separate kernels.
+# default; api_wavefront.hip) vs always the separate kernels.
 # fuse_set: the BSDF types that pass inlines -- 0 = what flx_upload_scene picked for the scene, 1 diffuse only (the rest through their
 # queues), 31 all.
 # ext_order: -1 = what the suite always used (1 with fuse_set 31, else 0 / the scene's), 2 = regenerated + continuing paths merged by path id.
@@ -120,7 +120,7 @@ def _lockstep(g, o, npix, iters):
 
 def _lockstep_iterations(g, o, npix, iters, order=("logic", "raygen", "materials"), separate_queues=1):
     """Whole-iteration lockstep: logic / genRays / materials enqueued back to back as the reference's host does
-    (src/tracer.cpp:247-251), which is when the device runs logic and the material kernels as ONE fused pass (api.hip); state,
+    (src/tracer.cpp:247-251), which is when the device runs logic and the material kernels as ONE fused pass (api_wavefront.hip); state,
     counters and every queue -- the extension queue's order included -- compared after the three calls, then after the two
     traversals.  `_lockstep` above looks at the state after every single call and therefore always gets the separate kernels."""
     fns = {"logic": lambda c: c.wf_logic(False), "raygen": lambda c: c.wf_raygen(), "materials": lambda c: c.wf_materials()}
@@ -132,7 +132,7 @@ def _lockstep_iterations(g, o, npix, iters, order=("logic", "raygen", "materials
             for name in order:
                 fns[name](c)
         fused_now = bool(TRACE_MODE["fuse"] and (separate_queues or g.get_option("fused_queue_mask") == 0xF8)) and g.get_option("ext_order") >= 1
-        # ext_order 2 merges the regenerated paths in only when genRays sits between logic and the material kernels (api.hip: extOrderFor)
+        # ext_order 2 merges the regenerated paths in only when genRays sits between logic and the material kernels (api_wavefront.hip: extOrderFor)
         merged = fused_now and g.get_option("ext_order") == 2 and tuple(order) == ("logic", "raygen", "materials")
         _compare(g, o, f"it{it} {'+'.join(order)}", ext_set=("merged" if merged else fused_now))
         cnt = o.get_counters().copy()
@@ -187,7 +187,7 @@ def test_lockstep_all_bsdfs_flag_matrix(area, env, expl, impl, sep, roulette):
 
 
 def test_deferred_logic_call_patterns():
-    """flx_wf_logic is deferred until the next call shows whether the material kernels follow (api.hip).  Call sequences that break the
+    """flx_wf_logic is deferred until the next call shows whether the material kernels follow (api_wavefront.hip).  Call sequences that break the
     logic -> [genRays ->] materials pattern, ask for something in between or repeat a call must give what the oracle gives for the
     same sequence, and the fused pass must run exactly when the pattern is complete."""
     d = common.mixed_material_scene()

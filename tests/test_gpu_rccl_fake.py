@@ -1,4 +1,4 @@
-"""The N > 1 branches of flx_gather / flx_gather_local (api.hip: grouped ncclSend on the peers, ncclRecv on the root) on a 1-GPU box.
+"""The N > 1 branches of flx_gather / flx_gather_local (api_group.hip: grouped ncclSend on the peers, ncclRecv on the root) on a 1-GPU box.
 
 Real RCCL refuses a communicator with duplicate devices, so with one GPU those branches never run.  tests/fake_rccl.cpp is a stand-in
 transport with the same entry points (host threads / several communicators on device 0, the receiver copies device-to-device in stream
@@ -63,7 +63,7 @@ def test_lost_message_returns_an_error_instead_of_hanging():
 
 
 def test_failure_inside_the_group_still_closes_it():
-    """ncclRecv fails between ncclGroupStart and ncclGroupEnd (api.hip: NcclGroup): the call returns the error AND the group is closed
+    """ncclRecv fails between ncclGroupStart and ncclGroupEnd (api_group.hip: NcclGroup): the call returns the error AND the group is closed
     on every rank; the peers, whose sends are never matched, fail too instead of waiting forever."""
     rc, out, _ = _run(3, 0, "threads", FAKE_RCCL_BREAK=3, FAKE_RCCL_TIMEOUT_MS=1500)
     assert any("rank 0" in e and "Recv" in e for e in out["errors"]), out

@@ -628,7 +628,7 @@ def test_prepared_regeneration_is_bit_identical_to_genrays(workload):
 
 
 def test_raw_hit_records_call_patterns():
-    """The persistent-wave extension kernel leaves RAW hit records; the host side of the boundary (api.hip: rawHits / KEEP_RAW / materialise)
+    """The persistent-wave extension kernel leaves RAW hit records; the host side of the boundary (api_wavefront.hip: rawHits / KEEP_RAW / materialise)
     has to commit them the moment anything but the reference's own loop could observe a hit record -- and only then.  Call sequences that
     look in between, change options, repeat calls or leave the logic -> genRays -> materials chain are run on the device (shipped defaults)
     and on the oracle from the same state; the WHOLE exported state, queues and counters must agree after each, and `k_materialise` /

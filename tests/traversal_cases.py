@@ -23,7 +23,7 @@ EPS_P = 1e-6                  # leaf-box margin of a hit point, relative to the 
 K_ERR = 16.0 * 2.0 ** -24     # fp32 evaluation error of one dot / cross product chain, with room to spare
 DET_CUT = float(np.float32(1e-12))              # the cut-off as the kernels compare it (an fp32 constant)
 FLT_MAX = float(np.finfo(np.float32).max)
-FAR_ORIGIN = 67108864.0                         # 2^26: flx_trace4.h WRay::setup's per-ray `far` branch, api.hip's wideClamp choice
+FAR_ORIGIN = 67108864.0                         # 2^26: flx_trace4.h WRay::setup's per-ray `far` branch, api_upload.hip's wideClamp choice
 COORD_MAX = 4.611686e18                         # 2^62: FLX_WIDE_COORD_MAX (csrc/flx_wide.h)
 BUILDERS = ("sbvh", "sah", "binned")
 
