@@ -1,0 +1,75 @@
+// api_refit.hip -- flx_update_triangles: the uploaded scene's triangles move, both traversal trees are refitted on the device over the topology
+// flx_upload_scene built (kernels: refit.hip; arithmetic and the exactness argument: flx_refit.h), and its test hook
+// flx_tree_read.  Validation runs on the device BEFORE anything is overwritten, so a refused call leaves the old scene as it was.
+#include "flx_ctx.h"
+#include "flx_wide.h"
+#include "flx_trace4.h"
+#include <cstring>
+
+namespace flxd {
+float wideClampFor(float maxAbsCoord) { return maxAbsCoord < 67108864.0f ? FLX_WIDE_DINV_MAX : FLX_WIDE_DINV_FAR; }
+}
+
+extern "C" {
+
+int flx_update_triangles(flx_ctx *c, const void *tris160, size_t ntris, int src_on_device)
+{
+    ENTER(c, CALL_OBSERVE);                               // deferred and fused launches run against the OLD scene
+    NEED(c, c->sc.bnodes, "flx_update_triangles: upload a scene first (flx_upload_scene)");
+    NEED(c, tris160, "flx_update_triangles: null triangles");
+    NEED(c, ntris == c->rf.ntris, "flx_update_triangles: the triangle count differs from the uploaded scene's (" + std::to_string(ntris) + " vs " + std::to_string(c->rf.ntris) + ")");
+    HIPCHK(c, hipSetDevice(c->device));
+    const void *src = tris160;
+    if (src_on_device) NEED(c, ((uintptr_t)tris160 & 15u) == 0, "flx_update_triangles: a device source must be 16-byte aligned");
+    else {
+        if (!c->rf.stage) {                               // first host source: the staging buffer stays with the scene allocations
+            flx_triangle *st = nullptr;
+            if (dalloc(c, c->sceneAllocs, &st, ntris)) return 1;
+            c->rf.stage = st;
+        }
+        HIPCHK(c, hipMemcpyAsync(c->rf.stage, tris160, ntris * sizeof(flx_triangle), hipMemcpyHostToDevice, c->stream));
+        src = c->rf.stage;
+    }
+    // one reduction over the source, one small blocking read (as flx_mk_adaptive_update reads its count)
+    uint32_t v[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemsetAsync(c->rf.valid, 0, 16, c->stream));
+    launch_refit_validate(c->stream, src, c->rf.ntris, c->rf.nmat, c->rf.valid);
+    LAUNCHED(c);
+    HIPCHK(c, hipMemcpyAsync(v, c->rf.valid, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float maxAbs; memcpy(&maxAbs, &v[1], 4);
+    NEED(c, !v[0], "flx_update_triangles: triangle with a NaN or infinite vertex");
+    NEED(c, maxAbs <= FLX_WIDE_COORD_MAX, "flx_update_triangles: vertex beyond +-2^62");
+    NEED(c, !v[2], "flx_update_triangles: triangle material id out of range");
+
+    // what flx_upload_scene clears: a list of active pixels and a G-buffer belong to the render of one geometry
+    c->ad.have = false;
+    c->temporal.gbTraced[0] = c->temporal.gbTraced[1] = false; c->temporal.histHave = false;
+    // the root box is the union of the vertices: the same maximum re-derives the node test's clamp
+    c->sc.wideClamp = wideClampFor(maxAbs);
+    {
+        ScopedTimer t(c, FLX_K_REFIT);
+        launch_refit(c->stream, src, c->sc, c->rf);
+    }
+    LAUNCHED(c);
+    return 0;
+}
+
+int flx_tree_read(flx_ctx *c, int which, void *out, size_t bytes, size_t *needed)
+{
+    ENTER(c, CALL_QUIET);                                 // a read-back of arrays no deferred launch writes
+    NEED(c, c->sc.bnodes, "flx_tree_read: upload a scene first (flx_upload_scene)");
+    NEED(c, which >= 0 && which <= 4 && needed, "flx_tree_read: which must be 0..4 and needed not null");
+    const void *p[5] = {c->sc.bnodes, c->sc.trirecs, c->sc.shade, c->sc.wnodes, c->sc.wleaf};
+    const size_t n[5] = {(size_t)c->wideInfo[6] * sizeof(BNode), (size_t)c->rf.nidx * sizeof(TriRec), (size_t)c->rf.ntris * sizeof(ShadeRec),
+                         (size_t)c->wideInfo[0] * sizeof(flxw::WNode), (size_t)c->wideInfo[1] * sizeof(float4)};
+    *needed = n[which];
+    if (!out) return 0;
+    NEED(c, bytes >= n[which], "flx_tree_read: buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, p[which], n[which], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+} // extern "C"

@@ -161,8 +161,8 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     flxw::WideTree wide;
     { const char *werr = nullptr; if (!flxw::build_wide(nodes, nnodes, tris, ntris, indices, nidx, wide, &werr)) { c->err = std::string("flx_upload_scene: ") + werr; return 1; } }
     uint32_t binDepth = 1;
+    std::vector<uint16_t> depth(nnodes, 0);
     {   // nodes are in DFS order with parent < child (checked above for the right child; the left child is i + 1)
-        std::vector<uint16_t> depth(nnodes, 0);
         for (size_t i = 0; i < nnodes; i++) {
             if (nodes[i].nPrims != 0) continue;
             const uint32_t l = (uint32_t)i + 1, r = nodes[i].iStartOrRight;
@@ -178,6 +178,33 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     // the 4-wide kernels page whole groups of 8 levels between their LDS ring and level-indexed spill rows (flx_trace4.h)
     if (wide.maxStack > WIDE_LDS_LEVELS - 4 && wide.maxStack + 8 > spillLevels) spillLevels = wide.maxStack + 8;
 
+    // 5. what a bottom-up pass over the same topology needs (flx_update_triangles, refit.hip): the records of each depth of both trees, where
+    // the wide leaf blocks and their triangles start
+    RefitTables rf;
+    std::vector<uint32_t> blevel, wlevel, wtriOff;
+    {
+        auto byDepth = [](size_t n, auto depthOf, auto idOf, std::vector<uint32_t> &list, std::vector<uint32_t> &start) {
+            uint32_t levels = 0;
+            for (size_t i = 0; i < n; i++) if (idOf(i) >= 0 && depthOf(i) + 1 > levels) levels = depthOf(i) + 1;
+            start.assign(levels + 1, 0);
+            for (size_t i = 0; i < n; i++) if (idOf(i) >= 0) start[depthOf(i) + 1]++;
+            for (uint32_t l = 0; l < levels; l++) start[l + 1] += start[l];
+            list.resize(start[levels]);
+            std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+            for (size_t i = 0; i < n; i++) if (idOf(i) >= 0) list[fill[depthOf(i)]++] = (uint32_t)idOf(i);
+        };
+        if (ninner == 0) { blevel.assign(1, 0); rf.blevelStart = {0, 1}; }            // the synthetic root
+        else byDepth(nnodes, [&](size_t i) { return (uint32_t)depth[i]; }, [&](size_t i) { return (int64_t)innerId[i]; }, blevel, rf.blevelStart);
+        if (!(wide.rootRef & FLX_WIDE_LEAF_BIT))
+            byDepth(wide.nodes.size(), [&](size_t i) { return wide.nodeDepth[i]; }, [&](size_t i) { return (int64_t)i; }, wlevel, rf.wlevelStart);
+        for (uint32_t off : wide.leafOffset) {
+            int cnt; memcpy(&cnt, &wide.leafdata[off].w, 4);
+            for (int k = 0; k < cnt; k++) wtriOff.push_back(off + 2 + 3 * (uint32_t)k);
+        }
+        NEED(c, ntris < 0xFFFFFFFFull && nidx + wtriOff.size() < 0xFFFFFFFFull, "flx_upload_scene: more than 2^32 triangle records");
+        rf.ntris = (uint32_t)ntris; rf.nidx = (uint32_t)nidx; rf.nmat = (uint32_t)nmat; rf.nwtri = (uint32_t)wtriOff.size(); rf.nwleaf = (uint32_t)wide.leafOffset.size();
+    }
+
     // Allocate and fill the new scene first; the previous one is released (and c->sc switched) only when everything succeeded,
     // so a failed upload leaves the context on its old scene instead of on dangling pointers.
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -187,7 +214,9 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     BNode *dB; TriRec *dT; ShadeRec *dS; flx_triangle *dTri; flx_material *dM; flx_texdesc *dD; uint8_t *dX; flxw::WNode *dW; float4 *dL;
     if (dalloc(c, fresh, &dB, bnodes.size()) || dalloc(c, fresh, &dT, trirecs.size() + 1) || dalloc(c, fresh, &dS, shade.size()) ||
         dalloc(c, fresh, &dTri, ntris) || dalloc(c, fresh, &dM, nmat) || dalloc(c, fresh, &dD, ntex) || dalloc(c, fresh, &dX, texbytes + 4) ||
-        dalloc(c, fresh, &dW, wide.nodes.size()) || dalloc(c, fresh, &dL, wide.leafdata.size() + 4))
+        dalloc(c, fresh, &dW, wide.nodes.size()) || dalloc(c, fresh, &dL, wide.leafdata.size() + 4) ||
+        dalloc(c, fresh, &rf.blevel, blevel.size()) || dalloc(c, fresh, &rf.wlevel, wlevel.size()) || dalloc(c, fresh, &rf.wtriOff, wtriOff.size()) ||
+        dalloc(c, fresh, &rf.wleafOff, wide.leafOffset.size()) || dalloc(c, fresh, &rf.wexact, 2 * wide.nodes.size()) || dalloc(c, fresh, &rf.valid, 4))
         return bail();
     uint32_t *sp1 = c->spill, *sp2 = c->spill2;
     const size_t lanes = ((size_t)c->numTasks + 255) / 256 * 256 + 1024;
@@ -202,8 +231,13 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     if (texbytes) UPCHK(hipMemcpy(dX, texdata, texbytes, hipMemcpyHostToDevice));
     UPCHK(hipMemcpy(dW, wide.nodes.data(), wide.nodes.size() * sizeof(flxw::WNode), hipMemcpyHostToDevice));
     UPCHK(hipMemcpy(dL, wide.leafdata.data(), wide.leafdata.size() * sizeof(float4), hipMemcpyHostToDevice));
+    UPCHK(hipMemcpy(rf.blevel, blevel.data(), blevel.size() * 4, hipMemcpyHostToDevice));
+    if (!wlevel.empty()) UPCHK(hipMemcpy(rf.wlevel, wlevel.data(), wlevel.size() * 4, hipMemcpyHostToDevice));
+    if (!wtriOff.empty()) UPCHK(hipMemcpy(rf.wtriOff, wtriOff.data(), wtriOff.size() * 4, hipMemcpyHostToDevice));
+    if (rf.nwleaf) UPCHK(hipMemcpy(rf.wleafOff, wide.leafOffset.data(), (size_t)rf.nwleaf * 4, hipMemcpyHostToDevice));
     freeAll(c->sceneAllocs);
     c->sceneAllocs.swap(fresh);
+    c->rf = std::move(rf);
     if (newSpill) { freeAll(c->spillAllocs); c->spillAllocs.swap(freshSpill); c->spill = sp1; c->spill2 = sp2; c->spillLevels = spillLevels; }
     c->sc.bnodes = dB; c->sc.trirecs = dT; c->sc.shade = dS; c->sc.tris = dTri; c->sc.materials = dM; c->sc.texdesc = dD; c->sc.texdata = dX;
     c->sc.rootRef = 0;
@@ -212,7 +246,7 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
         const flx_node &r0 = nodes[0];
         const float ext[6] = {r0.bmin.x, r0.bmin.y, r0.bmin.z, r0.bmax.x, r0.bmax.y, r0.bmax.z};
         float m = 0.0f; for (float v : ext) m = std::fabs(v) > m ? std::fabs(v) : m;
-        c->sc.wideClamp = m < 67108864.0f ? FLX_WIDE_DINV_MAX : FLX_WIDE_DINV_FAR;
+        c->sc.wideClamp = wideClampFor(m);
     }
     // the exactness argument of the wide any-hit traversal needs nested boxes (flx_wide.h); a tree without them (no builder of
     // ours or of the reference produces one) is traversed with the binary kernels

@@ -6,6 +6,7 @@
 //   api_image.hip      post-process, the two denoisers, temporal reprojection, the microkernel integrator and its adaptive render
 //   api_group.hip      the multi-GPU group: RCCL binding, flx_group_*, flx_gather*
 //   api_hooks.hip      measurement and test hooks
+//   api_refit.hip      flx_update_triangles (moved triangles -> refitted trees, refit.hip) and its test hook flx_tree_read
 // Everything here that is not `struct flx_ctx` (the C header's opaque type) lives in namespace flxd, like the launchers (flx_launch.h), so the
 // library's extern "C" surface is include/fluctus_hip.h and nothing else.
 #pragma once
@@ -118,6 +119,7 @@ struct flx_ctx {
     bool cursorDirty[2] = {false, false};       // block cursors of the persistent kernels (closest hit, any hit) used since they were last zeroed
 
     uint32_t wideInfo[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // flx_scene_info
+    RefitTables rf;             // flx_upload_scene -> flx_update_triangles (flx_launch.h)
     bool wideOK = false;        // the uploaded scene has a wide tree whose exactness conditions hold (nested boxes)
     uint32_t spillLevels = 0;   // levels per lane in each spill buffer (sized at upload from the tree's depth)
     int eagerBump = 0;          // A/B: bump the extension counter right after raygen / materials (option eager_bump)
@@ -215,5 +217,6 @@ extern thread_local std::string g_create_error;     // api.hip: the error of a c
 int enter(flx_ctx *c, Call call);                   // api_wavefront.hip: one step of the state machine; every entry point takes it first (ENTER)
 void flushExt(flx_ctx *c);                          // api_wavefront.hip: the lazy extension counter
 int fuseSetNow(const flx_ctx *c);                   // api_wavefront.hip: the BSDF set the fused pass inlines now (read-only options)
+float wideClampFor(float maxAbsCoord);              // api_refit.hip: the bound of |1 / dir| in the wide node test for a scene reaching this far (flx_trace4.h: WRay::setup)
 void pickSchedule(flx_ctx *c);                      // api.hip: the effective overlap / refill_shadow (options, flx_upload_scene)
 }

@@ -3,10 +3,24 @@
 // caller cannot reach is left undefined, and the library is linked with -Wl,--no-undefined: fluctus_amd/build.py).
 #pragma once
 #include "flx_device.h"
+#include <vector>
 
 namespace flx { struct ad_params; struct rp_view; struct rp_params; }     // flx_adaptive.h, flx_reproject.h: passed by reference only
 
 namespace flxd {
+// What flx_upload_scene keeps for flx_update_triangles (refit.hip): the records of each depth of both trees (deepest level launched first), where
+// the wide leaf blocks and their triangles start, the exact fp32 box of every wide node.  Device arrays live with the scene allocations.
+struct RefitTables {
+    uint32_t ntris = 0, nidx = 0, nmat = 0, nwtri = 0, nwleaf = 0;
+    uint32_t *blevel = nullptr, *wlevel = nullptr;      // BNode record / WNode numbers sorted by depth; level l = [levelStart[l], levelStart[l + 1])
+    std::vector<uint32_t> blevelStart, wlevelStart;
+    uint32_t *wtriOff = nullptr, *wleafOff = nullptr;   // per wide leaf triangle / per wide leaf block: its offset in the leaf data (16-byte units)
+    float4 *wexact = nullptr;                           // {min, max} per WNode, rewritten by every refit
+    uint32_t *valid = nullptr;                          // 4 words: the validation pass's result
+    void *stage = nullptr;                              // ntris wire triangles for a host source; allocated by the first such call
+};
+void launch_refit_validate(hipStream_t, const void *, uint32_t, uint32_t, uint32_t *);
+void launch_refit(hipStream_t, const void *, const Scene &, const RefitTables &);
 void launch_extend(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *, int);
 void launch_shadow(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *, int);
 void launch_extend4(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *);

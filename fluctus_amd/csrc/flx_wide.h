@@ -48,9 +48,50 @@ struct WideTree {
     uint32_t maxStack = 0;           // upper bound of traversal-stack entries any ray can need
     bool nested = true;              // every child box lies inside its parent's (the exactness argument needs it)
     uint32_t maxLeafCount = 0;
+    // what a bottom-up pass over the SAME topology needs (the refit, flx_refit.h); nothing above depends on them.
+    // A parent word is  WNode index | slot << 30  (FLX_WIDE_NO_PARENT: the root, or the leaf block that is the whole scene).
+    std::vector<uint32_t> nodeParent;    // per WNode
+    std::vector<uint32_t> nodeDepth;     // per WNode: 0 = the root; children are one deeper
+    std::vector<uint32_t> leafOffset;    // per leaf block, in node order: its offset in leafdata (16-byte units; the dummy leaf is not listed)
+    std::vector<uint32_t> leafParent;    // per leaf block
 };
+#define FLX_WIDE_NO_PARENT 0xFFFFFFFFu
 
 static inline float pow2f(int e) { return std::ldexp(1.0f, e); }
+
+// The grid of one wide node as a function of its (ns <= 4) child boxes alone: origin = min over the children, per-axis power-of-two scale
+// (exponent >= -108), the smallest with o + 255 s >= max over the children, and per child the planes with, in REAL arithmetic,
+// o + qlo s <= child min and o + qhi s >= child max.  Unused slots get the inverted box (lo plane 255, hi plane 0).  False when no
+// scale up to 2^121 fits.  (The device restates it in fp64 for the refit: flx_refit.h.)
+static inline bool quantise_children(const float cmin[][3], const float cmax[][3], int ns, float o[3], float s[3], uint32_t qlo[3], uint32_t qhi[3])
+{
+    for (int a = 0; a < 3; a++) {
+        qlo[a] = qhi[a] = 0;
+        float lo = cmin[0][a], hi = cmax[0][a];
+        for (int k = 1; k < ns; k++) { lo = cmin[k][a] < lo ? cmin[k][a] : lo; hi = cmax[k][a] > hi ? cmax[k][a] : hi; }
+        o[a] = lo;
+        const long double ext = (long double)hi - (long double)lo;
+        int e = ext > 0 ? (int)std::ceil(std::log2((double)(ext / 255.0L))) : -108;
+        if (e < -108) e = -108;
+        for (;; e++) {               // (re)quantise until every plane fits 8 bits
+            const long double sc = std::ldexp(1.0L, e);
+            bool ok = true; uint32_t pl = 0, ph = 0;
+            for (int k = 0; k < 4 && ok; k++) {
+                if (k >= ns) { pl |= 255u << (8 * k); continue; }              // empty slot: inverted box (lo plane 255, hi plane 0)
+                const long double dl = (long double)cmin[k][a] - lo, dh = (long double)cmax[k][a] - lo;
+                long double ql = std::floor(dl / sc), qh = std::ceil(dh / sc);
+                while (ql > 0 && ql * sc > dl) ql -= 1;                       // REAL o + ql*s <= bmin  and  o + qh*s >= bmax
+                while (qh * sc < dh) qh += 1;
+                if (ql < 0) ql = 0;
+                if (qh > 255) { ok = false; break; }
+                pl |= (uint32_t)ql << (8 * k); ph |= (uint32_t)qh << (8 * k);
+            }
+            if (ok) { qlo[a] = pl; qhi[a] = ph; s[a] = pow2f(e); break; }
+            if (e > 120) return false;
+        }
+    }
+    return true;
+}
 
 // Collapse the reference's node array (48-B nodes, left child = i + 1, right child = iStartOrRight, leaf when nPrims > 0;
 // src/bvhnode.hpp:50-59) into WNodes.  Returns false with *err set on malformed input.
@@ -60,8 +101,9 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
     auto fail = [&](const char *m) { *err = m; return false; };
     if (!nnodes) return fail("wide tree: empty node array");
     out.nodes.clear(); out.leafdata.clear(); out.nested = true; out.maxLeafCount = 0;
+    out.nodeParent.clear(); out.nodeDepth.clear(); out.leafOffset.clear(); out.leafParent.clear();
     // ---- leaf blocks, one per leaf node, in node order
-    std::vector<uint32_t> leafRef(nnodes, 0);
+    std::vector<uint32_t> leafRef(nnodes, 0), leafOrd(nnodes, 0);
     {
         size_t total = 0;
         for (size_t i = 0; i < nnodes; i++) if (nodes[i].nPrims) total += 2 + 3 * (size_t)nodes[i].nPrims;
@@ -83,6 +125,7 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
             if (!n.nPrims) continue;
             if ((size_t)n.iStartOrRight + n.nPrims > nidx) return fail("wide tree: leaf range outside the index list");
             leafRef[i] = FLX_WIDE_LEAF_BIT | (uint32_t)out.leafdata.size();
+            leafOrd[i] = (uint32_t)out.leafOffset.size(); out.leafOffset.push_back((uint32_t)out.leafdata.size());
             int cnt = n.nPrims; float fc; memcpy(&fc, &cnt, 4);
             out.leafdata.push_back({n.bmin.x, n.bmin.y, n.bmin.z, fc});
             out.leafdata.push_back({n.bmax.x, n.bmax.y, n.bmax.z, 0.0f});
@@ -100,6 +143,7 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
             }
         }
     }
+    out.leafParent.assign(out.leafOffset.size(), FLX_WIDE_NO_PARENT);
     {
         const flx_node &r0 = nodes[0];
         const float rb[6] = {r0.bmin.x, r0.bmin.y, r0.bmin.z, r0.bmax.x, r0.bmax.y, r0.bmax.z};
@@ -108,6 +152,7 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
     if (nodes[0].nPrims) {               // the whole scene is one leaf
         out.rootRef = leafRef[0]; out.maxStack = 1;
         out.nodes.resize(1); memset(out.nodes.data(), 0, sizeof(WNode));
+        out.nodeParent.assign(1, FLX_WIDE_NO_PARENT); out.nodeDepth.assign(1, 0);
         return true;
     }
     auto area = [&](uint32_t i) {
@@ -165,6 +210,7 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
     struct Item { uint32_t bin; uint32_t wide; uint32_t stackAbove; };      // binary inner node -> wide record; stack entries pending above it
     std::vector<Item> todo;
     out.nodes.resize(1);
+    out.nodeParent.assign(1, FLX_WIDE_NO_PARENT); out.nodeDepth.assign(1, 0);
     todo.push_back({0u, 0u, 0u});
     seen[0] = 1;
     out.rootRef = 0; out.maxStack = 0;
@@ -198,32 +244,8 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
                     return fail("wide tree: node box not finite or beyond +-2^62");
             }
         }
-        // grid: origin = min over the children, per-axis power-of-two scale with o + 255 s >= max over the children
-        float o[3], s[3]; uint32_t qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
-        for (int a = 0; a < 3; a++) {
-            float lo = cmin[0][a], hi = cmax[0][a];
-            for (int k = 1; k < ns; k++) { lo = cmin[k][a] < lo ? cmin[k][a] : lo; hi = cmax[k][a] > hi ? cmax[k][a] : hi; }
-            o[a] = lo;
-            const long double ext = (long double)hi - (long double)lo;
-            int e = ext > 0 ? (int)std::ceil(std::log2((double)(ext / 255.0L))) : -108;
-            if (e < -108) e = -108;
-            for (;; e++) {               // (re)quantise until every plane fits 8 bits
-                const long double sc = std::ldexp(1.0L, e);
-                bool ok = true; uint32_t pl = 0, ph = 0;
-                for (int k = 0; k < 4 && ok; k++) {
-                    if (k >= ns) { pl |= 255u << (8 * k); continue; }              // empty slot: inverted box (lo plane 255, hi plane 0)
-                    const long double dl = (long double)cmin[k][a] - lo, dh = (long double)cmax[k][a] - lo;
-                    long double ql = std::floor(dl / sc), qh = std::ceil(dh / sc);
-                    while (ql > 0 && ql * sc > dl) ql -= 1;                       // REAL o + ql*s <= bmin  and  o + qh*s >= bmax
-                    while (qh * sc < dh) qh += 1;
-                    if (ql < 0) ql = 0;
-                    if (qh > 255) { ok = false; break; }
-                    pl |= (uint32_t)ql << (8 * k); ph |= (uint32_t)qh << (8 * k);
-                }
-                if (ok) { qlo[a] = pl; qhi[a] = ph; s[a] = pow2f(e); break; }
-                if (e > 120) return fail("wide tree: box extent out of range");
-            }
-        }
+        float o[3], s[3]; uint32_t qlo[3], qhi[3];
+        if (!quantise_children(cmin, cmax, ns, o, s, qlo, qhi)) return fail("wide tree: box extent out of range");
         WNode w;
         w.ox = o[0]; w.oy = o[1]; w.oz = o[2]; w.sx = s[0]; w.sy = s[1]; w.sz = s[2];
         w.qlox = qlo[0]; w.qloy = qlo[1]; w.qloz = qlo[2]; w.qhix = qhi[0]; w.qhiy = qhi[1]; w.qhiz = qhi[2];
@@ -233,11 +255,13 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
         if (pending > out.maxStack) out.maxStack = pending;
         for (int k = 0; k < ns; k++) {
             const uint32_t c = slots[k];
-            if (nodes[c].nPrims) { refs[k] = leafRef[c]; continue; }
+            const uint32_t up = it.wide | (uint32_t)k << 30;
+            if (nodes[c].nPrims) { refs[k] = leafRef[c]; out.leafParent[leafOrd[c]] = up; continue; }
             if (seen[c]) return fail("wide tree: node reachable twice (cyclic or shared node array)");
             seen[c] = 1;
             refs[k] = (uint32_t)out.nodes.size();
             out.nodes.push_back(WNode());
+            out.nodeParent.push_back(up); out.nodeDepth.push_back(out.nodeDepth[it.wide] + 1);
         }
         for (int k = ns - 1; k >= 0; k--)                                      // left subtree processed first (pre-order-ish numbering)
             if (!nodes[slots[k]].nPrims) todo.push_back({slots[k], refs[k], pending});

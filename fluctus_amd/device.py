@@ -23,11 +23,13 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_queue_read", "flx_queue_write", "flx_set_counters", "flx_set_option", "flx_get_option", "flx_mk_reset", "flx_mk_raygen", "flx_mk_next_vertex",
            "flx_mk_sample_bsdf", "flx_mk_splat", "flx_mk_splat_preview", "flx_mk_stats_async", "flx_mk_stats_reset", "flx_write_pixels", "flx_denoise",
            "flx_denoise_variance_guided", "flx_gbuffer", "flx_history_capture", "flx_reproject", "flx_gbuffer_read", "flx_gbuffer_write",
-           "flx_mk_adaptive_update", "flx_mk_adaptive_clear", "flx_mk_active_read", "flx_mk_active_write"]
+           "flx_mk_adaptive_update", "flx_mk_adaptive_clear", "flx_mk_active_read", "flx_mk_active_write",
+           "flx_update_triangles", "flx_tree_read"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
 K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with HipContext.denoise_profile (not part of profile_get)
 K_GBUFFER, K_REPROJECT = 10, 11      # FLX_K_GBUFFER / FLX_K_REPROJECT: profile level 1, read with HipContext.kernel_profile
+K_REFIT = 12                         # FLX_K_REFIT: the kernels of update_triangles, likewise
 
 
 class DenoiseParams(C.Structure):
@@ -136,6 +138,30 @@ class HipContext:
         self._chk(self.L.flx_upload_scene(self.h, _p(d.tris), C.c_size_t(d.tris.size), _p(d.indices), C.c_size_t(d.indices.size),
                                           _p(d.nodes), C.c_size_t(d.nodes.size), _p(d.materials), C.c_size_t(d.materials.size),
                                           _p(d.texdesc), C.c_size_t(d.texdesc.size), _p(d.texdata), C.c_size_t(d.texdata.size)))
+
+    def update_triangles(self, tris, on_device=False):
+        """flx_update_triangles: move the uploaded scene's triangles and refit both traversal trees on the device (topology kept).  tris: a
+        SceneData or a wire.TRIANGLE array of the uploaded length; with on_device=True a torch tensor on this device holding the same bytes
+        (160 per triangle).  One small blocking read, then asynchronous."""
+        if on_device:
+            n, rem = divmod(tris.numel() * tris.element_size(), 160)
+            assert rem == 0 and tris.is_contiguous(), "a contiguous tensor of 160-byte wire triangles"
+            self._chk(self.L.flx_update_triangles(self.h, C.c_void_p(tris.data_ptr()), C.c_size_t(n), 1))
+            return
+        from . import wire
+        t = np.ascontiguousarray(getattr(tris, "tris", tris), wire.TRIANGLE).reshape(-1)
+        self._chk(self.L.flx_update_triangles(self.h, _p(t), C.c_size_t(t.size), 0))
+
+    TREE_ARRAYS = {0: ("bnodes", 64), 1: ("trirecs", 48), 2: ("shade", 64), 3: ("wnodes", 64), 4: ("wleaf", 16)}
+
+    def tree_read(self, which):
+        """test hook: device array `which` of the uploaded scene (0 BNode records, 1 TriRec, 2 ShadeRec, 3 WNode, 4 wide leaf data) as a
+        (records, words) uint32 array"""
+        need = C.c_size_t()
+        self._chk(self.L.flx_tree_read(self.h, int(which), None, C.c_size_t(0), C.byref(need)))
+        out = np.zeros(need.value // 4, np.uint32)
+        self._chk(self.L.flx_tree_read(self.h, int(which), _p(out), C.c_size_t(out.nbytes), C.byref(need)))
+        return out.reshape(-1, self.TREE_ARRAYS[int(which)][1] // 4)
 
     def upload_envmap(self, e):
         self._chk(self.L.flx_upload_envmap(self.h, _p(e.rgb), e.w, e.h, _p(e.prob), _p(e.alias), _p(e.pdf)))

@@ -142,6 +142,32 @@ def wide_tree_check(d):
                 slots_used={2: out[5], 3: out[6], 4: out[7]})
 
 
+def refit_bvh(d):
+    """BVH::refit: new boxes for d.nodes from d.tris over the SAME topology and index list (leaf = union of the full bounds of its triangles,
+    inner = union of its two children), in place; d.world_radius follows the new root box.  The CPU restatement of the device refit
+    (HipContext.update_triangles), bit for bit."""
+    wr = C.c_float()
+    _chk(lib().fh_bvh_refit(_p(d.nodes), C.c_uint64(d.nodes.size), _p(d.indices), C.c_uint64(d.indices.size), _p(d.tris), C.c_uint64(d.tris.size), C.byref(wr)))
+    d.world_radius = wr.value
+    return d
+
+
+def wide_quantise(cmin, cmax, device_arithmetic=False):
+    """The grid of one 4-wide node from its (ns, 3) child boxes: (o, s, qlo, qhi), three values each (qlo / qhi: byte k = child k).
+    device_arithmetic False: build_wide's quantiser (csrc/flx_wide.h); True: the refit's fp64 restatement (csrc/flx_refit.h)."""
+    cmin, cmax = np.ascontiguousarray(cmin, np.float32), np.ascontiguousarray(cmax, np.float32)
+    out = np.zeros(12, np.uint32)
+    _chk(lib().fh_wide_quantise(int(bool(device_arithmetic)), _p(cmin), _p(cmax), int(cmin.shape[0]), _p(out)))
+    return out[0:3].view(np.float32).copy(), out[3:6].view(np.float32).copy(), out[6:9].copy(), out[9:12].copy()
+
+
+def wide_tables_check(d):
+    """build_wide's parent, depth and leaf tables (what a refit schedules from) checked against the child refs; (wide nodes, leaf blocks)"""
+    out = (C.c_uint64 * 2)()
+    _chk(lib().fh_wide_tables_check(_p(d.nodes), C.c_uint64(d.nodes.size), _p(d.tris), C.c_uint64(d.tris.size), _p(d.indices), C.c_uint64(d.indices.size), out))
+    return int(out[0]), int(out[1])
+
+
 def bvh_export(d, path, mode="sbvh"):
     """Build and write the hierarchy cache file (the reference's on-disk format, host/bvh.hpp)."""
     L = lib()

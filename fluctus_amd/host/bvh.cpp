@@ -483,6 +483,31 @@ void BVH::build(const std::vector<flx_triangle> *tris, Mode mode)
     }
 }
 
+void BVH::refit(const std::vector<flx_triangle> &tris)
+{
+    const size_t n = m_nodes.size();
+    for (size_t i = n; i-- > 0;) {                           // DFS order: both children come after their parent
+        flx_node &nd = m_nodes[i];
+        Box b;
+        if (nd.nPrims) {
+            if ((size_t)nd.iStartOrRight + nd.nPrims > m_indices.size()) throw std::runtime_error("BVH::refit: leaf range outside the index list");
+            for (uint32_t k = 0; k < nd.nPrims; k++) {
+                const uint32_t ti = m_indices[nd.iStartOrRight + k];
+                if (ti >= tris.size()) throw std::runtime_error("BVH::refit: triangle index out of range");
+                const flx_triangle &t = tris[ti];
+                b.expand(&t.v0.p.x); b.expand(&t.v1.p.x); b.expand(&t.v2.p.x);
+            }
+        } else {
+            const size_t l = i + 1, r = nd.iStartOrRight;
+            if (l >= n || r >= n || r <= i) throw std::runtime_error("BVH::refit: child index out of range");
+            const float *lmn = &m_nodes[l].bmin.x, *lmx = &m_nodes[l].bmax.x, *rmn = &m_nodes[r].bmin.x, *rmx = &m_nodes[r].bmax.x;
+            for (int k = 0; k < 3; k++) { b.mn[k] = rmn[k] < lmn[k] ? rmn[k] : lmn[k]; b.mx[k] = rmx[k] > lmx[k] ? rmx[k] : lmx[k]; }   // left first, as the kernel folds
+        }
+        nd.bmin.x = b.mn[0]; nd.bmin.y = b.mn[1]; nd.bmin.z = b.mn[2];
+        nd.bmax.x = b.mx[0]; nd.bmax.y = b.mx[1]; nd.bmax.z = b.mx[2];
+    }
+}
+
 void BVH::getSceneBounds(float mn[3], float mx[3]) const
 {
     if (m_nodes.empty()) throw std::runtime_error("Cannot get scene bounds from uninitialized BVH");

@@ -47,6 +47,11 @@ public:
     void exportTo(const std::string &filename) const;
     bool importFrom(const std::string &filename);
 
+    // New boxes for the SAME topology from moved triangles (as many as the tree was built over): a leaf becomes the union of the FULL bounds of
+    // its triangles -- a leaf an SBVH spatial split had clipped becomes unclipped: correct, only looser -- an inner node the union of its two
+    // children.  Node order, parents, child links and the index list are untouched; worldRadius() follows the new root box.  The CPU
+    // restatement of the device refit (csrc/refit.hip), bit for bit.  Throws on a malformed tree or an index outside tris.
+    void refit(const std::vector<flx_triangle> &tris);
     void getSceneBounds(float mn[3], float mx[3]) const;   // reference: src/bvh.cpp:53-59
     float worldRadius() const;                             // 0.5*|max-min| (src/tracer.cpp:66-67)
 

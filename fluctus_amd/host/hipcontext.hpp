@@ -28,6 +28,7 @@ public:
     HipContext(const HipContext &) = delete;
 
     void uploadSceneData(BVH *bvh, Scene *scene);                 // src/clcontext.cpp:522-566
+    void updateTriangles(const std::vector<flx_triangle> &tris);  // flx_update_triangles: the uploaded triangles move, both trees are refitted on the device
     void createEnvMap(EnvironmentMap *map);                       // src/clcontext.cpp:467-511
     void updateParams(const RenderParams &params);                // src/clcontext.cpp:703-707
     void enqueueWfResetKernel(const RenderParams &params);        // src/clcontext.cpp:765-770

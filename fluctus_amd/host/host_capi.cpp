@@ -6,6 +6,7 @@
 #include "bvh.hpp"
 #include "envmap.hpp"
 #include "texture.hpp"
+#include "../csrc/flx_refit.h"     // the refit's fp64 quantiser compiles for the host too: the CPU tests run what the kernels run
 #include "../csrc/flx_wide.h"      // the 4-wide tree builder is plain host C++ (flx_upload_scene runs it); exposed here for CPU-side tests
 #include <cstring>
 #include <string>
@@ -211,6 +212,66 @@ static int wide_tree_check(const void *nodesv, uint64_t nnodes, const void *tris
     FH_CATCH
 }
 
+// BVH::refit over caller-owned arrays: the nodes are rewritten in place, *worldRadius follows the new root box
+int fh_bvh_refit(void *nodes, uint64_t nnodes, const uint32_t *indices, uint64_t nidx, const void *tris, uint64_t ntris, float *worldRadius)
+{
+    FH_TRY
+    BVH b;
+    b.m_nodes.assign((const flx_node *)nodes, (const flx_node *)nodes + nnodes);
+    b.m_indices.assign(indices, indices + nidx);
+    b.refit(std::vector<flx_triangle>((const flx_triangle *)tris, (const flx_triangle *)tris + ntris));
+    memcpy(nodes, b.m_nodes.data(), nnodes * sizeof(flx_node));
+    if (worldRadius) *worldRadius = b.worldRadius();
+    FH_CATCH
+}
+// the grid of one wide node from its ns child boxes (cmin / cmax: ns x 3 floats): which = 0 build_wide's quantiser (long double), 1 the refit's
+// (fp64 with error-free differences, csrc/flx_refit.h).  out12 = {o.xyz, s.xyz (float bits), qlo.xyz, qhi.xyz}
+int fh_wide_quantise(int which, const float *cmin, const float *cmax, int ns, uint32_t *out12)
+{
+    FH_TRY
+    if (ns < 1 || ns > 4) throw std::runtime_error("fh_wide_quantise: 1..4 children");
+    float o[3], s[3]; uint32_t qlo[3], qhi[3];
+    if (which == 0) {
+        float mn[4][3], mx[4][3];
+        for (int k = 0; k < ns; k++) for (int a = 0; a < 3; a++) { mn[k][a] = cmin[3 * k + a]; mx[k][a] = cmax[3 * k + a]; }
+        if (!flxw::quantise_children(mn, mx, ns, o, s, qlo, qhi)) throw std::runtime_error("wide tree: box extent out of range");
+    } else {
+        for (int a = 0; a < 3; a++) {
+            float mn[4], mx[4];
+            for (int k = 0; k < ns; k++) { mn[k] = cmin[3 * k + a]; mx[k] = cmax[3 * k + a]; }
+            flxrf::rf_quantise_axis(mn, mx, ns, &o[a], &s[a], &qlo[a], &qhi[a]);
+        }
+    }
+    memcpy(out12, o, 12); memcpy(out12 + 3, s, 12); memcpy(out12 + 6, qlo, 12); memcpy(out12 + 9, qhi, 12);
+    FH_CATCH
+}
+// build_wide's extra outputs (parent, depth and leaf tables) checked against the child refs they restate
+int fh_wide_tables_check(const void *nodesv, uint64_t nnodes, const void *trisv, uint64_t ntris, const uint32_t *indices, uint64_t nidx, uint64_t *out2)
+{
+    FH_TRY
+    flxw::WideTree w; const char *err = nullptr;
+    if (!flxw::build_wide((const flx_node *)nodesv, nnodes, (const flx_triangle *)trisv, ntris, indices, nidx, w, &err)) throw std::runtime_error(err ? err : "build_wide failed");
+    if (w.nodeParent.size() != w.nodes.size() || w.nodeDepth.size() != w.nodes.size() || w.leafParent.size() != w.leafOffset.size()) throw std::runtime_error("table sizes");
+    auto ref = [&](uint32_t up) { const flxw::WNode &p = w.nodes[up & 0x3FFFFFFFu]; const uint32_t r[4] = {p.c0, p.c1, p.c2, p.c3}; return r[up >> 30]; };
+    const bool oneLeaf = (w.rootRef & FLX_WIDE_LEAF_BIT) != 0;
+    for (size_t i = 0; i < w.nodes.size(); i++) {
+        if (i == 0) { if (w.nodeParent[0] != FLX_WIDE_NO_PARENT || w.nodeDepth[0] != 0) throw std::runtime_error("root has a parent"); continue; }
+        const uint32_t up = w.nodeParent[i];
+        if ((up & 0x3FFFFFFFu) >= i || ref(up) != i) throw std::runtime_error("node parent does not refer back");
+        if (w.nodeDepth[i] != w.nodeDepth[up & 0x3FFFFFFFu] + 1) throw std::runtime_error("node depth");
+    }
+    size_t off = 5;
+    for (size_t l = 0; l < w.leafOffset.size(); l++) {
+        if (w.leafOffset[l] != off) throw std::runtime_error("leaf offset");
+        int cnt; memcpy(&cnt, &w.leafdata[off].w, 4); off += 2 + 3 * (size_t)cnt;
+        if (oneLeaf) { if (w.leafParent[l] != FLX_WIDE_NO_PARENT) throw std::runtime_error("the only leaf has a parent"); continue; }
+        if (ref(w.leafParent[l]) != (FLX_WIDE_LEAF_BIT | w.leafOffset[l])) throw std::runtime_error("leaf parent does not refer back");
+    }
+    if (off != w.leafdata.size()) throw std::runtime_error("leaf offsets do not cover the leaf data");
+    out2[0] = w.nodes.size(); out2[1] = w.leafOffset.size();
+    FH_CATCH
+}
+
 int fh_usable_threads() { return BVH::usableThreads(); }
 int fh_bvh_destroy(void *b) { delete (BVH *)b; return 0; }
 int fh_bvh_counts(void *b, uint64_t *nnodes, uint64_t *nidx, uint32_t *metrics4)
@@ -276,6 +337,18 @@ int fh_tracer_read_accumulation(void *t, float *out, uint64_t capFloats)
 }
 int fh_tracer_destroy(void *t) { delete (Tracer *)t; return 0; }
 int fh_tracer_init(void *t, int width, int height, const char *scene) { FH_TRY ((Tracer *)t)->init(width, height, scene); FH_CATCH }
+int fh_tracer_update_geometry(void *t, const void *tris, uint64_t ntris)
+{
+    FH_TRY ((Tracer *)t)->updateGeometry(std::vector<flx_triangle>((const flx_triangle *)tris, (const flx_triangle *)tris + ntris)); FH_CATCH
+}
+int fh_tracer_get_triangles(void *t, void *out, uint64_t capTris, uint64_t *ntris)
+{
+    FH_TRY
+    auto &tr = ((Tracer *)t)->getScene()->getTriangles();
+    *ntris = tr.size();
+    if (out) { if (tr.size() > capTris) throw std::runtime_error("fh_tracer_get_triangles: buffer too small"); memcpy(out, tr.data(), tr.size() * sizeof(flx_triangle)); }
+    FH_CATCH
+}
 int fh_tracer_set_envmap(void *t, const char *hdr) { FH_TRY ((Tracer *)t)->setEnvMap(hdr); FH_CATCH }
 int fh_tracer_params(void *t, void *out240, const void *in240)
 {

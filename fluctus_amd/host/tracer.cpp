@@ -100,10 +100,25 @@ void Tracer::init(int width, int height, const std::string &sceneFile)
     initHierarchy();
     params.worldRadius = bvh->worldRadius();                 // :66-67
     for (auto *c : ranks()) c->uploadSceneData(bvh, scene.get());    // replicated: read-only, 288 GB per GPU
-    delete bvh; bvh = nullptr;                               // :72-73 data lives on the GPU now
+    // (the reference deletes the hierarchy here, :72-73; it stays for updateGeometry's refit: 48 bytes per node and the index list)
     paramsUpdatePending = true;
     iteration = 0;
     haveGbuffer = false;                                     // a new scene: no history
+}
+
+// The scene's triangles move (an animated mesh, a dragged object): same count, same materials.  The host tree and both device trees are refitted
+// over their topology instead of rebuilt; quality decays under strong deformation -- init() again rebuilds.
+void Tracer::updateGeometry(const std::vector<flx_triangle> &tris)
+{
+    if (!scene || !bvh) throw std::runtime_error("Tracer::updateGeometry: no scene (init first)");
+    if (tris.size() != scene->getTriangles().size()) throw std::runtime_error("Tracer::updateGeometry: the triangle count differs from the scene's");
+    for (auto *c : ranks()) c->updateTriangles(tris);         // refused (non-finite / out-of-range input): throws, and everything is still the old geometry's
+    bvh->refit(tris);
+    scene->getTriangles() = tris;
+    params.worldRadius = bvh->worldRadius();
+    paramsUpdatePending = true;
+    dropHistory();                                           // the G-buffer and the accumulation belong to the old geometry
+    iteration = 0;
 }
 
 void Tracer::setEnvMap(const std::string &hdrFile)

@@ -28,6 +28,9 @@ public:
 
     void init(int width, int height, const std::string &sceneFile);             // file path or "proc:<kind>:<tris>:<seed>"
     void setEnvMap(const std::string &hdrFile);                                   // Tracer::initEnvMap
+    // move the scene's triangles (same count and materials): refits the host tree and every rank's device trees (flx_update_triangles), re-derives
+    // worldRadius, drops the reprojection history and restarts the accumulation.  Topology is kept: init() rebuilds when quality matters.
+    void updateGeometry(const std::vector<flx_triangle> &tris);
     void update();                                                                // one frame (iteration 0 = 2-bounce preview x3)
     // benchmark-style iterations for `seconds` (reference: 30 s per scene) or exactly `iterations` if > 0;
     // returns the CSV text (header + one row per 0.5 s of wall time)

@@ -42,6 +42,22 @@ class Tracer:
     def init(self, width, height, scene):
         host._chk(self.L.fh_tracer_init(self.h, int(width), int(height), scene.encode()))
 
+    def triangles(self):
+        """the scene's wire triangles (a copy)"""
+        from .wire import TRIANGLE
+        n = C.c_uint64()
+        host._chk(self.L.fh_tracer_get_triangles(self.h, None, C.c_uint64(0), C.byref(n)))
+        t = np.zeros(n.value, TRIANGLE)
+        host._chk(self.L.fh_tracer_get_triangles(self.h, t.ctypes.data_as(C.c_void_p), C.c_uint64(t.size), C.byref(n)))
+        return t
+
+    def update_geometry(self, tris):
+        """Tracer::updateGeometry: the scene's triangles move (same count, same materials); the host tree and the device trees are refitted, the
+        accumulation restarts"""
+        from .wire import TRIANGLE
+        t = np.ascontiguousarray(tris, TRIANGLE).reshape(-1)
+        host._chk(self.L.fh_tracer_update_geometry(self.h, t.ctypes.data_as(C.c_void_p), C.c_uint64(t.size)))
+
     def set_envmap(self, path):
         host._chk(self.L.fh_tracer_set_envmap(self.h, path.encode()))
 

@@ -45,6 +45,23 @@ int flx_upload_scene(flx_ctx *ctx, const void *tris, size_t ntris, const uint32_
                      const void *nodes, size_t nnodes, const void *materials, size_t nmat,
                      const void *texdesc, size_t ntex, const uint8_t *texdata, size_t texbytes);
 
+/* Moving the triangles of the uploaded scene (no counterpart in the reference, which rebuilds and re-uploads, src/tracer.cpp:574-590;
+ * csrc/flx_refit.h, csrc/refit.hip): replaces every triangle by the `ntris` 160-byte wire triangles given -- positions, normals,
+ * uvs, matId -- and REFITS both traversal trees on the device: new leaf triangle records, shading records and boxes; the index list, the
+ * topology of both trees, materials, textures and the environment map stay as uploaded.  A leaf box becomes the union of the full bounds of its
+ * triangles (a leaf an SBVH spatial split had clipped becomes unclipped: correct, only looser) and traversal quality decays as the geometry
+ * leaves the shape the tree was built for: rebuild (flx_upload_scene) when that matters.  tris160: host memory, or device memory (16-byte
+ * aligned) when src_on_device != 0.  Flushes deferred and fused launches against the OLD scene first; clears the adaptive list and marks the
+ * G-buffer slots and the captured history of the temporal reprojection not traced; touches no path state, queue or counter; allocates nothing
+ * after the first call with a host source.  One small blocking read (the validation), then asynchronous on the context stream, timed under
+ * FLX_K_REFIT.  Fails -- and leaves the old scene in place, untouched -- when no scene is uploaded, ntris differs from the uploaded count, a
+ * position is not finite or beyond +-2^62 (FLX_WIDE_COORD_MAX), or a matId is outside the uploaded materials. */
+int flx_update_triangles(flx_ctx *ctx, const void *tris160, size_t ntris, int src_on_device);
+/* test hook, blocking: one device array of the uploaded scene as it is now.  which = 0 the binary tree's 64-byte inner-node records, 1 the
+ * 48-byte leaf triangle records (index-list order), 2 the 64-byte shading records, 3 the 64-byte nodes of the 4-wide tree, 4 its leaf data
+ * (16-byte units).  *needed = the array's size in bytes; out NULL only reports it, otherwise bytes must be at least that. */
+int flx_tree_read(flx_ctx *ctx, int which, void *out, size_t bytes, size_t *needed);
+
 /* CLContext::createEnvMap (src/clcontext.cpp:467-511): RGB float image + alias/prob/pdf tables. */
 int flx_upload_envmap(flx_ctx *ctx, const float *rgb, int w, int h, const float *prob, const int *alias, const float *pdf);
 
@@ -240,7 +257,8 @@ enum { FLX_K_RESET = 0, FLX_K_RAYGEN = 1, FLX_K_EXTEND = 2, FLX_K_SHADOW = 3, FL
        FLX_K_DENOISE = 9,      /* the whole of one flx_denoise or flx_denoise_variance_guided */
        FLX_K_GBUFFER = 10,     /* flx_gbuffer */
        FLX_K_REPROJECT = 11,   /* flx_reproject */
-       FLX_K_COUNT = 12 };
+       FLX_K_REFIT = 12,       /* the kernels of one flx_update_triangles */
+       FLX_K_COUNT = 13 };
 /* on: 0 off | 1 time every kernel | 2 time only the two trace kernels (+ their span), as the reference does | 3 only the
  * extension kernel | 4 the three kernels bench.py prices against a roof: extension, logic (the fused pass incl. its queue scan + scatter), shadow.
  * Each event pair costs a few microseconds of stream time, which shows at ~11 launches per 0.7 ms
