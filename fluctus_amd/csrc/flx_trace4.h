@@ -178,12 +178,17 @@ __device__ __forceinline__ bool wide_leaf_visit(const float4 *wleaf, const WRay 
 {
     const float4 *lp = wleaf + (cur & FLX_WIDE_OFF_MASK);
     const float4 b0 = lp[0], b1 = lp[1];
+    // The first triangle and the count travel with the header.  Every leaf block holds a triangle behind its header (a leaf has nPrims > 0, the
+    // dummy leaf of unused slots a degenerate one: flx_wide.h), so lp[2..4] lie inside the array.  The empty asm pins the five loads in front
+    // of the box test: left alone the compiler sinks them behind it again (header -> count -> triangle, three dependent fetches).
+    float4 a = lp[2], b = lp[3], c = lp[4];
+    float cnt = b0.w;
+    asm volatile("" : "+v"(cnt), "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(c.x), "+v"(c.y), "+v"(c.z));
     const float bmin[3] = {b0.x, b0.y, b0.z}, bmax[3] = {b1.x, b1.y, b1.z};
     float tnear;
     if (slab(bmin, bmax, r.orig, r.dinv, tbest, &tnear)) {         // the reference's own test of the leaf node's box
-        const int count = __float_as_int(b0.w);
+        const int count = __float_as_int(cnt);
         const float4 *tp = lp + 2;
-        float4 a = tp[0], b = tp[1], c = tp[2];
         for (int k = 0;;) {
             if (STATS && wstats) { const uint64_t m_ = __ballot(true); if (lane_id() == (uint32_t)__ffsll((long long)m_) - 1u) atomicAdd(&wstats[3], 1ull); }
             if (STATS) nTri++;

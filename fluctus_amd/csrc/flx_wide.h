@@ -113,6 +113,7 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
         // dummy leaf for unused child slots: a point box far outside every scene and one degenerate triangle (det == 0: never hit).
         // An unused slot's quantised box is inverted (lo plane 255, hi plane 0) and fails the node test except for rays more than
         // ~2^28 grid cells away (the conservative shift e); those land here and find nothing.
+        // (The triangle is not optional: the leaf visit fetches a block's first triangle together with its header, flx_trace4.h.)
         {
             int one = 1; float fc; memcpy(&fc, &one, 4);
             int none = -1; float fn; memcpy(&fn, &none, 4);

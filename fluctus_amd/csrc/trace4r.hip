@@ -151,7 +151,8 @@ __global__ __launch_bounds__(WIDE_BLOCK, WIDE_R_MIN_WAVES) void k_trace4r(State 
 #endif
         if (cur != FLX_RAY_DONE && (cur & FLX_WIDE_LEAF_BIT)) {
 #ifdef FLX_LAB_RSTATS
-            {   // the leaf visit of flx_trace4.h with the triangle loop counted (closest hit only)
+            {   // the leaf visit of flx_trace4.h with the triangle loop counted (closest hit only).  NOT the shipped order of loads: the first triangle
+                // is fetched after the box test here (wide_leaf_visit fetches it with the header), so the lab build counts, it does not time
                 const float4 *lp = sc.wleaf + (cur & FLX_WIDE_OFF_MASK);
                 const float4 b0 = lp[0], b1 = lp[1];
                 const float bmin[3] = {b0.x, b0.y, b0.z}, bmax[3] = {b1.x, b1.y, b1.z};
