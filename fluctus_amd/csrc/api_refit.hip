@@ -1,6 +1,7 @@
 // api_refit.hip -- flx_update_triangles: the uploaded scene's triangles move, both traversal trees are refitted on the device over the topology
 // flx_upload_scene built (kernels: refit.hip; arithmetic and the exactness argument: flx_refit.h), and its test hook
-// flx_tree_read.  Validation runs on the device BEFORE anything is overwritten, so a refused call leaves the old scene as it was.
+// flx_tree_read, and flx_tree_cost (kernels: tree_cost.hip; what is summed: flx_tree_cost.h): how far the refits have degraded
+// the trees.  Validation runs on the device BEFORE anything is overwritten, so a refused call leaves the old scene as it was.
 #include "flx_ctx.h"
 #include "flx_wide.h"
 #include "flx_trace4.h"
@@ -68,6 +69,24 @@ int flx_tree_read(flx_ctx *c, int which, void *out, size_t bytes, size_t *needed
     NEED(c, bytes >= n[which], "flx_tree_read: buffer too small");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(out, p[which], n[which], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int flx_tree_cost(flx_ctx *c, double *out8)
+{
+    ENTER(c, CALL_QUIET);                                 // reads arrays no deferred launch writes; stream-ordered behind a refit
+    NEED(c, c->sc.bnodes, "flx_tree_cost: upload a scene first (flx_upload_scene)");
+    NEED(c, out8, "flx_tree_cost: null out8");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->rf.costSlab && dalloc(c, c->sceneAllocs, &c->rf.costSlab, tree_cost_slab_doubles(c->rf))) return 1;   // stays with the scene allocations
+    const double *res;
+    {
+        ScopedTimer t(c, FLX_K_TREE_COST);
+        res = launch_tree_cost(c->stream, c->sc, c->rf, c->rf.costSlab);
+    }
+    LAUNCHED(c);
+    HIPCHK(c, hipMemcpyAsync(out8, res, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // one small blocking read, as flx_update_triangles' validation
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

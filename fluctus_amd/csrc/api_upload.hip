@@ -179,7 +179,8 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     if (wide.maxStack > WIDE_LDS_LEVELS - 4 && wide.maxStack + 8 > spillLevels) spillLevels = wide.maxStack + 8;
 
     // 5. what a bottom-up pass over the same topology needs (flx_update_triangles, refit.hip): the records of each depth of both trees, where
-    // the wide leaf blocks and their triangles start
+    // the wide leaf blocks and their triangles start.  (Level 0 of both lists holds the root ALONE, so the first listed record is the root:
+    // flx_tree_cost's kernels take A_root from list entry 0, tree_cost.hip.)
     RefitTables rf;
     std::vector<uint32_t> blevel, wlevel, wtriOff;
     {

@@ -6,7 +6,7 @@
 //   api_image.hip      post-process, the two denoisers, temporal reprojection, the microkernel integrator and its adaptive render
 //   api_group.hip      the multi-GPU group: RCCL binding, flx_group_*, flx_gather*
 //   api_hooks.hip      measurement and test hooks
-//   api_refit.hip      flx_update_triangles (moved triangles -> refitted trees, refit.hip) and its test hook flx_tree_read
+//   api_refit.hip      flx_update_triangles (moved triangles -> refitted trees, refit.hip), its test hook flx_tree_read, flx_tree_cost (tree_cost.hip)
 // Everything here that is not `struct flx_ctx` (the C header's opaque type) lives in namespace flxd, like the launchers (flx_launch.h), so the
 // library's extern "C" surface is include/fluctus_hip.h and nothing else.
 #pragma once

@@ -18,9 +18,12 @@ struct RefitTables {
     float4 *wexact = nullptr;                           // {min, max} per WNode, rewritten by every refit
     uint32_t *valid = nullptr;                          // 4 words: the validation pass's result
     void *stage = nullptr;                              // ntris wire triangles for a host source; allocated by the first such call
+    double *costSlab = nullptr;                         // flx_tree_cost's per-block partial sums and results (tree_cost.hip); allocated by the first call
 };
 void launch_refit_validate(hipStream_t, const void *, uint32_t, uint32_t, uint32_t *);
 void launch_refit(hipStream_t, const void *, const Scene &, const RefitTables &);
+size_t tree_cost_slab_doubles(const RefitTables &);
+double *launch_tree_cost(hipStream_t, const Scene &, const RefitTables &, double *);      // -> where the eight results land in the slab
 void launch_extend(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *, int);
 void launch_shadow(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *, int);
 void launch_extend4(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *);

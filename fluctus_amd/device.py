@@ -24,12 +24,22 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_mk_sample_bsdf", "flx_mk_splat", "flx_mk_splat_preview", "flx_mk_stats_async", "flx_mk_stats_reset", "flx_write_pixels", "flx_denoise",
            "flx_denoise_variance_guided", "flx_gbuffer", "flx_history_capture", "flx_reproject", "flx_gbuffer_read", "flx_gbuffer_write",
            "flx_mk_adaptive_update", "flx_mk_adaptive_clear", "flx_mk_active_read", "flx_mk_active_write",
-           "flx_update_triangles", "flx_tree_read"]
+           "flx_update_triangles", "flx_tree_read", "flx_tree_cost"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
 K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with HipContext.denoise_profile (not part of profile_get)
 K_GBUFFER, K_REPROJECT = 10, 11      # FLX_K_GBUFFER / FLX_K_REPROJECT: profile level 1, read with HipContext.kernel_profile
 K_REFIT = 12                         # FLX_K_REFIT: the kernels of update_triangles, likewise
+K_TREE_COST = 13                     # FLX_K_TREE_COST: the kernels of tree_cost, likewise
+
+
+def tree_cost_value(sums4):
+    """flxTreeCostValue (include/fluctus_hip.h): (S_node + S_tri) / A_root of four sums of tree_cost -- the two-constant surface-area heuristic
+    with both constants 1; NaN when A_root is not a positive finite number ("no decision")"""
+    a, s_node, _, s_tri = (float(v) for v in sums4)
+    if not (a > 0.0) or a == float("inf"):
+        return float("nan")
+    return (s_node + s_tri) / a
 
 
 class DenoiseParams(C.Structure):
@@ -162,6 +172,14 @@ class HipContext:
         out = np.zeros(need.value // 4, np.uint32)
         self._chk(self.L.flx_tree_read(self.h, int(which), _p(out), C.c_size_t(out.nbytes), C.byref(need)))
         return out.reshape(-1, self.TREE_ARRAYS[int(which)][1] // 4)
+
+    def tree_cost(self):
+        """flx_tree_cost (one small blocking read): the surface-area cost sums of both device trees as they stand now, after a fresh upload or
+        any number of update_triangles -- ((A_root, S_node, S_leaf, S_tri) of the binary tree, the same of the 4-wide tree), float64.
+        tree_cost_value turns four sums into one figure."""
+        out = np.zeros(8, np.float64)
+        self._chk(self.L.flx_tree_cost(self.h, _p(out)))
+        return tuple(float(v) for v in out[:4]), tuple(float(v) for v in out[4:])
 
     def upload_envmap(self, e):
         self._chk(self.L.flx_upload_envmap(self.h, _p(e.rgb), e.w, e.h, _p(e.prob), _p(e.alias), _p(e.pdf)))

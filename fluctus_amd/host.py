@@ -152,6 +152,82 @@ def refit_bvh(d):
     return d
 
 
+def _bvh_arrays(h):
+    """(nodes, indices, world radius) of a BVH handle"""
+    L = lib()
+    nn, ni = C.c_uint64(), C.c_uint64()
+    _chk(L.fh_bvh_counts(h, C.byref(nn), C.byref(ni), None))
+    nodes, idx = np.zeros(nn.value, NODE), np.zeros(ni.value, np.uint32)
+    wr = C.c_float()
+    _chk(L.fh_bvh_get(h, _p(nodes), _p(idx), C.byref(wr)))
+    return nodes, idx, wr.value
+
+
+class RebuildJob:
+    """RebuildJob (host/rebuild_job.hpp): one BVH build on a worker thread over a snapshot of the triangles; GPU-free.
+    start(tris, mode) / ready() / wait() / take() -> (nodes, indices, snapshot triangles); close() joins."""
+
+    def __init__(self):
+        self.L = lib()
+        self.h = C.c_void_p()
+        _chk(self.L.fh_rebuild_job_create(C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.fh_rebuild_job_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def start(self, tris, mode="sbvh", threads=0):
+        t = np.ascontiguousarray(getattr(tris, "tris", tris), TRIANGLE).reshape(-1)
+        _chk(self.L.fh_rebuild_job_start(self.h, _p(t), C.c_uint64(t.size), BVH_MODES[mode], int(threads)))
+        self._n = t.size
+
+    def ready(self):
+        return bool(self.L.fh_rebuild_job_ready(self.h))
+
+    def wait(self):
+        _chk(self.L.fh_rebuild_job_wait(self.h))
+
+    def hold(self, on):
+        """test hook: while held, a finished build stays unpublished (ready() is False); wait() releases it"""
+        _chk(self.L.fh_rebuild_job_hold(self.h, int(bool(on))))
+
+    def take(self):
+        b, n = C.c_void_p(), C.c_uint64()
+        snap = np.zeros(getattr(self, "_n", 0), TRIANGLE)
+        _chk(self.L.fh_rebuild_job_take(self.h, C.byref(b), _p(snap), C.c_uint64(snap.size), C.byref(n)))
+        try:
+            nodes, idx, _ = _bvh_arrays(b)
+        finally:
+            self.L.fh_bvh_destroy(b)
+        return nodes, idx, snap[:n.value]
+
+
+def tree_cost_binary(bnodes, blevel, trirecs):
+    """The binary tree's (A_root, S_node, S_leaf, S_tri) on the CPU with the very functions flx_tree_cost's kernel runs (csrc/flx_tree_cost.h):
+    bnodes / trirecs as HipContext.tree_read(0) / (1) return them, blevel the reachable record numbers, the root's first."""
+    bn, tr = np.ascontiguousarray(bnodes, np.uint32), np.ascontiguousarray(trirecs, np.uint32)
+    lst = np.ascontiguousarray(blevel, np.uint32)
+    out = np.zeros(4, np.float64)
+    _chk(lib().fh_tree_cost_binary(_p(bn), _p(lst), C.c_uint64(lst.size), _p(tr), C.c_uint64(tr.size // 12), _p(out)))
+    return tuple(float(v) for v in out)
+
+
+def tree_cost_value(sums4):
+    """flxTreeCostValue of include/fluctus_hip.h, compiled into the host library"""
+    L = lib()
+    L.fh_tree_cost_value.restype = C.c_double
+    s = np.ascontiguousarray(sums4, np.float64)
+    assert s.size == 4
+    return float(L.fh_tree_cost_value(_p(s)))
+
+
 def wide_quantise(cmin, cmax, device_arithmetic=False):
     """The grid of one 4-wide node from its (ns, 3) child boxes: (o, s, qlo, qhi), three values each (qlo / qhi: byte k = child k).
     device_arithmetic False: build_wide's quantiser (csrc/flx_wide.h); True: the refit's fp64 restatement (csrc/flx_refit.h)."""

@@ -17,7 +17,7 @@ struct HipContext::Api {
     FN(flx_mk_reset) FN(flx_mk_raygen) FN(flx_mk_next_vertex) FN(flx_mk_sample_bsdf) FN(flx_mk_splat) FN(flx_mk_splat_preview)
     FN(flx_mk_stats_async) FN(flx_mk_stats_reset) FN(flx_set_option) FN(flx_get_option) FN(flx_group_init_local) FN(flx_gather_local)
     FN(flx_denoise) FN(flx_denoise_variance_guided) FN(flx_gbuffer) FN(flx_history_capture) FN(flx_reproject)
-    FN(flx_mk_adaptive_update) FN(flx_mk_adaptive_clear) FN(flx_update_triangles)
+    FN(flx_mk_adaptive_update) FN(flx_mk_adaptive_clear) FN(flx_update_triangles) FN(flx_tree_cost) FN(flx_tree_read)
 #undef FN
 };
 
@@ -46,7 +46,7 @@ HipContext::HipContext(int device, uint32_t numTasks, const std::string &libPath
     BIND(flx_mk_reset) BIND(flx_mk_raygen) BIND(flx_mk_next_vertex) BIND(flx_mk_sample_bsdf) BIND(flx_mk_splat) BIND(flx_mk_splat_preview)
     BIND(flx_mk_stats_async) BIND(flx_mk_stats_reset) BIND(flx_set_option) BIND(flx_get_option) BIND(flx_group_init_local) BIND(flx_gather_local)
     BIND(flx_denoise) BIND(flx_denoise_variance_guided) BIND(flx_gbuffer) BIND(flx_history_capture) BIND(flx_reproject)
-    BIND(flx_mk_adaptive_update) BIND(flx_mk_adaptive_clear) BIND(flx_update_triangles)
+    BIND(flx_mk_adaptive_update) BIND(flx_mk_adaptive_clear) BIND(flx_update_triangles) BIND(flx_tree_cost) BIND(flx_tree_read)
 #undef BIND
     if (api->flx_create(device, numTasks, &ctx) != 0)
         throw std::runtime_error(std::string("HipContext: ") + api->flx_last_error(nullptr));
@@ -65,17 +65,31 @@ void HipContext::check(int rc, const char *what)
     if (rc != 0) throw std::runtime_error(std::string(what) + ": " + api->flx_last_error(ctx));
 }
 
-void HipContext::uploadSceneData(BVH *bvh, Scene *scene)
+void HipContext::uploadSceneData(BVH *bvh, Scene *scene) { uploadSceneData(bvh, scene, scene->getTriangles()); }
+void HipContext::uploadSceneData(BVH *bvh, Scene *scene, const std::vector<flx_triangle> &tris)
 {
     std::vector<flx_texdesc> descs; std::vector<uint8_t> blob;
     scene->packTextures(descs, blob);
-    auto &tris = scene->getTriangles(); auto &mats = scene->getMaterials();
+    auto &mats = scene->getMaterials();
     check(api->flx_upload_scene(ctx, tris.data(), tris.size(), bvh->m_indices.data(), bvh->m_indices.size(), bvh->m_nodes.data(), bvh->m_nodes.size(),
                                 mats.data(), mats.size(), descs.data(), descs.size(), blob.data(), blob.size()), "uploadSceneData");
 }
 void HipContext::updateTriangles(const std::vector<flx_triangle> &tris)
 {
     check(api->flx_update_triangles(ctx, tris.data(), tris.size(), 0), "updateTriangles");
+}
+std::array<double, 8> HipContext::treeCost()
+{
+    std::array<double, 8> s {};
+    check(api->flx_tree_cost(ctx, s.data()), "treeCost");
+    return s;
+}
+void HipContext::treeRead(int which, std::vector<uint8_t> &out)
+{
+    size_t need = 0;
+    check(api->flx_tree_read(ctx, which, nullptr, 0, &need), "treeRead");
+    out.resize(need);
+    check(api->flx_tree_read(ctx, which, out.data(), out.size(), &need), "treeRead");
 }
 void HipContext::createEnvMap(EnvironmentMap *m)
 {

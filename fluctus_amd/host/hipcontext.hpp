@@ -7,6 +7,7 @@
 #pragma once
 #include <string>
 #include <vector>
+#include <array>
 #include <cstdint>
 #include "../../include/fluctus_hip.h"
 #include "../csrc/flx_adaptive.h"       // FLX_AD_DEFAULT_*
@@ -28,7 +29,13 @@ public:
     HipContext(const HipContext &) = delete;
 
     void uploadSceneData(BVH *bvh, Scene *scene);                 // src/clcontext.cpp:522-566
+    // ... with the triangles the tree was built for given apart from the scene's (a rebuilt tree and its snapshot: Tracer's rebuild policy)
+    void uploadSceneData(BVH *bvh, Scene *scene, const std::vector<flx_triangle> &tris);
     void updateTriangles(const std::vector<flx_triangle> &tris);  // flx_update_triangles: the uploaded triangles move, both trees are refitted on the device
+    // flx_tree_cost: {A_root, S_node, S_leaf, S_tri} of the binary tree [0..3] and of the 4-wide tree [4..7] as they stand on the device (blocking);
+    // flxTreeCostValue (include/fluctus_hip.h) turns four of them into one figure
+    std::array<double, 8> treeCost();
+    void treeRead(int which, std::vector<uint8_t> &out);          // flx_tree_read (test hook): device array `which` of the uploaded scene
     void createEnvMap(EnvironmentMap *map);                       // src/clcontext.cpp:467-511
     void updateParams(const RenderParams &params);                // src/clcontext.cpp:703-707
     void enqueueWfResetKernel(const RenderParams &params);        // src/clcontext.cpp:765-770

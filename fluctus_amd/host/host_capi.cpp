@@ -6,7 +6,12 @@
 #include "bvh.hpp"
 #include "envmap.hpp"
 #include "texture.hpp"
+#include "rebuild_job.hpp"
+#include "../../include/fluctus_hip.h"   // flxTreeCostValue
+#include <memory>
+#include <array>
 #include "../csrc/flx_refit.h"     // the refit's fp64 quantiser compiles for the host too: the CPU tests run what the kernels run
+#include "../csrc/flx_tree_cost.h" // the cost sums of flx_tree_cost, likewise
 #include "../csrc/flx_wide.h"      // the 4-wide tree builder is plain host C++ (flx_upload_scene runs it); exposed here for CPU-side tests
 #include <cstring>
 #include <string>
@@ -272,6 +277,53 @@ int fh_wide_tables_check(const void *nodesv, uint64_t nnodes, const void *trisv,
     FH_CATCH
 }
 
+// ---- the cost sums of flx_tree_cost on the CPU (csrc/flx_tree_cost.h: the functions the kernels run) and the header's helper
+// the binary tree's four sums from a BNode array as flx_tree_read returns it, the listed records (the first is the root) and the TriRec array
+int fh_tree_cost_binary(const void *bnodes64, const uint32_t *list, uint64_t n, const void *trirecs48, uint64_t nrec, double *out4)
+{
+    FH_TRY
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (uint64_t i = 0; i < n; i++) {
+        const float *w = (const float *)bnodes64 + 16 * (size_t)list[i];
+        uint32_t refs[2], counts[2] = {0, 0};
+        memcpy(refs, w + 12, 8);
+        for (int h = 0; h < 2; h++) if (refs[h] & FLX_TC_LEAF_BIT) {
+            const uint64_t slot = refs[h] & ~FLX_TC_LEAF_BIT;
+            if (slot >= nrec) throw std::runtime_error("fh_tree_cost_binary: leaf slot outside the triangle records");
+            memcpy(&counts[h], (const float *)trirecs48 + 12 * slot + 7, 4);
+        }
+        flxtc::tc_binary_record(w, refs[0], refs[1], counts, i == 0, s);
+    }
+    memcpy(out4, s, sizeof(s));
+    FH_CATCH
+}
+double fh_tree_cost_value(const double *sums4) { return flxTreeCostValue(sums4); }
+
+// ---- RebuildJob (rebuild_job.hpp): one BVH build on a worker thread
+int fh_rebuild_job_create(void **out) { FH_TRY *out = new RebuildJob(); FH_CATCH }
+int fh_rebuild_job_destroy(void *j) { delete (RebuildJob *)j; return 0; }
+int fh_rebuild_job_start(void *j, const void *tris, uint64_t ntris, int mode, int threads)
+{
+    FH_TRY
+    ((RebuildJob *)j)->start(std::vector<flx_triangle>((const flx_triangle *)tris, (const flx_triangle *)tris + ntris),
+                             mode == 0 ? BVH::Mode::SBVH : mode == 1 ? BVH::Mode::SAH : BVH::Mode::Binned, threads);
+    FH_CATCH
+}
+int fh_rebuild_job_ready(void *j) { return ((RebuildJob *)j)->ready() ? 1 : 0; }
+int fh_rebuild_job_wait(void *j) { FH_TRY ((RebuildJob *)j)->wait(); FH_CATCH }
+int fh_rebuild_job_hold(void *j, int on) { FH_TRY ((RebuildJob *)j)->hold(on != 0); FH_CATCH }
+// hands the tree over as a BVH handle (fh_bvh_counts / fh_bvh_get / fh_bvh_destroy) and, where snapshot is not null, the snapshot's triangles
+int fh_rebuild_job_take(void *j, void **bvh, void *snapshot, uint64_t capTris, uint64_t *ntris)
+{
+    FH_TRY
+    std::unique_ptr<BVH> b; std::vector<flx_triangle> snap;
+    ((RebuildJob *)j)->take(b, snap);
+    if (ntris) *ntris = snap.size();
+    if (snapshot) { if (snap.size() > capTris) throw std::runtime_error("fh_rebuild_job_take: buffer too small"); memcpy(snapshot, snap.data(), snap.size() * sizeof(flx_triangle)); }
+    *bvh = b.release();
+    FH_CATCH
+}
+
 int fh_usable_threads() { return BVH::usableThreads(); }
 int fh_bvh_destroy(void *b) { delete (BVH *)b; return 0; }
 int fh_bvh_counts(void *b, uint64_t *nnodes, uint64_t *nidx, uint32_t *metrics4)
@@ -347,6 +399,29 @@ int fh_tracer_get_triangles(void *t, void *out, uint64_t capTris, uint64_t *ntri
     auto &tr = ((Tracer *)t)->getScene()->getTriangles();
     *ntris = tr.size();
     if (out) { if (tr.size() > capTris) throw std::runtime_error("fh_tracer_get_triangles: buffer too small"); memcpy(out, tr.data(), tr.size() * sizeof(flx_triangle)); }
+    FH_CATCH
+}
+// the rebuild policy (Tracer::setRebuildPolicy).  mode: 0 off, 1 blocking, 2 background
+int fh_tracer_set_rebuild_policy(void *t, int mode, double threshold) { FH_TRY ((Tracer *)t)->setRebuildPolicy((Tracer::RebuildMode)mode, threshold); FH_CATCH }
+int fh_tracer_rebuild_state(void *t, uint32_t *count, int *pending, double *lastRatio)
+{
+    FH_TRY
+    Tracer *tr = (Tracer *)t;
+    if (count) *count = tr->rebuildCount();
+    if (pending) *pending = tr->rebuildPending() ? 1 : 0;
+    if (lastRatio) *lastRatio = tr->lastCostRatio();
+    FH_CATCH
+}
+int fh_tracer_wait_for_rebuild(void *t) { FH_TRY ((Tracer *)t)->waitForRebuild(); FH_CATCH }
+int fh_tracer_get_option(void *t, uint32_t rank, const char *name, int *value) { FH_TRY *value = ((Tracer *)t)->getOption(rank, name ? name : ""); FH_CATCH }
+int fh_tracer_hold_rebuild(void *t, int on) { FH_TRY ((Tracer *)t)->holdRebuild(on != 0); FH_CATCH }
+int fh_tracer_tree_cost(void *t, double *out8) { FH_TRY const std::array<double, 8> s = ((Tracer *)t)->treeCost(); memcpy(out8, s.data(), sizeof(s)); FH_CATCH }
+int fh_tracer_tree_read(void *t, uint32_t rank, int which, void *out, uint64_t cap, uint64_t *needed)
+{
+    FH_TRY
+    std::vector<uint8_t> a; ((Tracer *)t)->treeRead(rank, which, a);
+    *needed = a.size();
+    if (out) { if (a.size() > cap) throw std::runtime_error("fh_tracer_tree_read: buffer too small"); memcpy(out, a.data(), a.size()); }
     FH_CATCH
 }
 int fh_tracer_set_envmap(void *t, const char *hdr) { FH_TRY ((Tracer *)t)->setEnvMap(hdr); FH_CATCH }

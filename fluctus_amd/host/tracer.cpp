@@ -22,6 +22,7 @@ Tracer::Tracer(int width, int height, int device, uint32_t numTasks)
     initAreaLight();
     scene.reset(new Scene());
     clctx.reset(new HipContext(device, numTasks));
+    lastRatio = std::nan("");
 }
 
 Tracer::Tracer(int width, int height, const std::vector<int> &devices, uint32_t numTasks) : Tracer(width, height, devices.empty() ? 0 : devices[0], numTasks)
@@ -82,6 +83,8 @@ void Tracer::initHierarchy()
 // reference: src/tracer.cpp:55-80
 void Tracer::init(int width, int height, const std::string &sceneFile)
 {
+    job.discard();                                           // a rebuild in flight belongs to the scene that goes away (joins the worker)
+    movedSinceSnapshot = false; haveBaseline = false; lastRatio = std::nan("");
     resetParams(width, height);
     scene.reset(new Scene());
     sceneName = sceneFile;
@@ -100,6 +103,7 @@ void Tracer::init(int width, int height, const std::string &sceneFile)
     initHierarchy();
     params.worldRadius = bvh->worldRadius();                 // :66-67
     for (auto *c : ranks()) c->uploadSceneData(bvh, scene.get());    // replicated: read-only, 288 GB per GPU
+    if (rebuildMode != RebuildOff) { baselineCost = wideCost(); haveBaseline = true; }
     // (the reference deletes the hierarchy here, :72-73; it stays for updateGeometry's refit: 48 bytes per node and the index list)
     paramsUpdatePending = true;
     iteration = 0;
@@ -107,18 +111,96 @@ void Tracer::init(int width, int height, const std::string &sceneFile)
 }
 
 // The scene's triangles move (an animated mesh, a dragged object): same count, same materials.  The host tree and both device trees are refitted
-// over their topology instead of rebuilt; quality decays under strong deformation -- init() again rebuilds.
-void Tracer::updateGeometry(const std::vector<flx_triangle> &tris)
+// over their topology instead of rebuilt; quality decays under strong deformation -- init() again rebuilds, or a rebuild policy
+// does when the trees' cost says so.
+void Tracer::refitAll(const std::vector<flx_triangle> &tris)
 {
-    if (!scene || !bvh) throw std::runtime_error("Tracer::updateGeometry: no scene (init first)");
-    if (tris.size() != scene->getTriangles().size()) throw std::runtime_error("Tracer::updateGeometry: the triangle count differs from the scene's");
     for (auto *c : ranks()) c->updateTriangles(tris);         // refused (non-finite / out-of-range input): throws, and everything is still the old geometry's
     bvh->refit(tris);
     scene->getTriangles() = tris;
+}
+void Tracer::geometryChanged()
+{
     params.worldRadius = bvh->worldRadius();
     paramsUpdatePending = true;
     dropHistory();                                           // the G-buffer and the accumulation belong to the old geometry
     iteration = 0;
+}
+void Tracer::updateGeometry(const std::vector<flx_triangle> &tris)
+{
+    if (!scene || !bvh) throw std::runtime_error("Tracer::updateGeometry: no scene (init first)");
+    if (tris.size() != scene->getTriangles().size()) throw std::runtime_error("Tracer::updateGeometry: the triangle count differs from the scene's");
+    if (rebuildMode == RebuildOff) {
+        refitAll(tris); geometryChanged();
+        if (job.active()) movedSinceSnapshot = true;         // a job started before the policy was switched off: whoever adopts it later must refit
+        return;
+    }
+    adoptFinishedRebuild();
+    refitAll(tris);
+    geometryChanged();
+    if (job.active()) movedSinceSnapshot = true;
+    if (!haveBaseline) { lastRatio = std::nan(""); return; }
+    lastRatio = wideCost() / baselineCost;
+    if (!(lastRatio > rebuildThreshold) || job.active()) return;     // (a NaN ratio: no decision)
+    if (rebuildMode == RebuildBackground) { job.start(tris, BVH::Mode::SBVH); movedSinceSnapshot = false; return; }
+    std::unique_ptr<BVH> fresh(new BVH());
+    fresh->build(&tris, BVH::Mode::SBVH);
+    uploadTopology(fresh.get(), tris);                       // the pose is the tree's: no refit behind it
+    delete bvh; bvh = fresh.release();
+    geometryChanged();
+    lastRatio = 1.0;
+}
+
+void Tracer::setRebuildPolicy(RebuildMode mode, double threshold)
+{
+    if (mode != RebuildOff && mode != RebuildBlocking && mode != RebuildBackground) throw std::runtime_error("setRebuildPolicy: unknown mode");
+    if (mode != RebuildOff && (!(threshold > 1.0) || !std::isfinite(threshold))) throw std::runtime_error("setRebuildPolicy: the threshold must be finite and > 1");
+    rebuildMode = mode; rebuildThreshold = threshold;
+    if (mode != RebuildOff && !haveBaseline && bvh) { baselineCost = wideCost(); haveBaseline = true; }
+}
+double Tracer::wideCost()
+{
+    const std::array<double, 8> s = clctx->treeCost();
+    return flxTreeCostValue(s.data() + 4);
+}
+void Tracer::treeRead(uint32_t rank, int which, std::vector<uint8_t> &out)
+{
+    auto R = ranks();
+    if (rank >= R.size()) throw std::runtime_error("treeRead: no such rank");
+    R[rank]->treeRead(which, out);
+}
+int Tracer::getOption(uint32_t rank, const std::string &name)
+{
+    auto R = ranks();
+    if (rank >= R.size()) throw std::runtime_error("getOption: no such rank");
+    return R[rank]->getOption(name);
+}
+void Tracer::uploadTopology(BVH *tree, const std::vector<flx_triangle> &tris)
+{
+    for (auto *c : ranks()) {
+        // flx_upload_scene re-derives "fuse_set" / "ext_order" from the triangles it is given; the first upload's choice (or the caller's override) stays
+        const int fuseSet = c->getOption("fuse_set"), extOrder = c->getOption("ext_order");
+        c->uploadSceneData(tree, scene.get(), tris);
+        c->setOption("fuse_set", fuseSet); c->setOption("ext_order", extOrder);
+    }
+    baselineCost = wideCost(); haveBaseline = true;          // before any refit: the ratio never hides the drift since the snapshot
+    rebuilds++;
+}
+bool Tracer::adoptFinishedRebuild()
+{
+    if (!job.ready()) return false;
+    std::unique_ptr<BVH> fresh; std::vector<flx_triangle> snapshot;
+    const bool moved = movedSinceSnapshot;
+    movedSinceSnapshot = false;
+    job.take(fresh, snapshot);                               // (rethrows a failed build; the old trees stay)
+    uploadTopology(fresh.get(), snapshot);
+    delete bvh; bvh = fresh.release();
+    if (moved) {
+        const std::vector<flx_triangle> current = scene->getTriangles();
+        refitAll(current);
+    }
+    geometryChanged();
+    return true;
 }
 
 void Tracer::setEnvMap(const std::string &hdrFile)
@@ -325,6 +407,7 @@ void Tracer::updateMicrokernel()
 // thread keeps them busy); each rank has its own counters and pixel cursor.
 void Tracer::update()
 {
+    if (rebuildMode != RebuildOff) adoptFinishedRebuild();
     auto R = ranks();
     bool reprojectNow = false;
     if (paramsUpdatePending) {

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "hipcontext.hpp"
+#include "rebuild_job.hpp"
 
 namespace fluctus {
 
@@ -31,6 +32,35 @@ public:
     // move the scene's triangles (same count and materials): refits the host tree and every rank's device trees (flx_update_triangles), re-derives
     // worldRadius, drops the reprojection history and restarts the accumulation.  Topology is kept: init() rebuilds when quality matters.
     void updateGeometry(const std::vector<flx_triangle> &tris);
+    // Rebuild policy, default Off: updateGeometry only refits, exactly as described above.  Otherwise every updateGeometry
+    // reads the root rank's flx_tree_cost after its refit and forms  ratio = cost of the 4-wide tree now / the same right after the last topology
+    // upload  (flxTreeCostValue: (S_node + S_tri) / A_root).  When ratio > threshold and no rebuild is in flight:
+    //   Blocking    builds the SBVH for the new triangles inside the call and uploads it (no refit behind it: the pose is the tree's);
+    //   Background  starts a worker thread (RebuildJob) on a snapshot of the new triangles and returns; frames go on with refits.  A finished
+    //               build is picked up at the start of the next updateGeometry or update(): the new topology is uploaded to every rank with its
+    //               snapshot, the cost baseline is re-read, then one refit brings it to the current triangles (skipped when none moved since
+    //               the snapshot) -- so the ratio never hides the drift since the snapshot.  worldRadius, the dropped reprojection history and the
+    //               restarted accumulation as in updateGeometry.  The upload still runs on the calling thread (build_wide and the copies).
+    // At most one job is in flight; init() discards one.  The environment map, the parameters and what the first upload chose for the options
+    // "fuse_set" / "ext_order" survive a swap.  threshold: required for Blocking / Background, > 1 and finite, else the call throws; DESIGN.md
+    // 4.10.1 tabulates what a value means.  A NaN ratio (degenerate root box) is "no decision".  Switching the policy on after geometry updates
+    // takes the trees as they stand then as the baseline: set the policy before the first updateGeometry.  Switching to Off keeps a job in
+    // flight; it is adopted, and refitted to the triangles of that moment, once a policy is on again.
+    enum RebuildMode { RebuildOff = 0, RebuildBlocking = 1, RebuildBackground = 2 };
+    void setRebuildPolicy(RebuildMode mode, double threshold);
+    RebuildMode getRebuildMode() const { return rebuildMode; }
+    uint32_t rebuildCount() const { return rebuilds; }                            // topologies uploaded by the policy since construction
+    bool rebuildPending() const { return job.active(); }                          // a job was started and its tree is not uploaded yet
+    void waitForRebuild() { job.wait(); }                                         // joins the worker; swaps nothing (the next updateGeometry / update does)
+    double lastCostRatio() const { return lastRatio; }                            // of the last updateGeometry under a policy (1 after a Blocking rebuild); NaN: none yet
+    std::array<double, 8> treeCost() { return clctx->treeCost(); }                // the root rank's flx_tree_cost
+    // ---- TEST HOOKS ONLY (tests/test_gpu_rebuild.py); a host has no use for them
+    // holdRebuild (RebuildJob::hold): while held, a finished build stays unpublished, so a test decides between which two calls a job completes;
+    // waitForRebuild and the destructor release it.  getOption / treeRead: a rank's HipContext::getOption / flx_tree_read.
+    void holdRebuild(bool on) { job.hold(on); }
+    int getOption(uint32_t rank, const std::string &name);
+    void treeRead(uint32_t rank, int which, std::vector<uint8_t> &out);
+    // ----
     void update();                                                                // one frame (iteration 0 = 2-bounce preview x3)
     // benchmark-style iterations for `seconds` (reference: 30 s per scene) or exactly `iterations` if > 0;
     // returns the CSV text (header + one row per 0.5 s of wall time)
@@ -104,6 +134,20 @@ private:
     std::vector<std::unique_ptr<HipContext>> peers;                               // ranks 1..R-1 (multi-GPU wavefront path)
     std::vector<HipContext *> ranks() { std::vector<HipContext *> r{clctx.get()}; for (auto &p : peers) r.push_back(p.get()); return r; }
     BVH *bvh = nullptr;
+    // the rebuild policy
+    RebuildMode rebuildMode = RebuildOff;
+    double rebuildThreshold = 0.0;
+    double baselineCost = 0.0;                                                    // flxTreeCostValue of the 4-wide tree right after the last topology upload; valid while haveBaseline
+    bool haveBaseline = false;
+    double lastRatio = 0.0;                                                       // (set to NaN by the constructor)
+    uint32_t rebuilds = 0;
+    bool movedSinceSnapshot = false;                                              // an updateGeometry happened since the job in flight took its snapshot
+    RebuildJob job;
+    double wideCost();                                                            // flxTreeCostValue of the root rank's 4-wide tree now
+    void uploadTopology(BVH *tree, const std::vector<flx_triangle> &tris);        // every rank; keeps the first upload's option choices; re-reads the baseline
+    void refitAll(const std::vector<flx_triangle> &tris);                         // every rank + the host tree + the scene's triangles
+    bool adoptFinishedRebuild();                                                  // a finished job -> uploaded and refitted to the current triangles
+    void geometryChanged();                                                       // worldRadius, history, accumulation: what a change of the trees resets
     uint32_t iteration = 0;
     bool paramsUpdatePending = true;
     bool useDenoiser = false;                                                     // the feature buffers (+ flx_denoise while denoiserStrength > 0)

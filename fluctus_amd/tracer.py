@@ -58,6 +58,72 @@ class Tracer:
         t = np.ascontiguousarray(tris, TRIANGLE).reshape(-1)
         host._chk(self.L.fh_tracer_update_geometry(self.h, t.ctypes.data_as(C.c_void_p), C.c_uint64(t.size)))
 
+    REBUILD_MODES = {"off": 0, "blocking": 1, "background": 2}
+
+    def set_rebuild_policy(self, mode, threshold=None):
+        """Tracer::setRebuildPolicy (DESIGN.md 4.10.1): "off" (the default: update_geometry only refits), "blocking" or "background".  Otherwise
+        every update_geometry reads the 4-wide tree's surface-area cost after its refit; when cost now / cost right after the last topology
+        upload exceeds `threshold` (required, > 1; no default -- DESIGN.md tabulates what a value means) the SBVH is rebuilt for the new
+        triangles: inside the call ("blocking"), or on a worker thread while frames go on with refits ("background"; the finished tree is
+        uploaded and refitted to the current triangles at the start of the next update_geometry or update)."""
+        if mode not in self.REBUILD_MODES:
+            raise ValueError(f"set_rebuild_policy: mode must be one of {sorted(self.REBUILD_MODES)}, not {mode!r}")
+        if threshold is None:
+            if mode != "off":
+                raise ValueError("set_rebuild_policy: a threshold is required (there is no default)")
+            threshold = 0.0
+        host._chk(self.L.fh_tracer_set_rebuild_policy(self.h, self.REBUILD_MODES[mode], C.c_double(float(threshold))))
+
+    def _rebuild_state(self):
+        n, pend, ratio = C.c_uint32(), C.c_int(), C.c_double()
+        host._chk(self.L.fh_tracer_rebuild_state(self.h, C.byref(n), C.byref(pend), C.byref(ratio)))
+        return int(n.value), bool(pend.value), float(ratio.value)
+
+    @property
+    def rebuild_count(self):
+        """topologies the rebuild policy has uploaded"""
+        return self._rebuild_state()[0]
+
+    @property
+    def rebuild_pending(self):
+        """a background rebuild was started and its tree is not uploaded yet"""
+        return self._rebuild_state()[1]
+
+    @property
+    def last_cost_ratio(self):
+        """cost ratio of the last update_geometry under a policy (1.0 after a blocking rebuild; NaN: none yet)"""
+        return self._rebuild_state()[2]
+
+    def wait_for_rebuild(self):
+        """joins the background worker; swaps nothing (the next update_geometry / update does)"""
+        host._chk(self.L.fh_tracer_wait_for_rebuild(self.h))
+
+    def get_option(self, name, rank=0):
+        """test hook: a rank's HipContext.get_option(name)"""
+        v = C.c_int()
+        host._chk(self.L.fh_tracer_get_option(self.h, C.c_uint32(rank), name.encode(), C.byref(v)))
+        return v.value
+
+    def hold_rebuild(self, on):
+        """TEST HOOK ONLY (a host has no use for it): while held, a finished background build stays unpublished (rebuild_pending, nothing
+        swapped), so a test decides between which two calls a job completes; wait_for_rebuild and close release it"""
+        host._chk(self.L.fh_tracer_hold_rebuild(self.h, int(bool(on))))
+
+    def tree_cost(self):
+        """the root rank's HipContext.tree_cost: ((A_root, S_node, S_leaf, S_tri) of the binary tree, the same of the 4-wide tree)"""
+        out = np.zeros(8, np.float64)
+        host._chk(self.L.fh_tracer_tree_cost(self.h, out.ctypes.data_as(C.c_void_p)))
+        return tuple(float(v) for v in out[:4]), tuple(float(v) for v in out[4:])
+
+    def tree_read(self, which, rank=0):
+        """test hook: a rank's HipContext.tree_read(which) as a (records, words) uint32 array"""
+        from .device import HipContext
+        need = C.c_uint64()
+        host._chk(self.L.fh_tracer_tree_read(self.h, C.c_uint32(rank), int(which), None, C.c_uint64(0), C.byref(need)))
+        out = np.zeros(need.value // 4, np.uint32)
+        host._chk(self.L.fh_tracer_tree_read(self.h, C.c_uint32(rank), int(which), out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), C.byref(need)))
+        return out.reshape(-1, HipContext.TREE_ARRAYS[int(which)][1] // 4)
+
     def set_envmap(self, path):
         host._chk(self.L.fh_tracer_set_envmap(self.h, path.encode()))
 

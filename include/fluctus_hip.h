@@ -61,6 +61,17 @@ int flx_update_triangles(flx_ctx *ctx, const void *tris160, size_t ntris, int sr
  * 48-byte leaf triangle records (index-list order), 2 the 64-byte shading records, 3 the 64-byte nodes of the 4-wide tree, 4 its leaf data
  * (16-byte units).  *needed = the array's size in bytes; out NULL only reports it, otherwise bytes must be at least that. */
 int flx_tree_read(flx_ctx *ctx, int which, void *out, size_t bytes, size_t *needed);
+/* How far refits have degraded the trees (csrc/flx_tree_cost.h, csrc/tree_cost.hip): the surface-area cost sums of both
+ * device trees as they stand now -- after a fresh upload or after any number of flx_update_triangles -- over the records the traversal kernels
+ * walk.  out8[0..3] the binary tree, out8[4..7] the 4-wide tree, each {A_root, S_node, S_leaf, S_tri}: the area of the root box; the areas of the
+ * boxes tested to enter an inner node (A_root included); the areas of the boxes tested to enter a leaf; per leaf, the area of the last box
+ * tested before its triangles (binary: the parent's half; 4-wide: the leaf header's exact box) x its triangle count.  A(box) = 2 (dx dy + dy dz +
+ * dz dx) in fp64; a 4-wide slot's box is the quantised one the node test sees.  flxTreeCostValue below turns four sums into one figure; the ratio
+ * of that figure to its value right after the upload is what a caller compares with a threshold to decide on a rebuild (Tracer::setRebuildPolicy).
+ * Reduced without floating-point atomics: the eight numbers are bit-identical from call to call and from context to context.  Changes no state
+ * a render can observe; allocates its partial-sum slab with the scene at the first call; one small blocking read, timed under FLX_K_TREE_COST.
+ * Fails when no scene is uploaded or out8 is NULL. */
+int flx_tree_cost(flx_ctx *ctx, double out8[8]);
 
 /* CLContext::createEnvMap (src/clcontext.cpp:467-511): RGB float image + alias/prob/pdf tables. */
 int flx_upload_envmap(flx_ctx *ctx, const float *rgb, int w, int h, const float *prob, const int *alias, const float *pdf);
@@ -258,7 +269,8 @@ enum { FLX_K_RESET = 0, FLX_K_RAYGEN = 1, FLX_K_EXTEND = 2, FLX_K_SHADOW = 3, FL
        FLX_K_GBUFFER = 10,     /* flx_gbuffer */
        FLX_K_REPROJECT = 11,   /* flx_reproject */
        FLX_K_REFIT = 12,       /* the kernels of one flx_update_triangles */
-       FLX_K_COUNT = 13 };
+       FLX_K_TREE_COST = 13,   /* the kernels of one flx_tree_cost */
+       FLX_K_COUNT = 14 };
 /* on: 0 off | 1 time every kernel | 2 time only the two trace kernels (+ their span), as the reference does | 3 only the
  * extension kernel | 4 the three kernels bench.py prices against a roof: extension, logic (the fused pass incl. its queue scan + scatter), shadow.
  * Each event pair costs a few microseconds of stream time, which shows at ~11 launches per 0.7 ms
@@ -362,4 +374,14 @@ int flx_get_option(flx_ctx *ctx, const char *name, int *value);
 #ifdef __cplusplus
 }
 #endif
+
+/* The two-constant surface-area heuristic with both constants 1 over four sums of flx_tree_cost: (S_node + S_tri) / A_root -- the expected
+ * number of node entries plus triangle tests of a random ray that hits the root box.  The constants are a choice, not a measurement (DESIGN.md
+ * 4.10.1).  NaN when A_root is not a positive finite number: a caller treats NaN as "no decision". */
+static inline double flxTreeCostValue(const double sums4[4])
+{
+    const double a = sums4[0];
+    if (!(a > 0.0) || a > 1.7976931348623157e308) return __builtin_nan("");
+    return (sums4[1] + sums4[3]) / a;
+}
 #endif /* FLUCTUS_HIP_H */
