@@ -399,6 +399,7 @@ int flx_get_option(flx_ctx *c, const char *name, int *value)
         {"denoiser", c->denoiser}, {"moments", c->moments}, {"eager_bump", c->eagerBump}, {"node_layout", c->nodeLayout}, {"fuse_set", c->fuseSet}, {"ext_order", c->extOrder}, {"regen", c->regenOpt}, {"regroup", c->regroup}, {"regen_prep", c->prepOpt}, {"refill_extend", c->refillExt}, {"refill_shadow", c->refillShadow}, {"shadow_split", c->shadowSplit}, {"fused_queue_mask", (int)fused_queue_mask(fuseSetNow(c))}, {"fuse_set_now", fuseSetNow(c)}};
     for (const auto &t : tab) if (strcmp(name, t.n) == 0) { *value = t.v; return 0; }
     if (strcmp(name, "phase") == 0) { *value = phaseCode(c); return 0; }
+    if (strcmp(name, "wide_far") == 0) { *value = wideFar(c); return 0; }
     c->err = std::string("flx_get_option: unknown option ") + name;
     return 1;
 }

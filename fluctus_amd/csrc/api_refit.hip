@@ -1,4 +1,4 @@
-// api_refit.hip -- flx_update_triangles: the uploaded scene's triangles move, both traversal trees are refitted on the device over the topology
+// api_refit.hip -- flx_update_triangles and flx_update_triangles_subset: the uploaded scene's triangles (or a listed subset of them) move, both traversal trees are refitted on the device over the topology
 // flx_upload_scene built (kernels: refit.hip; arithmetic and the exactness argument: flx_refit.h), and its test hook
 // flx_tree_read, and flx_tree_cost (kernels: tree_cost.hip; what is summed: flx_tree_cost.h): how far the refits have degraded
 // the trees.  Validation runs on the device BEFORE anything is overwritten, so a refused call leaves the old scene as it was.
@@ -9,6 +9,7 @@
 
 namespace flxd {
 float wideClampFor(float maxAbsCoord) { return maxAbsCoord < 67108864.0f ? FLX_WIDE_DINV_MAX : FLX_WIDE_DINV_FAR; }
+int wideFar(const flx_ctx *c) { return c->sc.wideClamp == FLX_WIDE_DINV_FAR ? 1 : 0; }
 }
 
 extern "C" {
@@ -51,6 +52,69 @@ int flx_update_triangles(flx_ctx *c, const void *tris160, size_t ntris, int src_
     {
         ScopedTimer t(c, FLX_K_REFIT);
         launch_refit(c->stream, src, c->sc, c->rf);
+    }
+    LAUNCHED(c);
+    return 0;
+}
+
+// What changes against flx_update_triangles: the source is a list; validation also checks the list and reduces the maximum |coordinate| over the
+// unmoved triangles' stored positions (the clamp is that of the WHOLE resulting set, never a running maximum); the passes rewrite only what is
+// dirty (refit.hip).  The boundary is the same, line for line.
+int flx_update_triangles_subset(flx_ctx *c, const void *tris160, const uint32_t *indices, size_t count, int src_on_device)
+{
+    ENTER(c, CALL_OBSERVE);                               // deferred and fused launches run against the OLD scene
+    NEED(c, c->sc.bnodes, "flx_update_triangles_subset: upload a scene first (flx_upload_scene)");
+    NEED(c, count <= c->rf.ntris, "flx_update_triangles_subset: more triangles listed than the uploaded scene has (" + std::to_string(count) + " vs " + std::to_string(c->rf.ntris) + ")");
+    NEED(c, count == 0 || (tris160 && indices), "flx_update_triangles_subset: null triangles or indices");
+    HIPCHK(c, hipSetDevice(c->device));
+    RefitTables &rf = c->rf;
+    const void *src = tris160; const uint32_t *idx = indices;
+    if (count) {
+        if (!rf.triStamp) {                               // first call on this scene: the stamps stay with the scene allocations, zeroed ONCE
+            const size_t nb = c->wideInfo[6], nw = c->wideInfo[0], nl = c->wideInfo[1];
+            uint32_t *st = nullptr;
+            if (dalloc(c, c->sceneAllocs, &st, (size_t)rf.ntris + nb + nw + nl)) return 1;
+            rf.stampWords = (size_t)rf.ntris + nb + nw + nl;
+            HIPCHK(c, hipMemsetAsync(st, 0, rf.stampWords * 4, c->stream));
+            rf.triStamp = st; rf.bStamp = st + rf.ntris; rf.wStamp = rf.bStamp + nb; rf.lStamp = rf.wStamp + nw;
+            rf.epoch = 0;
+        }
+        if (src_on_device) NEED(c, ((uintptr_t)tris160 & 15u) == 0 && ((uintptr_t)indices & 3u) == 0, "flx_update_triangles_subset: a device source must be 16-byte (triangles) and 4-byte (indices) aligned");
+        else {
+            if (!rf.stage) {                              // shared with flx_update_triangles: ntris wire triangles
+                flx_triangle *st = nullptr;
+                if (dalloc(c, c->sceneAllocs, &st, rf.ntris)) return 1;
+                rf.stage = st;
+            }
+            if (!rf.stageIdx && dalloc(c, c->sceneAllocs, &rf.stageIdx, rf.ntris)) return 1;
+            HIPCHK(c, hipMemcpyAsync(rf.stage, tris160, count * sizeof(flx_triangle), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(rf.stageIdx, indices, count * 4, hipMemcpyHostToDevice, c->stream));
+            src = rf.stage; idx = rf.stageIdx;
+        }
+        if (++rf.epoch == 0) {                            // the counter wrapped: stamps of 2^32 calls ago would read as this call's
+            HIPCHK(c, hipMemsetAsync(rf.triStamp, 0, rf.stampWords * 4, c->stream));
+            rf.epoch = 1;
+        }
+        uint32_t v[4] = {0, 0, 0, 0};
+        HIPCHK(c, hipMemsetAsync(rf.valid, 0, 16, c->stream));
+        launch_refit_subset_validate(c->stream, src, idx, (uint32_t)count, c->sc, rf, rf.valid);
+        LAUNCHED(c);
+        HIPCHK(c, hipMemcpyAsync(v, rf.valid, 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        float maxAbs; memcpy(&maxAbs, &v[1], 4);
+        NEED(c, !(v[3] & 2u), "flx_update_triangles_subset: triangle index out of range");
+        NEED(c, !(v[3] & 1u), "flx_update_triangles_subset: the indices are not strictly ascending");
+        NEED(c, !v[0], "flx_update_triangles_subset: triangle with a NaN or infinite vertex");
+        NEED(c, maxAbs <= FLX_WIDE_COORD_MAX, "flx_update_triangles_subset: vertex beyond +-2^62");
+        NEED(c, !v[2], "flx_update_triangles_subset: triangle material id out of range");
+        c->sc.wideClamp = wideClampFor(maxAbs);           // of the moved triangles' new and the unmoved triangles' stored positions
+    }
+    c->ad.have = false;
+    c->temporal.gbTraced[0] = c->temporal.gbTraced[1] = false; c->temporal.histHave = false;
+    if (!count) return 0;                                 // nothing listed: no byte of any tree changes
+    {
+        ScopedTimer t(c, FLX_K_REFIT);
+        launch_refit_subset(c->stream, src, idx, (uint32_t)count, c->sc, rf);
     }
     LAUNCHED(c);
     return 0;

@@ -183,6 +183,7 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     // flx_tree_cost's kernels take A_root from list entry 0, tree_cost.hip.)
     RefitTables rf;
     std::vector<uint32_t> blevel, wlevel, wtriOff;
+    std::vector<float4> wexact;
     {
         auto byDepth = [](size_t n, auto depthOf, auto idOf, std::vector<uint32_t> &list, std::vector<uint32_t> &start) {
             uint32_t levels = 0;
@@ -198,6 +199,13 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
         else byDepth(nnodes, [&](size_t i) { return (uint32_t)depth[i]; }, [&](size_t i) { return (int64_t)innerId[i]; }, blevel, rf.blevelStart);
         if (!(wide.rootRef & FLX_WIDE_LEAF_BIT))
             byDepth(wide.nodes.size(), [&](size_t i) { return wide.nodeDepth[i]; }, [&](size_t i) { return (int64_t)i; }, wlevel, rf.wlevelStart);
+        // the exact box of a wide node is its binary node's: what the parent's grid was quantised from.  A full refit rewrites all of them, a
+        // subset refit reads those of the children it does not touch (refit.hip)
+        wexact.resize(2 * wide.nodes.size());
+        for (size_t i = 0; i < wide.nodes.size(); i++) {
+            const flx_node &b = nodes[wide.nodeBin[i]];
+            wexact[2 * i] = make_float4(b.bmin.x, b.bmin.y, b.bmin.z, 0.0f); wexact[2 * i + 1] = make_float4(b.bmax.x, b.bmax.y, b.bmax.z, 0.0f);
+        }
         for (uint32_t off : wide.leafOffset) {
             int cnt; memcpy(&cnt, &wide.leafdata[off].w, 4);
             for (int k = 0; k < cnt; k++) wtriOff.push_back(off + 2 + 3 * (uint32_t)k);
@@ -235,6 +243,7 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     UPCHK(hipMemcpy(rf.blevel, blevel.data(), blevel.size() * 4, hipMemcpyHostToDevice));
     if (!wlevel.empty()) UPCHK(hipMemcpy(rf.wlevel, wlevel.data(), wlevel.size() * 4, hipMemcpyHostToDevice));
     if (!wtriOff.empty()) UPCHK(hipMemcpy(rf.wtriOff, wtriOff.data(), wtriOff.size() * 4, hipMemcpyHostToDevice));
+    UPCHK(hipMemcpy(rf.wexact, wexact.data(), wexact.size() * sizeof(float4), hipMemcpyHostToDevice));
     if (rf.nwleaf) UPCHK(hipMemcpy(rf.wleafOff, wide.leafOffset.data(), (size_t)rf.nwleaf * 4, hipMemcpyHostToDevice));
     freeAll(c->sceneAllocs);
     c->sceneAllocs.swap(fresh);

@@ -6,7 +6,7 @@
 //   api_image.hip      post-process, the two denoisers, temporal reprojection, the microkernel integrator and its adaptive render
 //   api_group.hip      the multi-GPU group: RCCL binding, flx_group_*, flx_gather*
 //   api_hooks.hip      measurement and test hooks
-//   api_refit.hip      flx_update_triangles (moved triangles -> refitted trees, refit.hip), its test hook flx_tree_read, flx_tree_cost (tree_cost.hip)
+//   api_refit.hip      flx_update_triangles / flx_update_triangles_subset (moved triangles -> refitted trees, refit.hip), their test hook flx_tree_read, flx_tree_cost (tree_cost.hip)
 // Everything here that is not `struct flx_ctx` (the C header's opaque type) lives in namespace flxd, like the launchers (flx_launch.h), so the
 // library's extern "C" surface is include/fluctus_hip.h and nothing else.
 #pragma once
@@ -218,5 +218,6 @@ int enter(flx_ctx *c, Call call);                   // api_wavefront.hip: one st
 void flushExt(flx_ctx *c);                          // api_wavefront.hip: the lazy extension counter
 int fuseSetNow(const flx_ctx *c);                   // api_wavefront.hip: the BSDF set the fused pass inlines now (read-only options)
 float wideClampFor(float maxAbsCoord);              // api_refit.hip: the bound of |1 / dir| in the wide node test for a scene reaching this far (flx_trace4.h: WRay::setup)
+int wideFar(const flx_ctx *c);                      // api_refit.hip: 1 when sc.wideClamp is the far clamp (read-only option "wide_far")
 void pickSchedule(flx_ctx *c);                      // api.hip: the effective overlap / refill_shadow (options, flx_upload_scene)
 }

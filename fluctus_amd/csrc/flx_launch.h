@@ -15,13 +15,23 @@ struct RefitTables {
     uint32_t *blevel = nullptr, *wlevel = nullptr;      // BNode record / WNode numbers sorted by depth; level l = [levelStart[l], levelStart[l + 1])
     std::vector<uint32_t> blevelStart, wlevelStart;
     uint32_t *wtriOff = nullptr, *wleafOff = nullptr;   // per wide leaf triangle / per wide leaf block: its offset in the leaf data (16-byte units)
-    float4 *wexact = nullptr;                           // {min, max} per WNode, rewritten by every refit
+    float4 *wexact = nullptr;                           // {min, max} per WNode: the box of its binary node as uploaded, rewritten by every refit
     uint32_t *valid = nullptr;                          // 4 words: the validation pass's result
     void *stage = nullptr;                              // ntris wire triangles for a host source; allocated by the first such call
     double *costSlab = nullptr;                         // flx_tree_cost's per-block partial sums and results (tree_cost.hip); allocated by the first call
+    // flx_update_triangles_subset.  A record is dirty in a call when its stamp equals that call's epoch: one stamp per triangle,
+    // per BNode record, per WNode and per wide leaf block (lStamp is indexed by the block's OFFSET in the leaf data, the very number a wide leaf
+    // reference carries: no table from reference to block number, and no dependent read of one).  ONE allocation, made and zeroed by the first
+    // call; epoch 0 is never a call's, and a wrap of the counter re-zeroes the stamps.
+    uint32_t *triStamp = nullptr, *bStamp = nullptr, *wStamp = nullptr, *lStamp = nullptr;
+    size_t stampWords = 0;
+    uint32_t epoch = 0;
+    uint32_t *stageIdx = nullptr;                       // ntris indices for a host source (the triangles go to `stage`); allocated by the first such call
 };
 void launch_refit_validate(hipStream_t, const void *, uint32_t, uint32_t, uint32_t *);
 void launch_refit(hipStream_t, const void *, const Scene &, const RefitTables &);
+void launch_refit_subset_validate(hipStream_t, const void *, const uint32_t *, uint32_t, const Scene &, const RefitTables &, uint32_t *);
+void launch_refit_subset(hipStream_t, const void *, const uint32_t *, uint32_t, const Scene &, const RefitTables &);
 size_t tree_cost_slab_doubles(const RefitTables &);
 double *launch_tree_cost(hipStream_t, const Scene &, const RefitTables &, double *);      // -> where the eight results land in the slab
 void launch_extend(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *, int);

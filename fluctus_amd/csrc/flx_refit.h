@@ -11,7 +11,11 @@
 // of its children; (2) quantised planes that contain the child's exact box in REAL arithmetic: rf_quantise_axis below; (3) an exact fp32 leaf box
 // tested with the reference's slab arithmetic: the leaf header is rewritten with the same union the binary tree's parent record gets.
 //
-// THE QUANTISER IN FP64.  The host (flx_wide.h: quantise_children) works in long double; the device has fp64.  For fp32 operands c >= lo the
+// A SUBSET (flx_update_triangles_subset) rewrites only the leaves holding a listed triangle and the records above them, with the
+// same folds and the same quantiser; a leaf none of whose triangles is listed keeps its box, clipped or not -- its triangles have not moved -- and
+// the three conditions hold as above, since every rewritten box is a union of what lies below it.
+//
+// THE QUANTISER IN FP64. The host (flx_wide.h: quantise_children) works in long double; the device has fp64.  For fp32 operands c >= lo the
 // difference d = c - lo is NOT always an fp64 number (2^61 - 2^-100 needs 161 bits), but TwoSum (Knuth; Moller 1965) gives it as an unevaluated
 // sum d = dh + dl EXACTLY, dh = fl(c - lo), |dl| <= ulp(dh) / 2: no operand overflows (|c|, |lo| <= 2^62) and every quantity is a multiple of
 // 2^-149, far above fp64's subnormals, so the six operations are error free.  With s = 2^e:

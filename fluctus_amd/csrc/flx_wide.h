@@ -52,6 +52,7 @@ struct WideTree {
     // A parent word is  WNode index | slot << 30  (FLX_WIDE_NO_PARENT: the root, or the leaf block that is the whole scene).
     std::vector<uint32_t> nodeParent;    // per WNode
     std::vector<uint32_t> nodeDepth;     // per WNode: 0 = the root; children are one deeper
+    std::vector<uint32_t> nodeBin;       // per WNode: the binary node it stands for (its box is the WNode's exact box)
     std::vector<uint32_t> leafOffset;    // per leaf block, in node order: its offset in leafdata (16-byte units; the dummy leaf is not listed)
     std::vector<uint32_t> leafParent;    // per leaf block
 };
@@ -101,7 +102,7 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
     auto fail = [&](const char *m) { *err = m; return false; };
     if (!nnodes) return fail("wide tree: empty node array");
     out.nodes.clear(); out.leafdata.clear(); out.nested = true; out.maxLeafCount = 0;
-    out.nodeParent.clear(); out.nodeDepth.clear(); out.leafOffset.clear(); out.leafParent.clear();
+    out.nodeParent.clear(); out.nodeDepth.clear(); out.nodeBin.clear(); out.leafOffset.clear(); out.leafParent.clear();
     // ---- leaf blocks, one per leaf node, in node order
     std::vector<uint32_t> leafRef(nnodes, 0), leafOrd(nnodes, 0);
     {
@@ -153,7 +154,7 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
     if (nodes[0].nPrims) {               // the whole scene is one leaf
         out.rootRef = leafRef[0]; out.maxStack = 1;
         out.nodes.resize(1); memset(out.nodes.data(), 0, sizeof(WNode));
-        out.nodeParent.assign(1, FLX_WIDE_NO_PARENT); out.nodeDepth.assign(1, 0);
+        out.nodeParent.assign(1, FLX_WIDE_NO_PARENT); out.nodeDepth.assign(1, 0); out.nodeBin.assign(1, 0);
         return true;
     }
     auto area = [&](uint32_t i) {
@@ -211,7 +212,7 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
     struct Item { uint32_t bin; uint32_t wide; uint32_t stackAbove; };      // binary inner node -> wide record; stack entries pending above it
     std::vector<Item> todo;
     out.nodes.resize(1);
-    out.nodeParent.assign(1, FLX_WIDE_NO_PARENT); out.nodeDepth.assign(1, 0);
+    out.nodeParent.assign(1, FLX_WIDE_NO_PARENT); out.nodeDepth.assign(1, 0); out.nodeBin.assign(1, 0);
     todo.push_back({0u, 0u, 0u});
     seen[0] = 1;
     out.rootRef = 0; out.maxStack = 0;
@@ -262,7 +263,7 @@ static inline bool build_wide(const flx_node *nodes, size_t nnodes, const flx_tr
             seen[c] = 1;
             refs[k] = (uint32_t)out.nodes.size();
             out.nodes.push_back(WNode());
-            out.nodeParent.push_back(up); out.nodeDepth.push_back(out.nodeDepth[it.wide] + 1);
+            out.nodeParent.push_back(up); out.nodeDepth.push_back(out.nodeDepth[it.wide] + 1); out.nodeBin.push_back(c);
         }
         for (int k = ns - 1; k >= 0; k--)                                      // left subtree processed first (pre-order-ish numbering)
             if (!nodes[slots[k]].nPrims) todo.push_back({slots[k], refs[k], pending});

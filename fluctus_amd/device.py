@@ -24,7 +24,7 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_mk_sample_bsdf", "flx_mk_splat", "flx_mk_splat_preview", "flx_mk_stats_async", "flx_mk_stats_reset", "flx_write_pixels", "flx_denoise",
            "flx_denoise_variance_guided", "flx_gbuffer", "flx_history_capture", "flx_reproject", "flx_gbuffer_read", "flx_gbuffer_write",
            "flx_mk_adaptive_update", "flx_mk_adaptive_clear", "flx_mk_active_read", "flx_mk_active_write",
-           "flx_update_triangles", "flx_tree_read", "flx_tree_cost"]
+           "flx_update_triangles", "flx_update_triangles_subset", "flx_tree_read", "flx_tree_cost"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
 K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with HipContext.denoise_profile (not part of profile_get)
@@ -161,6 +161,24 @@ class HipContext:
         from . import wire
         t = np.ascontiguousarray(getattr(tris, "tris", tris), wire.TRIANGLE).reshape(-1)
         self._chk(self.L.flx_update_triangles(self.h, _p(t), C.c_size_t(t.size), 0))
+
+    def update_triangles_subset(self, tris, indices, on_device=False):
+        """flx_update_triangles_subset: tris[k] replaces triangle indices[k] of the uploaded scene (indices strictly ascending, uint32); only the
+        records holding those triangles and the boxes above them are rewritten, everything else keeps its bytes.  tris: a wire.TRIANGLE array
+        of len(indices); with on_device=True both are torch tensors on this device (160 bytes per triangle; int32 or uint32 indices).  One
+        small blocking read, then asynchronous."""
+        if on_device:
+            n, rem = divmod(tris.numel() * tris.element_size(), 160)
+            assert rem == 0 and tris.is_contiguous() and indices.is_contiguous(), "contiguous tensors of 160-byte wire triangles and 4-byte indices"
+            assert indices.element_size() == 4 and indices.numel() == n, "one 4-byte index per triangle"
+            self._chk(self.L.flx_update_triangles_subset(self.h, C.c_void_p(tris.data_ptr() if n else None), C.c_void_p(indices.data_ptr() if n else None), C.c_size_t(n), 1))
+            return
+        from . import wire
+        t = np.ascontiguousarray(tris, wire.TRIANGLE).reshape(-1)
+        i = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        if t.size != i.size:
+            raise ValueError("update_triangles_subset: as many triangles as indices")
+        self._chk(self.L.flx_update_triangles_subset(self.h, _p(t), _p(i), C.c_size_t(i.size), 0))
 
     TREE_ARRAYS = {0: ("bnodes", 64), 1: ("trirecs", 48), 2: ("shade", 64), 3: ("wnodes", 64), 4: ("wleaf", 16)}
 

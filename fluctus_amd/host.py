@@ -152,6 +152,19 @@ def refit_bvh(d):
     return d
 
 
+def refit_bvh_subset(d, indices):
+    """BVH::refitSubset: d.tris is the full array with the moved triangles already in place, indices lists them (strictly ascending).  A leaf
+    holding a listed triangle becomes the union of the full bounds of its triangles, an inner node with a changed child the union of its two
+    children, every other node of d.nodes keeps its bytes; in place, d.world_radius follows the root box.  The CPU restatement of
+    HipContext.update_triangles_subset, bit for bit.  Raises, and leaves d.nodes untouched, on a malformed tree or list."""
+    wr = C.c_float()
+    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+    _chk(lib().fh_bvh_refit_subset(_p(d.nodes), C.c_uint64(d.nodes.size), _p(d.indices), C.c_uint64(d.indices.size), _p(d.tris), C.c_uint64(d.tris.size),
+                                   _p(idx), C.c_uint64(idx.size), C.byref(wr)))
+    d.world_radius = wr.value
+    return d
+
+
 def _bvh_arrays(h):
     """(nodes, indices, world radius) of a BVH handle"""
     L = lib()

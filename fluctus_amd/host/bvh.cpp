@@ -508,6 +508,43 @@ void BVH::refit(const std::vector<flx_triangle> &tris)
     }
 }
 
+void BVH::refitSubset(const std::vector<flx_triangle> &tris, const std::vector<uint32_t> &indices)
+{
+    std::vector<uint8_t> moved(tris.size(), 0);
+    for (size_t k = 0; k < indices.size(); k++) {
+        if (indices[k] >= tris.size()) throw std::runtime_error("BVH::refitSubset: triangle index out of range");
+        if (k && indices[k - 1] >= indices[k]) throw std::runtime_error("BVH::refitSubset: the indices are not strictly ascending");
+        moved[indices[k]] = 1;
+    }
+    const size_t n = m_nodes.size();
+    std::vector<flx_node> out(m_nodes);                      // a throw below leaves m_nodes as it was
+    std::vector<uint8_t> dirty(n, 0);
+    for (size_t i = n; i-- > 0;) {                           // DFS order: both children come after their parent
+        flx_node &nd = out[i];
+        Box b;
+        if (nd.nPrims) {
+            if ((size_t)nd.iStartOrRight + nd.nPrims > m_indices.size()) throw std::runtime_error("BVH::refitSubset: leaf range outside the index list");
+            for (uint32_t k = 0; k < nd.nPrims; k++) {
+                const uint32_t ti = m_indices[nd.iStartOrRight + k];
+                if (ti >= tris.size()) throw std::runtime_error("BVH::refitSubset: triangle index out of range");
+                dirty[i] |= moved[ti];
+                const flx_triangle &t = tris[ti];
+                b.expand(&t.v0.p.x); b.expand(&t.v1.p.x); b.expand(&t.v2.p.x);
+            }
+        } else {
+            const size_t l = i + 1, r = nd.iStartOrRight;
+            if (l >= n || r >= n || r <= i) throw std::runtime_error("BVH::refitSubset: child index out of range");
+            dirty[i] = dirty[l] | dirty[r];
+            const float *lmn = &out[l].bmin.x, *lmx = &out[l].bmax.x, *rmn = &out[r].bmin.x, *rmx = &out[r].bmax.x;
+            for (int k = 0; k < 3; k++) { b.mn[k] = rmn[k] < lmn[k] ? rmn[k] : lmn[k]; b.mx[k] = rmx[k] > lmx[k] ? rmx[k] : lmx[k]; }   // left first, as BVH::refit
+        }
+        if (!dirty[i]) continue;                             // every clean node keeps its bytes
+        nd.bmin.x = b.mn[0]; nd.bmin.y = b.mn[1]; nd.bmin.z = b.mn[2];
+        nd.bmax.x = b.mx[0]; nd.bmax.y = b.mx[1]; nd.bmax.z = b.mx[2];
+    }
+    m_nodes.swap(out);
+}
+
 void BVH::getSceneBounds(float mn[3], float mx[3]) const
 {
     if (m_nodes.empty()) throw std::runtime_error("Cannot get scene bounds from uninitialized BVH");

@@ -52,6 +52,12 @@ public:
     // children.  Node order, parents, child links and the index list are untouched; worldRadius() follows the new root box.  The CPU
     // restatement of the device refit (csrc/refit.hip), bit for bit.  Throws on a malformed tree or an index outside tris.
     void refit(const std::vector<flx_triangle> &tris);
+    // The same for a SUBSET of the triangles (csrc/refit.hip: the subset passes).  tris is the full array with the moved
+    // triangles already in place, indices lists them, strictly ascending.  A leaf holding a listed triangle becomes the union of the full bounds
+    // of its triangles, an inner node with a changed child the union of its two children; EVERY OTHER NODE KEEPS ITS BYTES, so a clipped SBVH leaf
+    // none of whose triangles moved stays clipped.  Throws -- and leaves the nodes untouched -- on a malformed tree, an index outside tris, or a
+    // list that is not strictly ascending.
+    void refitSubset(const std::vector<flx_triangle> &tris, const std::vector<uint32_t> &indices);
     void getSceneBounds(float mn[3], float mx[3]) const;   // reference: src/bvh.cpp:53-59
     float worldRadius() const;                             // 0.5*|max-min| (src/tracer.cpp:66-67)
 

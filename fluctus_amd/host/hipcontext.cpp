@@ -17,7 +17,7 @@ struct HipContext::Api {
     FN(flx_mk_reset) FN(flx_mk_raygen) FN(flx_mk_next_vertex) FN(flx_mk_sample_bsdf) FN(flx_mk_splat) FN(flx_mk_splat_preview)
     FN(flx_mk_stats_async) FN(flx_mk_stats_reset) FN(flx_set_option) FN(flx_get_option) FN(flx_group_init_local) FN(flx_gather_local)
     FN(flx_denoise) FN(flx_denoise_variance_guided) FN(flx_gbuffer) FN(flx_history_capture) FN(flx_reproject)
-    FN(flx_mk_adaptive_update) FN(flx_mk_adaptive_clear) FN(flx_update_triangles) FN(flx_tree_cost) FN(flx_tree_read)
+    FN(flx_mk_adaptive_update) FN(flx_mk_adaptive_clear) FN(flx_update_triangles) FN(flx_update_triangles_subset) FN(flx_tree_cost) FN(flx_tree_read)
 #undef FN
 };
 
@@ -46,7 +46,7 @@ HipContext::HipContext(int device, uint32_t numTasks, const std::string &libPath
     BIND(flx_mk_reset) BIND(flx_mk_raygen) BIND(flx_mk_next_vertex) BIND(flx_mk_sample_bsdf) BIND(flx_mk_splat) BIND(flx_mk_splat_preview)
     BIND(flx_mk_stats_async) BIND(flx_mk_stats_reset) BIND(flx_set_option) BIND(flx_get_option) BIND(flx_group_init_local) BIND(flx_gather_local)
     BIND(flx_denoise) BIND(flx_denoise_variance_guided) BIND(flx_gbuffer) BIND(flx_history_capture) BIND(flx_reproject)
-    BIND(flx_mk_adaptive_update) BIND(flx_mk_adaptive_clear) BIND(flx_update_triangles) BIND(flx_tree_cost) BIND(flx_tree_read)
+    BIND(flx_mk_adaptive_update) BIND(flx_mk_adaptive_clear) BIND(flx_update_triangles) BIND(flx_update_triangles_subset) BIND(flx_tree_cost) BIND(flx_tree_read)
 #undef BIND
     if (api->flx_create(device, numTasks, &ctx) != 0)
         throw std::runtime_error(std::string("HipContext: ") + api->flx_last_error(nullptr));
@@ -77,6 +77,11 @@ void HipContext::uploadSceneData(BVH *bvh, Scene *scene, const std::vector<flx_t
 void HipContext::updateTriangles(const std::vector<flx_triangle> &tris)
 {
     check(api->flx_update_triangles(ctx, tris.data(), tris.size(), 0), "updateTriangles");
+}
+void HipContext::updateTriangles(const std::vector<uint32_t> &indices, const std::vector<flx_triangle> &tris)
+{
+    if (indices.size() != tris.size()) throw std::runtime_error("updateTriangles: as many triangles as indices");
+    check(api->flx_update_triangles_subset(ctx, tris.data(), indices.data(), indices.size(), 0), "updateTriangles");
 }
 std::array<double, 8> HipContext::treeCost()
 {

@@ -32,6 +32,8 @@ public:
     // ... with the triangles the tree was built for given apart from the scene's (a rebuilt tree and its snapshot: Tracer's rebuild policy)
     void uploadSceneData(BVH *bvh, Scene *scene, const std::vector<flx_triangle> &tris);
     void updateTriangles(const std::vector<flx_triangle> &tris);  // flx_update_triangles: the uploaded triangles move, both trees are refitted on the device
+    // flx_update_triangles_subset: tris[k] replaces triangle indices[k] (strictly ascending); only the boxes above them are refitted
+    void updateTriangles(const std::vector<uint32_t> &indices, const std::vector<flx_triangle> &tris);
     // flx_tree_cost: {A_root, S_node, S_leaf, S_tri} of the binary tree [0..3] and of the 4-wide tree [4..7] as they stand on the device (blocking);
     // flxTreeCostValue (include/fluctus_hip.h) turns four of them into one figure
     std::array<double, 8> treeCost();

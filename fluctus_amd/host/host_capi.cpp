@@ -229,6 +229,19 @@ int fh_bvh_refit(void *nodes, uint64_t nnodes, const uint32_t *indices, uint64_t
     if (worldRadius) *worldRadius = b.worldRadius();
     FH_CATCH
 }
+// BVH::refitSubset likewise: tris is the full array with the moved triangles in place, moved lists them (strictly ascending)
+int fh_bvh_refit_subset(void *nodes, uint64_t nnodes, const uint32_t *indices, uint64_t nidx, const void *tris, uint64_t ntris, const uint32_t *moved, uint64_t nmoved,
+                        float *worldRadius)
+{
+    FH_TRY
+    BVH b;
+    b.m_nodes.assign((const flx_node *)nodes, (const flx_node *)nodes + nnodes);
+    b.m_indices.assign(indices, indices + nidx);
+    b.refitSubset(std::vector<flx_triangle>((const flx_triangle *)tris, (const flx_triangle *)tris + ntris), std::vector<uint32_t>(moved, moved + nmoved));
+    memcpy(nodes, b.m_nodes.data(), nnodes * sizeof(flx_node));
+    if (worldRadius) *worldRadius = b.worldRadius();
+    FH_CATCH
+}
 // the grid of one wide node from its ns child boxes (cmin / cmax: ns x 3 floats): which = 0 build_wide's quantiser (long double), 1 the refit's
 // (fp64 with error-free differences, csrc/flx_refit.h).  out12 = {o.xyz, s.xyz (float bits), qlo.xyz, qhi.xyz}
 int fh_wide_quantise(int which, const float *cmin, const float *cmax, int ns, uint32_t *out12)
@@ -392,6 +405,12 @@ int fh_tracer_init(void *t, int width, int height, const char *scene) { FH_TRY (
 int fh_tracer_update_geometry(void *t, const void *tris, uint64_t ntris)
 {
     FH_TRY ((Tracer *)t)->updateGeometry(std::vector<flx_triangle>((const flx_triangle *)tris, (const flx_triangle *)tris + ntris)); FH_CATCH
+}
+int fh_tracer_update_geometry_subset(void *t, const void *tris, const uint32_t *indices, uint64_t count)
+{
+    FH_TRY
+    ((Tracer *)t)->updateGeometry(std::vector<uint32_t>(indices, indices + count), std::vector<flx_triangle>((const flx_triangle *)tris, (const flx_triangle *)tris + count));
+    FH_CATCH
 }
 int fh_tracer_get_triangles(void *t, void *out, uint64_t capTris, uint64_t *ntris)
 {

@@ -130,18 +130,34 @@ void Tracer::updateGeometry(const std::vector<flx_triangle> &tris)
 {
     if (!scene || !bvh) throw std::runtime_error("Tracer::updateGeometry: no scene (init first)");
     if (tris.size() != scene->getTriangles().size()) throw std::runtime_error("Tracer::updateGeometry: the triangle count differs from the scene's");
-    if (rebuildMode == RebuildOff) {
-        refitAll(tris); geometryChanged();
-        if (job.active()) movedSinceSnapshot = true;         // a job started before the policy was switched off: whoever adopts it later must refit
-        return;
-    }
-    adoptFinishedRebuild();
+    if (rebuildMode != RebuildOff) adoptFinishedRebuild();
     refitAll(tris);
+    afterMove();
+}
+// ... a subset of them (flx_update_triangles_subset, BVH::refitSubset): only the boxes above the listed triangles are refitted.
+// Takes part in the rebuild policy exactly as the full overload does.
+void Tracer::updateGeometry(const std::vector<uint32_t> &indices, const std::vector<flx_triangle> &tris)
+{
+    if (!scene || !bvh) throw std::runtime_error("Tracer::updateGeometry: no scene (init first)");
+    if (indices.size() != tris.size()) throw std::runtime_error("Tracer::updateGeometry: as many triangles as indices");
+    if (rebuildMode != RebuildOff) adoptFinishedRebuild();
+    for (auto *c : ranks()) c->updateTriangles(indices, tris);   // refused (a bad index list or triangle): throws, and everything is still the old geometry's
+    std::vector<flx_triangle> all = scene->getTriangles();
+    for (size_t k = 0; k < indices.size(); k++) all[indices[k]] = tris[k];      // (the device has checked the list: ascending, in range)
+    bvh->refitSubset(all, indices);
+    scene->getTriangles().swap(all);
+    afterMove();
+}
+// what follows every move of the triangles: the resets of geometryChanged, then the rebuild policy on the trees as they stand now
+void Tracer::afterMove()
+{
     geometryChanged();
-    if (job.active()) movedSinceSnapshot = true;
+    if (job.active()) movedSinceSnapshot = true;             // (under Off too: a job started before the policy was switched off -- whoever adopts it later must refit)
+    if (rebuildMode == RebuildOff) return;
     if (!haveBaseline) { lastRatio = std::nan(""); return; }
     lastRatio = wideCost() / baselineCost;
     if (!(lastRatio > rebuildThreshold) || job.active()) return;     // (a NaN ratio: no decision)
+    const std::vector<flx_triangle> tris = scene->getTriangles();
     if (rebuildMode == RebuildBackground) { job.start(tris, BVH::Mode::SBVH); movedSinceSnapshot = false; return; }
     std::unique_ptr<BVH> fresh(new BVH());
     fresh->build(&tris, BVH::Mode::SBVH);

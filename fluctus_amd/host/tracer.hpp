@@ -32,6 +32,12 @@ public:
     // move the scene's triangles (same count and materials): refits the host tree and every rank's device trees (flx_update_triangles), re-derives
     // worldRadius, drops the reprojection history and restarts the accumulation.  Topology is kept: init() rebuilds when quality matters.
     void updateGeometry(const std::vector<flx_triangle> &tris);
+    // move a SUBSET of them (a dragged object): tris[k] replaces triangle indices[k], indices strictly ascending.  Every rank's
+    // flx_update_triangles_subset and the host tree's BVH::refitSubset recompute only the boxes above the listed triangles; every other box --
+    // a clipped SBVH leaf among them -- keeps its bytes.  Everything else, the rebuild policy included, as the full overload;
+    // a background tree that finishes later is refitted to the full current triangle set.  A refused call (bad list or triangle) throws and
+    // leaves the old geometry in place.
+    void updateGeometry(const std::vector<uint32_t> &indices, const std::vector<flx_triangle> &tris);
     // Rebuild policy, default Off: updateGeometry only refits, exactly as described above.  Otherwise every updateGeometry
     // reads the root rank's flx_tree_cost after its refit and forms  ratio = cost of the 4-wide tree now / the same right after the last topology
     // upload  (flxTreeCostValue: (S_node + S_tri) / A_root).  When ratio > threshold and no rebuild is in flight:
@@ -147,6 +153,7 @@ private:
     void uploadTopology(BVH *tree, const std::vector<flx_triangle> &tris);        // every rank; keeps the first upload's option choices; re-reads the baseline
     void refitAll(const std::vector<flx_triangle> &tris);                         // every rank + the host tree + the scene's triangles
     bool adoptFinishedRebuild();                                                  // a finished job -> uploaded and refitted to the current triangles
+    void afterMove();                                                             // geometryChanged + the rebuild policy: what both updateGeometry overloads end on
     void geometryChanged();                                                       // worldRadius, history, accumulation: what a change of the trees resets
     uint32_t iteration = 0;
     bool paramsUpdatePending = true;

@@ -58,6 +58,17 @@ class Tracer:
         t = np.ascontiguousarray(tris, TRIANGLE).reshape(-1)
         host._chk(self.L.fh_tracer_update_geometry(self.h, t.ctypes.data_as(C.c_void_p), C.c_uint64(t.size)))
 
+    def update_geometry_subset(self, tris, indices):
+        """Tracer::updateGeometry(indices, tris): tris[k] replaces triangle indices[k] of the scene (indices strictly ascending); only the boxes
+        above the listed triangles are refitted, on the host tree and on every rank.  The rebuild policy applies as in
+        update_geometry."""
+        from .wire import TRIANGLE
+        t = np.ascontiguousarray(tris, TRIANGLE).reshape(-1)
+        i = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        if t.size != i.size:
+            raise ValueError("update_geometry_subset: as many triangles as indices")
+        host._chk(self.L.fh_tracer_update_geometry_subset(self.h, t.ctypes.data_as(C.c_void_p), i.ctypes.data_as(C.c_void_p), C.c_uint64(i.size)))
+
     REBUILD_MODES = {"off": 0, "blocking": 1, "background": 2}
 
     def set_rebuild_policy(self, mode, threshold=None):

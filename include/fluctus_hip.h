@@ -57,6 +57,20 @@ int flx_upload_scene(flx_ctx *ctx, const void *tris, size_t ntris, const uint32_
  * FLX_K_REFIT.  Fails -- and leaves the old scene in place, untouched -- when no scene is uploaded, ntris differs from the uploaded count, a
  * position is not finite or beyond +-2^62 (FLX_WIDE_COORD_MAX), or a matId is outside the uploaded materials. */
 int flx_update_triangles(flx_ctx *ctx, const void *tris160, size_t ntris, int src_on_device);
+/* Moving a SUBSET of the triangles (a dragged object; csrc/refit.hip): tris160[k] is the new 160-byte wire triangle for
+ * triangle indices[k] of the uploaded scene -- positions, normals, uvs and matId may all change.  Only what hangs above the listed triangles is
+ * rewritten: their shading records and leaf triangle records, the headers of the wide leaf blocks holding one (the union of the full bounds of the
+ * block's triangles), the halves of the binary records and the 4-wide nodes with such a leaf below them.  EVERY OTHER BYTE of the five
+ * flx_tree_read arrays stays as it was, so an SBVH leaf a spatial split had clipped stays clipped unless one of its own triangles is listed (moving
+ * a triangle back does not re-clip its leaves).  Both pointers are host memory, or device memory when src_on_device != 0 (tris160 16-byte,
+ * indices 4-byte aligned).  The boundary is flx_update_triangles': flushes deferred and fused launches against the OLD scene first, clears the
+ * adaptive list, marks the G-buffer slots and the captured history not traced, touches no path state, queue or counter, keeps what the upload
+ * chose; allocates only at its first call (stamps; the staging buffers at the first call with a host source), one small blocking read (the
+ * validation), timed under FLX_K_REFIT.  The wide node test's clamp is re-derived from the whole resulting triangle set (read-only option
+ * "wide_far").  Fails -- before anything is overwritten -- when no scene is uploaded, count exceeds the uploaded triangle count, a pointer is
+ * null while count > 0, indices is not strictly ascending (duplicates included) or holds an index outside the uploaded triangles, a position
+ * is not finite or beyond +-2^62, or a matId is outside the uploaded materials.  count == 0 is accepted and changes no byte of any tree. */
+int flx_update_triangles_subset(flx_ctx *ctx, const void *tris160, const uint32_t *indices, size_t count, int src_on_device);
 /* test hook, blocking: one device array of the uploaded scene as it is now.  which = 0 the binary tree's 64-byte inner-node records, 1 the
  * 48-byte leaf triangle records (index-list order), 2 the 64-byte shading records, 3 the 64-byte nodes of the 4-wide tree, 4 its leaf data
  * (16-byte units).  *needed = the array's size in bytes; out NULL only reports it, otherwise bytes must be at least that. */
@@ -368,7 +382,9 @@ int flx_set_option(flx_ctx *ctx, const char *name, int value);
  * deferred / fused / early-started kernels (flx_ctx.h: enum Phase) -- bits 0-2: 0 idle, 1 flx_wf_logic deferred, 2 flx_wf_logic +
  * flx_wf_raygen deferred, 3 only genRays / material kernels enqueued since logic, 4 ... and the extension kernel last, 5 the extension
  * kernel last with the chain since logic broken; bit 3: the hit records of the last extension launch are still RAW; bit 4: the material
- * queues are known to be empty.  Never changes any state (tests/test_gpu_fuzz.py reports its coverage with it). */
+ * queues are known to be empty; or of the read-only "wide_far": 1 when the 4-wide node test clamps 1 / dir for a scene reaching beyond +-2^26
+ * (FLX_WIDE_DINV_FAR), else 0 -- re-derived by every upload, flx_update_triangles and flx_update_triangles_subset from the triangles the
+ * scene then holds.  Never changes any state (tests/test_gpu_fuzz.py reports its coverage with it). */
 int flx_get_option(flx_ctx *ctx, const char *name, int *value);
 
 #ifdef __cplusplus
