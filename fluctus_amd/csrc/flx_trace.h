@@ -18,10 +18,9 @@ namespace flxd {
 #ifndef SHADOW_MIN_WAVES
 #define SHADOW_MIN_WAVES 1         // 8 fits (64 VGPRs, no spill) but measures the same as 7
 #endif
-#define MAX_LEVELS 64
 
 struct TraceAux {
-    uint32_t *spill;        // (MAX_LEVELS - LDS_LEVELS) x totalThreads
+    uint32_t *spill;        // spillLevels rows x totalThreads columns: sized at upload from the depth of both trees (api_upload.hip; up to 4095 levels)
     uint32_t totalThreads;
     unsigned long long *stats;   // 16 counters (7 ray-level, [8..11] / [12..15] wave-level trips of k_extend / k_shadow) or nullptr
 };

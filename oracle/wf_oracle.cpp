@@ -181,10 +181,20 @@ void intersectLight(Hit *hit, f3 orig, f3 dir, const flx_render_params &p)
 /* bvh.cl (stack variant, :232-374)                                          */
 /* ------------------------------------------------------------------------ */
 
+/* The reference keeps `uint stack[64]` in private memory, which a ray that pushes at more than 63 levels overruns.  The device kernels spill
+   instead and accept trees of up to 4095 levels (csrc/api_upload.hip), so the oracle keeps the reference's visit order on a stack sized by
+   the tree: at most one entry per node (tests/stack_cases.py: a 100-card deck drives 100 entries). */
+static uint32_t *traversal_stack(const Ctx &c)
+{
+    thread_local std::vector<uint32_t> s;
+    if (s.size() < c.nodes.size() + 2) s.resize(c.nodes.size() + 2);
+    return s.data();
+}
+
 /* reference: bvh.cl:234-310 */
 void bvh_intersect(Ctx &c, f3 orig, f3 dir, Hit *hit, uint64_t *nInner, uint64_t *nTri)
 {
-    uint32_t stack[64];
+    uint32_t *stack = traversal_stack(c);
     int sp = 0;
     stack[0] = 0;
     while (sp >= 0) {
@@ -231,7 +241,7 @@ void bvh_intersect(Ctx &c, f3 orig, f3 dir, Hit *hit, uint64_t *nInner, uint64_t
 /* reference: bvh.cl:312-373 */
 bool bvh_occluded(Ctx &c, f3 orig, f3 dir, float maxDist, uint64_t *nInner, uint64_t *nTri)
 {
-    uint32_t stack[64];
+    uint32_t *stack = traversal_stack(c);
     int sp = 0;
     stack[0] = 0;
     while (sp >= 0) {

@@ -461,8 +461,11 @@ def test_c_abi_error_paths():
 
 
 def test_single_leaf_scene_and_deep_stack_spill():
-    """Edge cases of the traversal layout: a scene that is ONE leaf (synthetic root) and a degenerate, very deep tree
-    (median-split chain) that overflows the LDS stack levels into the global spill area."""
+    """Edge cases of the traversal layout: a scene that is ONE leaf (synthetic root) and a degenerate, very deep tree (a right-leaning
+    chain of 40 levels): the upload sizes the spill area for it and the kernels walk it.  The name is historical: no ray of this test
+    spills -- the tree's depth bounds the stack, it does not fill it; over these six iterations no binary stack holds more than 1 entry
+    (tests/test_stack_spill.py::test_the_older_chain_tests_never_leave_the_lds_levels states the figures).  The spill paths are tested on
+    rays that provably reach them in tests/test_gpu_stack_spill.py."""
     from fluctus_amd.device import HipContext
     from oracle.binding import OracleContext
     # (a) two triangles -> the whole BVH is a single leaf node

@@ -109,8 +109,11 @@ def test_wide_closest_hit_lockstep_small(scene):
 
 
 def test_wide_tree_edge_cases_single_leaf_and_deep_chain():
-    """(a) a scene that is ONE leaf (the wide root is a leaf reference), (b) a 40-level right-leaning chain (every wide node = three
-    leaves + one inner child; the traversal stack outgrows its LDS levels and spills)."""
+    """(a) a scene that is ONE leaf (the wide root is a leaf reference), (b) a 60-level right-leaning chain (every wide node = three
+    leaves + one inner child; the stack BOUND outgrows the LDS levels, so the upload sizes the spill area for paging).  No ray of this test
+    pages: camera rays over the flat grid pierce a handful of leaf boxes, the deepest 4-wide stack over the six iterations holds 3 entries
+    for closest hit and none for any hit (tests/test_stack_spill.py::test_the_older_chain_tests_never_leave_the_lds_levels).  Paging is
+    tested on rays that provably reach it in tests/test_gpu_stack_spill.py."""
     d = common.small_mesh_scene(n=6)
     d.tris = d.tris[:2].copy()
     d.materials = np.array([common.default_material()], wire.MATERIAL)
@@ -146,8 +149,8 @@ def test_wide_tree_edge_cases_single_leaf_and_deep_chain():
     d.nodes, d.indices = nodes, np.arange(nt, dtype=np.uint32)
     d.world_radius = float(0.5 * np.linalg.norm(sufmax[0] - sufmin[0]))
     p = common.scene_params(d, 32, 32, maxBounces=3)
-    # the stack pages through the spill area in the persistent closest-hit kernel (default), in the thread-per-ray any-hit kernel (default)
-    # and, second pass, in the persistent any-hit kernel and the thread-per-ray closest-hit kernel
+    # the deep chain under the persistent closest-hit kernel and the thread-per-ray any-hit kernel (default) and, second pass, under the
+    # persistent any-hit kernel and the thread-per-ray closest-hit kernel (none of these rays pages: see the docstring)
     for refill_ext, refill_sh in ((None, None), (0, 16 | (32 << 8))):
         g, o = _ctxs(d, p, 1024)
         if refill_ext is not None:

@@ -4,6 +4,8 @@
 //                        wide_leaf_visit: same float operations in the same order, fmaf for the plane evaluations) over caller-supplied
 //                        rays, on the tree build_wide() (csrc/flx_wide.h -- the product's own builder) makes: hits per ray + visit counts.
 //                        tests/test_wide_emulation.py compares its hits with the oracle's binary traversal (src/bvh.cl:234-373).
+//   fh_wide_visits_stack the same emulation, reporting per ray what flx_trace4.h's WStack would have done for its push / pop sequence: peak
+//                        entry count, page-outs, page-ins, and where a node-visit budget (k_shadow4s) ran out.  tests/stack_cases.py.
 //   fh_wide_optimise     the archived topology optimiser (scripts/experiments/flx_wide_opt.h) for scripts/exp_tree_opt.py.
 #include <stdint.h>
 #include <stdexcept>
@@ -72,17 +74,29 @@ static inline bool sim_mt(f3 orig, f3 dir, f3 p0, f3 p1, f3 p2, float *tret)
 // rays: n x 8 floats {orig.xyz, tmax, dir.xyz, unused}.  mode 0 closest hit (nearest child first), 1 any hit / last hit slot first, 2 any hit / farthest
 // first.  out8 = {node visits, leaf visits, leaf boxes passed, triangle tests, rays with a hit, deepest stack, wide nodes, sum of hit triangle
 // indices + 1 (a checksum to compare two trees over the same leaves: closest hit must agree up to ties)}.
+int fh_wide_visits_stack(const void *nodesv, uint64_t nnodes, const void *trisv, uint64_t ntris, const uint32_t *indices, uint64_t nidx,
+                         const float *rays, uint64_t nrays, int mode, int ldsLevels, int budget, double *out8, int32_t *hitTri, uint32_t *nodeVisitsPerRay,
+                         int32_t *stackPerRay);
 int fh_wide_visits_ex(const void *nodesv, uint64_t nnodes, const void *trisv, uint64_t ntris, const uint32_t *indices, uint64_t nidx,
-                      const float *rays, uint64_t nrays, int mode, double *out8, int32_t *hitTri, uint32_t *nodeVisitsPerRay);
+                      const float *rays, uint64_t nrays, int mode, double *out8, int32_t *hitTri, uint32_t *nodeVisitsPerRay)
+{
+    return fh_wide_visits_stack(nodesv, nnodes, trisv, ntris, indices, nidx, rays, nrays, mode, 16, 0, out8, hitTri, nodeVisitsPerRay, nullptr);
+}
 int fh_wide_visits(const void *nodesv, uint64_t nnodes, const void *trisv, uint64_t ntris, const uint32_t *indices, uint64_t nidx,
                    const float *rays, uint64_t nrays, int mode, double *out8)
 {
     return fh_wide_visits_ex(nodesv, nnodes, trisv, ntris, indices, nidx, rays, nrays, mode, out8, nullptr, nullptr);
 }
-// + per ray: the triangle found (closest hit: the winner; any hit: the first occluder met, in the device's visit order; -1 none) and the
-// number of wide-node visits
-int fh_wide_visits_ex(const void *nodesv, uint64_t nnodes, const void *trisv, uint64_t ntris, const uint32_t *indices, uint64_t nidx,
-                      const float *rays, uint64_t nrays, int mode, double *out8, int32_t *hitTri, uint32_t *nodeVisitsPerRay)
+// fh_wide_visits_ex: + per ray the triangle found (closest hit: the winner; any hit: the first occluder met, in the device's visit order; -1
+// none) and the number of wide-node visits.
+// fh_wide_visits_stack: + stackPerRay, 6 ints per ray, the bookkeeping of flx_trace4.h's WStack replayed on the ray's own push / pop sequence
+// with a ring of ldsLevels entries (WIDE_LDS_LEVELS): {peak entry count, page-outs, page-ins, sp and base where the node-visit budget ran out
+// in front of an inner node (traverse4_any_budget; -1, -1: it never did, or budget 0), 0}.  The ring rule: WStack::reserve pages the oldest 8
+// levels out when more than ldsLevels - 4 entries sit above `base` before a node visit; WStack::pop pages 8 back in when it finds
+// sp == base > 0.
+int fh_wide_visits_stack(const void *nodesv, uint64_t nnodes, const void *trisv, uint64_t ntris, const uint32_t *indices, uint64_t nidx,
+                         const float *rays, uint64_t nrays, int mode, int ldsLevels, int budget, double *out8, int32_t *hitTri, uint32_t *nodeVisitsPerRay,
+                         int32_t *stackPerRay)
 {
     FH_TRY
     flxw::WideTree w; const char *err = nullptr;
@@ -113,8 +127,16 @@ int fh_wide_visits_ex(const void *nodesv, uint64_t nnodes, const void *trisv, ui
         std::vector<uint32_t> stack; stack.reserve(64);
         uint32_t cur = w.rootRef;
         bool done = false;
+        int base = 0, peak = 0, pageOuts = 0, pageIns = 0, left = budget, suspSp = -1, suspBase = -1;
+        auto pop = [&]() -> uint32_t {                 // WStack::pop
+            if ((int)stack.size() == base) { if (base == 0) return 0xFFFFFFFFu; base -= 8; pageIns++; }
+            const uint32_t v = stack.back(); stack.pop_back(); return v;
+        };
         while (!done) {
             while (!(cur & FLX_WIDE_LEAF_BIT)) {
+                if (budget > 0 && left == 0 && suspSp < 0) { suspSp = (int)stack.size(); suspBase = base; }      // out of budget in front of an inner node
+                left -= left > 0 ? 1 : 0;
+                if ((int)stack.size() - base > ldsLevels - 4) { pageOuts++; base += 8; }                          // WStack::reserve
                 nv += 1;
                 const flxw::WNode &n = w.nodes[cur];
                 const float o[3] = {n.ox, n.oy, n.oz}, sc[3] = {n.sx, n.sy, n.sz};
@@ -139,18 +161,18 @@ int fh_wide_visits_ex(const void *nodesv, uint64_t nnodes, const void *trisv, ui
                 if (mode == 1) {                       // any hit: last hit slot first, earlier ones pushed in slot order
                     int last = -1; for (int c = 0; c < 4; c++) if (hit[c]) last = c;
                     for (int c = 0; c < last; c++) if (hit[c]) stack.push_back(refs[c]);
+                    if ((int)stack.size() > peak) peak = (int)stack.size();
                     if (last >= 0) cur = refs[last];
-                    else if (stack.empty()) { cur = 0xFFFFFFFFu; }
-                    else { cur = stack.back(); stack.pop_back(); }
+                    else cur = pop();
                 } else {
                     const float INF = __builtin_huge_valf();
                     float k[4]; for (int c = 0; c < 4; c++) k[c] = hit[c] ? (mode == 2 ? -key[c] : key[c]) : INF;
                     auto ce = [&](int a, int b) { if (k[b] < k[a]) { std::swap(k[a], k[b]); std::swap(refs[a], refs[b]); } };
                     ce(0, 1); ce(2, 3); ce(0, 2); ce(1, 3); ce(1, 2);
                     for (int c = 3; c >= 1; c--) if (k[c] < INF) stack.push_back(refs[c]);
+                    if ((int)stack.size() > peak) peak = (int)stack.size();
                     if (k[0] < INF) cur = refs[0];
-                    else if (stack.empty()) { cur = 0xFFFFFFFFu; }
-                    else { cur = stack.back(); stack.pop_back(); }
+                    else cur = pop();
                 }
                 if ((int)stack.size() > deepest) deepest = (int)stack.size();
             }
@@ -172,9 +194,10 @@ int fh_wide_visits_ex(const void *nodesv, uint64_t nnodes, const void *trisv, ui
                 }
             }
             if (done) break;
-            if (stack.empty()) break;
-            cur = stack.back(); stack.pop_back();
+            cur = pop();
+            if (cur == 0xFFFFFFFFu) break;
         }
+        if (stackPerRay) { int32_t *sp = stackPerRay + ri * 6; sp[0] = peak; sp[1] = pageOuts; sp[2] = pageIns; sp[3] = suspSp; sp[4] = suspBase; sp[5] = 0; }
         if (tribest >= 0) { hits += 1; chk += (double)(tribest + 1); }
         if (hitTri) hitTri[ri] = tribest;
         if (nodeVisitsPerRay) nodeVisitsPerRay[ri] = (uint32_t)(nv - nv0);
