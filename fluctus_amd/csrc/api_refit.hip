@@ -12,112 +12,97 @@ float wideClampFor(float maxAbsCoord) { return maxAbsCoord < 67108864.0f ? FLX_W
 int wideFar(const flx_ctx *c) { return c->sc.wideClamp == FLX_WIDE_DINV_FAR ? 1 : 0; }
 }
 
-extern "C" {
-
-int flx_update_triangles(flx_ctx *c, const void *tris160, size_t ntris, int src_on_device)
+// The boundary of both calls, written once.  flx_update_triangles: every triangle, count must be the scene's.  flx_update_triangles_subset
+// (`subset`): the source is a list, validation also checks the list and reduces the maximum |coordinate| over the unmoved triangles' stored
+// positions (the clamp is that of the WHOLE resulting set, never a running maximum), and the passes rewrite only what is dirty (refit.hip: one
+// set of passes, two modes).  Every message carries the name of the call it refuses.
+static int updateTriangles(flx_ctx *c, bool subset, const void *tris160, const uint32_t *indices, size_t count, int src_on_device)
 {
+    const std::string fn = subset ? "flx_update_triangles_subset: " : "flx_update_triangles: ";
     ENTER(c, CALL_OBSERVE);                               // deferred and fused launches run against the OLD scene
-    NEED(c, c->sc.bnodes, "flx_update_triangles: upload a scene first (flx_upload_scene)");
-    NEED(c, tris160, "flx_update_triangles: null triangles");
-    NEED(c, ntris == c->rf.ntris, "flx_update_triangles: the triangle count differs from the uploaded scene's (" + std::to_string(ntris) + " vs " + std::to_string(c->rf.ntris) + ")");
-    HIPCHK(c, hipSetDevice(c->device));
-    const void *src = tris160;
-    if (src_on_device) NEED(c, ((uintptr_t)tris160 & 15u) == 0, "flx_update_triangles: a device source must be 16-byte aligned");
-    else {
-        if (!c->rf.stage) {                               // first host source: the staging buffer stays with the scene allocations
-            flx_triangle *st = nullptr;
-            if (dalloc(c, c->sceneAllocs, &st, ntris)) return 1;
-            c->rf.stage = st;
-        }
-        HIPCHK(c, hipMemcpyAsync(c->rf.stage, tris160, ntris * sizeof(flx_triangle), hipMemcpyHostToDevice, c->stream));
-        src = c->rf.stage;
+    NEED(c, c->sc.bnodes, fn + "upload a scene first (flx_upload_scene)");
+    RefitTables &rf = c->rf;
+    if (subset) {
+        NEED(c, count <= rf.ntris, fn + "more triangles listed than the uploaded scene has (" + std::to_string(count) + " vs " + std::to_string(rf.ntris) + ")");
+        NEED(c, count == 0 || (tris160 && indices), fn + "null triangles or indices");
+    } else {
+        NEED(c, tris160, fn + "null triangles");
+        NEED(c, count == rf.ntris, fn + "the triangle count differs from the uploaded scene's (" + std::to_string(count) + " vs " + std::to_string(rf.ntris) + ")");
     }
-    // one reduction over the source, one small blocking read (as flx_mk_adaptive_update reads its count)
-    uint32_t v[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemsetAsync(c->rf.valid, 0, 16, c->stream));
-    launch_refit_validate(c->stream, src, c->rf.ntris, c->rf.nmat, c->rf.valid);
-    LAUNCHED(c);
-    HIPCHK(c, hipMemcpyAsync(v, c->rf.valid, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float maxAbs; memcpy(&maxAbs, &v[1], 4);
-    NEED(c, !v[0], "flx_update_triangles: triangle with a NaN or infinite vertex");
-    NEED(c, maxAbs <= FLX_WIDE_COORD_MAX, "flx_update_triangles: vertex beyond +-2^62");
-    NEED(c, !v[2], "flx_update_triangles: triangle material id out of range");
-
+    HIPCHK(c, hipSetDevice(c->device));
+    const void *src = tris160; const uint32_t *idx = subset ? indices : nullptr;
+    if (!subset || count) {                               // (nothing listed: no byte of any tree changes)
+        if (src_on_device) {
+            if (subset) NEED(c, ((uintptr_t)tris160 & 15u) == 0 && ((uintptr_t)indices & 3u) == 0, fn + "a device source must be 16-byte (triangles) and 4-byte (indices) aligned");
+            else NEED(c, ((uintptr_t)tris160 & 15u) == 0, fn + "a device source must be 16-byte aligned");
+        } else {                                          // first host source: the staging buffers (ntris wire triangles, ntris indices) stay with the scene allocations
+            if (!rf.stage) {
+                flx_triangle *st = nullptr;
+                if (dalloc(c, c->sceneAllocs, &st, rf.ntris)) return 1;
+                rf.stage = st;
+            }
+            HIPCHK(c, hipMemcpyAsync(rf.stage, tris160, count * sizeof(flx_triangle), hipMemcpyHostToDevice, c->stream));
+            src = rf.stage;
+            if (subset) {
+                if (!rf.stageIdx && dalloc(c, c->sceneAllocs, &rf.stageIdx, rf.ntris)) return 1;
+                HIPCHK(c, hipMemcpyAsync(rf.stageIdx, indices, count * 4, hipMemcpyHostToDevice, c->stream));
+                idx = rf.stageIdx;
+            }
+        }
+        if (subset) {
+            if (!rf.triStamp) {                           // first subset call on this scene: the stamps stay with the scene allocations, zeroed ONCE
+                const size_t nb = c->wideInfo[6], nw = c->wideInfo[0], nl = c->wideInfo[1];
+                uint32_t *st = nullptr;
+                if (dalloc(c, c->sceneAllocs, &st, (size_t)rf.ntris + nb + nw + nl)) return 1;
+                rf.stampWords = (size_t)rf.ntris + nb + nw + nl;
+                HIPCHK(c, hipMemsetAsync(st, 0, rf.stampWords * 4, c->stream));
+                rf.triStamp = st; rf.bStamp = st + rf.ntris; rf.wStamp = rf.bStamp + nb; rf.lStamp = rf.wStamp + nw;
+                rf.epoch = 0;
+            }
+            if (++rf.epoch == 0) {                        // the counter wrapped: stamps of 2^32 calls ago would read as this call's
+                HIPCHK(c, hipMemsetAsync(rf.triStamp, 0, rf.stampWords * 4, c->stream));
+                rf.epoch = 1;
+            }
+        }
+        // one reduction over the source, one small blocking read (as flx_mk_adaptive_update reads its count)
+        uint32_t v[4] = {0, 0, 0, 0};
+        HIPCHK(c, hipMemsetAsync(rf.valid, 0, 16, c->stream));
+        launch_refit_validate(c->stream, src, idx, (uint32_t)count, c->sc, rf, rf.valid);
+        LAUNCHED(c);
+        HIPCHK(c, hipMemcpyAsync(v, rf.valid, 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        float maxAbs; memcpy(&maxAbs, &v[1], 4);
+        NEED(c, !(v[3] & 2u), fn + "triangle index out of range");              // (v[3]: the list's word, zero without one)
+        NEED(c, !(v[3] & 1u), fn + "the indices are not strictly ascending");
+        NEED(c, !v[0], fn + "triangle with a NaN or infinite vertex");
+        NEED(c, maxAbs <= FLX_WIDE_COORD_MAX, fn + "vertex beyond +-2^62");
+        NEED(c, !v[2], fn + "triangle material id out of range");
+        // the root box is the union of the vertices: the same maximum -- over the moved triangles' new and the unmoved triangles' stored
+        // positions -- re-derives the node test's clamp
+        c->sc.wideClamp = wideClampFor(maxAbs);
+    }
     // what flx_upload_scene clears: a list of active pixels and a G-buffer belong to the render of one geometry
     c->ad.have = false;
     c->temporal.gbTraced[0] = c->temporal.gbTraced[1] = false; c->temporal.histHave = false;
-    // the root box is the union of the vertices: the same maximum re-derives the node test's clamp
-    c->sc.wideClamp = wideClampFor(maxAbs);
+    if (subset && !count) return 0;
     {
         ScopedTimer t(c, FLX_K_REFIT);
-        launch_refit(c->stream, src, c->sc, c->rf);
+        launch_refit(c->stream, src, idx, (uint32_t)count, c->sc, rf);
     }
     LAUNCHED(c);
     return 0;
 }
 
-// What changes against flx_update_triangles: the source is a list; validation also checks the list and reduces the maximum |coordinate| over the
-// unmoved triangles' stored positions (the clamp is that of the WHOLE resulting set, never a running maximum); the passes rewrite only what is
-// dirty (refit.hip).  The boundary is the same, line for line.
+extern "C" {
+
+int flx_update_triangles(flx_ctx *c, const void *tris160, size_t ntris, int src_on_device)
+{
+    return updateTriangles(c, false, tris160, nullptr, ntris, src_on_device);
+}
+
 int flx_update_triangles_subset(flx_ctx *c, const void *tris160, const uint32_t *indices, size_t count, int src_on_device)
 {
-    ENTER(c, CALL_OBSERVE);                               // deferred and fused launches run against the OLD scene
-    NEED(c, c->sc.bnodes, "flx_update_triangles_subset: upload a scene first (flx_upload_scene)");
-    NEED(c, count <= c->rf.ntris, "flx_update_triangles_subset: more triangles listed than the uploaded scene has (" + std::to_string(count) + " vs " + std::to_string(c->rf.ntris) + ")");
-    NEED(c, count == 0 || (tris160 && indices), "flx_update_triangles_subset: null triangles or indices");
-    HIPCHK(c, hipSetDevice(c->device));
-    RefitTables &rf = c->rf;
-    const void *src = tris160; const uint32_t *idx = indices;
-    if (count) {
-        if (!rf.triStamp) {                               // first call on this scene: the stamps stay with the scene allocations, zeroed ONCE
-            const size_t nb = c->wideInfo[6], nw = c->wideInfo[0], nl = c->wideInfo[1];
-            uint32_t *st = nullptr;
-            if (dalloc(c, c->sceneAllocs, &st, (size_t)rf.ntris + nb + nw + nl)) return 1;
-            rf.stampWords = (size_t)rf.ntris + nb + nw + nl;
-            HIPCHK(c, hipMemsetAsync(st, 0, rf.stampWords * 4, c->stream));
-            rf.triStamp = st; rf.bStamp = st + rf.ntris; rf.wStamp = rf.bStamp + nb; rf.lStamp = rf.wStamp + nw;
-            rf.epoch = 0;
-        }
-        if (src_on_device) NEED(c, ((uintptr_t)tris160 & 15u) == 0 && ((uintptr_t)indices & 3u) == 0, "flx_update_triangles_subset: a device source must be 16-byte (triangles) and 4-byte (indices) aligned");
-        else {
-            if (!rf.stage) {                              // shared with flx_update_triangles: ntris wire triangles
-                flx_triangle *st = nullptr;
-                if (dalloc(c, c->sceneAllocs, &st, rf.ntris)) return 1;
-                rf.stage = st;
-            }
-            if (!rf.stageIdx && dalloc(c, c->sceneAllocs, &rf.stageIdx, rf.ntris)) return 1;
-            HIPCHK(c, hipMemcpyAsync(rf.stage, tris160, count * sizeof(flx_triangle), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(rf.stageIdx, indices, count * 4, hipMemcpyHostToDevice, c->stream));
-            src = rf.stage; idx = rf.stageIdx;
-        }
-        if (++rf.epoch == 0) {                            // the counter wrapped: stamps of 2^32 calls ago would read as this call's
-            HIPCHK(c, hipMemsetAsync(rf.triStamp, 0, rf.stampWords * 4, c->stream));
-            rf.epoch = 1;
-        }
-        uint32_t v[4] = {0, 0, 0, 0};
-        HIPCHK(c, hipMemsetAsync(rf.valid, 0, 16, c->stream));
-        launch_refit_subset_validate(c->stream, src, idx, (uint32_t)count, c->sc, rf, rf.valid);
-        LAUNCHED(c);
-        HIPCHK(c, hipMemcpyAsync(v, rf.valid, 16, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        float maxAbs; memcpy(&maxAbs, &v[1], 4);
-        NEED(c, !(v[3] & 2u), "flx_update_triangles_subset: triangle index out of range");
-        NEED(c, !(v[3] & 1u), "flx_update_triangles_subset: the indices are not strictly ascending");
-        NEED(c, !v[0], "flx_update_triangles_subset: triangle with a NaN or infinite vertex");
-        NEED(c, maxAbs <= FLX_WIDE_COORD_MAX, "flx_update_triangles_subset: vertex beyond +-2^62");
-        NEED(c, !v[2], "flx_update_triangles_subset: triangle material id out of range");
-        c->sc.wideClamp = wideClampFor(maxAbs);           // of the moved triangles' new and the unmoved triangles' stored positions
-    }
-    c->ad.have = false;
-    c->temporal.gbTraced[0] = c->temporal.gbTraced[1] = false; c->temporal.histHave = false;
-    if (!count) return 0;                                 // nothing listed: no byte of any tree changes
-    {
-        ScopedTimer t(c, FLX_K_REFIT);
-        launch_refit_subset(c->stream, src, idx, (uint32_t)count, c->sc, rf);
-    }
-    LAUNCHED(c);
-    return 0;
+    return updateTriangles(c, true, tris160, indices, count, src_on_device);
 }
 
 int flx_tree_read(flx_ctx *c, int which, void *out, size_t bytes, size_t *needed)

@@ -2,6 +2,7 @@
 // quantised tree) and flx_upload_envmap (alias records, the per-texel NEE table).  Both build the new set first and switch over only on success.
 #include "flx_ctx.h"
 #include "flx_wide.h"
+#include "flx_refit.h"
 #include "flx_trace.h"
 #include "flx_trace4.h"
 #include <cmath>
@@ -146,13 +147,10 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     // 3. shading records per ORIGINAL triangle index
     std::vector<ShadeRec> shade(ntris);
     for (size_t i = 0; i < ntris; i++) {
-        const flx_triangle &t = tris[i];
-        float fm; int m = t.matId; memcpy(&fm, &m, 4);
+        const int m = tris[i].matId;
         NEED(c, m >= 0 && (size_t)m < nmat, "flx_upload_scene: triangle material id out of range");
-        shade[i].a = make_float4(t.v0.n.x, t.v0.n.y, t.v0.n.z, t.v0.t.x);
-        shade[i].b = make_float4(t.v1.n.x, t.v1.n.y, t.v1.n.z, t.v0.t.y);
-        shade[i].c = make_float4(t.v2.n.x, t.v2.n.y, t.v2.n.z, t.v1.t.x);
-        shade[i].d = make_float4(t.v1.t.y, t.v2.t.x, t.v2.t.y, fm);
+        float4 w[10]; memcpy(w, &tris[i], sizeof w);       // the wire triangle as the refit's shade pass reads it
+        flxrf::rf_shade_rec(w, shade[i].a, shade[i].b, shade[i].c, shade[i].d);
     }
     // 4. the 4-wide quantised tree over the same leaves (flx_wide.h) + the depth of the binary tree (stack-spill sizing)
     // (Round 4 re-optimised the inner topology over the reference's leaves before this collapse -- subtree reinsertion, archived in

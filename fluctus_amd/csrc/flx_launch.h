@@ -28,10 +28,9 @@ struct RefitTables {
     uint32_t epoch = 0;
     uint32_t *stageIdx = nullptr;                       // ntris indices for a host source (the triangles go to `stage`); allocated by the first such call
 };
-void launch_refit_validate(hipStream_t, const void *, uint32_t, uint32_t, uint32_t *);
-void launch_refit(hipStream_t, const void *, const Scene &, const RefitTables &);
-void launch_refit_subset_validate(hipStream_t, const void *, const uint32_t *, uint32_t, const Scene &, const RefitTables &, uint32_t *);
-void launch_refit_subset(hipStream_t, const void *, const uint32_t *, uint32_t, const Scene &, const RefitTables &);
+// (source triangles, index list, listed count: a null list means every triangle of the scene, the full refit)
+void launch_refit_validate(hipStream_t, const void *, const uint32_t *, uint32_t, const Scene &, const RefitTables &, uint32_t *);
+void launch_refit(hipStream_t, const void *, const uint32_t *, uint32_t, const Scene &, const RefitTables &);
 size_t tree_cost_slab_doubles(const RefitTables &);
 double *launch_tree_cost(hipStream_t, const Scene &, const RefitTables &, double *);      // -> where the eight results land in the slab
 void launch_extend(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *, int);

@@ -49,6 +49,17 @@ FLX_RF_HD int rf_exponent(double x) { uint64_t b; __builtin_memcpy(&b, &x, 8); r
 FLX_RF_HD float rf_min(float acc, float v) { return v < acc ? v : acc; }
 FLX_RF_HD float rf_max(float acc, float v) { return v > acc ? v : acc; }
 
+// The shading record of one wire triangle -- ten 4-float vectors: v0 {p, n, t} v1 {p, n, t} v2 {p, n, t} {matId, pad} -- as the traversal and
+// material kernels read it (ShadeRec, flx_device.h): the three normals, the uvs packed into the spare words, the matId's bits last.  V4 is
+// float4 on both sides (a template only so that this header needs no vector type); flx_upload_scene and the refit's shade pass both call it.
+template <class V4> FLX_RF_HD void rf_shade_rec(const V4 t[10], V4 &a, V4 &b, V4 &c, V4 &d)
+{
+    a.x = t[1].x; a.y = t[1].y; a.z = t[1].z; a.w = t[2].x;
+    b.x = t[4].x; b.y = t[4].y; b.z = t[4].z; b.w = t[2].y;
+    c.x = t[7].x; c.y = t[7].y; c.z = t[7].z; c.w = t[5].x;
+    d.x = t[5].y; d.y = t[8].x; d.z = t[8].y; d.w = t[9].x;
+}
+
 struct Split { double h, l; };         // h + l, exactly
 FLX_RF_HD Split rf_diff(float c, float lo)
 {

@@ -483,30 +483,41 @@ void BVH::build(const std::vector<flx_triangle> *tris, Mode mode)
     }
 }
 
-void BVH::refit(const std::vector<flx_triangle> &tris)
+// The bottom-up fold of BVH::refit and BVH::refitSubset over `nodes`: a leaf becomes the union of the full bounds of its triangles, an inner node
+// the union of its two children, left first, as the kernel folds.  With a `moved` mask (one flag per triangle) only a node with a moved triangle
+// below it is written; without one every node is.  `who` names the caller in what is thrown.
+static void refitFold(std::vector<flx_node> &nodes, const std::vector<uint32_t> &indices, const std::vector<flx_triangle> &tris, const std::vector<uint8_t> *moved, const std::string &who)
 {
-    const size_t n = m_nodes.size();
+    const size_t n = nodes.size();
+    std::vector<uint8_t> dirty(moved ? n : 0, 0);
     for (size_t i = n; i-- > 0;) {                           // DFS order: both children come after their parent
-        flx_node &nd = m_nodes[i];
+        flx_node &nd = nodes[i];
         Box b;
+        bool d = !moved;
         if (nd.nPrims) {
-            if ((size_t)nd.iStartOrRight + nd.nPrims > m_indices.size()) throw std::runtime_error("BVH::refit: leaf range outside the index list");
+            if ((size_t)nd.iStartOrRight + nd.nPrims > indices.size()) throw std::runtime_error(who + ": leaf range outside the index list");
             for (uint32_t k = 0; k < nd.nPrims; k++) {
-                const uint32_t ti = m_indices[nd.iStartOrRight + k];
-                if (ti >= tris.size()) throw std::runtime_error("BVH::refit: triangle index out of range");
+                const uint32_t ti = indices[nd.iStartOrRight + k];
+                if (ti >= tris.size()) throw std::runtime_error(who + ": triangle index out of range");
+                if (moved) d |= (*moved)[ti] != 0;
                 const flx_triangle &t = tris[ti];
                 b.expand(&t.v0.p.x); b.expand(&t.v1.p.x); b.expand(&t.v2.p.x);
             }
         } else {
             const size_t l = i + 1, r = nd.iStartOrRight;
-            if (l >= n || r >= n || r <= i) throw std::runtime_error("BVH::refit: child index out of range");
-            const float *lmn = &m_nodes[l].bmin.x, *lmx = &m_nodes[l].bmax.x, *rmn = &m_nodes[r].bmin.x, *rmx = &m_nodes[r].bmax.x;
-            for (int k = 0; k < 3; k++) { b.mn[k] = rmn[k] < lmn[k] ? rmn[k] : lmn[k]; b.mx[k] = rmx[k] > lmx[k] ? rmx[k] : lmx[k]; }   // left first, as the kernel folds
+            if (l >= n || r >= n || r <= i) throw std::runtime_error(who + ": child index out of range");
+            if (moved) d = dirty[l] | dirty[r];
+            const float *lmn = &nodes[l].bmin.x, *lmx = &nodes[l].bmax.x, *rmn = &nodes[r].bmin.x, *rmx = &nodes[r].bmax.x;
+            for (int k = 0; k < 3; k++) { b.mn[k] = rmn[k] < lmn[k] ? rmn[k] : lmn[k]; b.mx[k] = rmx[k] > lmx[k] ? rmx[k] : lmx[k]; }
         }
+        if (!d) continue;                                    // every clean node keeps its bytes
+        if (moved) dirty[i] = 1;
         nd.bmin.x = b.mn[0]; nd.bmin.y = b.mn[1]; nd.bmin.z = b.mn[2];
         nd.bmax.x = b.mx[0]; nd.bmax.y = b.mx[1]; nd.bmax.z = b.mx[2];
     }
 }
+
+void BVH::refit(const std::vector<flx_triangle> &tris) { refitFold(m_nodes, m_indices, tris, nullptr, "BVH::refit"); }     // in place, as the device refits
 
 void BVH::refitSubset(const std::vector<flx_triangle> &tris, const std::vector<uint32_t> &indices)
 {
@@ -516,32 +527,8 @@ void BVH::refitSubset(const std::vector<flx_triangle> &tris, const std::vector<u
         if (k && indices[k - 1] >= indices[k]) throw std::runtime_error("BVH::refitSubset: the indices are not strictly ascending");
         moved[indices[k]] = 1;
     }
-    const size_t n = m_nodes.size();
-    std::vector<flx_node> out(m_nodes);                      // a throw below leaves m_nodes as it was
-    std::vector<uint8_t> dirty(n, 0);
-    for (size_t i = n; i-- > 0;) {                           // DFS order: both children come after their parent
-        flx_node &nd = out[i];
-        Box b;
-        if (nd.nPrims) {
-            if ((size_t)nd.iStartOrRight + nd.nPrims > m_indices.size()) throw std::runtime_error("BVH::refitSubset: leaf range outside the index list");
-            for (uint32_t k = 0; k < nd.nPrims; k++) {
-                const uint32_t ti = m_indices[nd.iStartOrRight + k];
-                if (ti >= tris.size()) throw std::runtime_error("BVH::refitSubset: triangle index out of range");
-                dirty[i] |= moved[ti];
-                const flx_triangle &t = tris[ti];
-                b.expand(&t.v0.p.x); b.expand(&t.v1.p.x); b.expand(&t.v2.p.x);
-            }
-        } else {
-            const size_t l = i + 1, r = nd.iStartOrRight;
-            if (l >= n || r >= n || r <= i) throw std::runtime_error("BVH::refitSubset: child index out of range");
-            dirty[i] = dirty[l] | dirty[r];
-            const float *lmn = &out[l].bmin.x, *lmx = &out[l].bmax.x, *rmn = &out[r].bmin.x, *rmx = &out[r].bmax.x;
-            for (int k = 0; k < 3; k++) { b.mn[k] = rmn[k] < lmn[k] ? rmn[k] : lmn[k]; b.mx[k] = rmx[k] > lmx[k] ? rmx[k] : lmx[k]; }   // left first, as BVH::refit
-        }
-        if (!dirty[i]) continue;                             // every clean node keeps its bytes
-        nd.bmin.x = b.mn[0]; nd.bmin.y = b.mn[1]; nd.bmin.z = b.mn[2];
-        nd.bmax.x = b.mx[0]; nd.bmax.y = b.mx[1]; nd.bmax.z = b.mx[2];
-    }
+    std::vector<flx_node> out(m_nodes);                      // a throw in the fold leaves m_nodes as it was
+    refitFold(out, m_indices, tris, &moved, "BVH::refitSubset");
     m_nodes.swap(out);
 }
 

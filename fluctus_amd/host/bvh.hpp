@@ -52,7 +52,7 @@ public:
     // children.  Node order, parents, child links and the index list are untouched; worldRadius() follows the new root box.  The CPU
     // restatement of the device refit (csrc/refit.hip), bit for bit.  Throws on a malformed tree or an index outside tris.
     void refit(const std::vector<flx_triangle> &tris);
-    // The same for a SUBSET of the triangles (csrc/refit.hip: the subset passes).  tris is the full array with the moved
+    // The same for a SUBSET of the triangles (csrc/refit.hip: the passes' SUBSET mode; one fold in bvh.cpp serves both).  tris is the full array with the moved
     // triangles already in place, indices lists them, strictly ascending.  A leaf holding a listed triangle becomes the union of the full bounds
     // of its triangles, an inner node with a changed child the union of its two children; EVERY OTHER NODE KEEPS ITS BYTES, so a clipped SBVH leaf
     // none of whose triangles moved stays clipped.  Throws -- and leaves the nodes untouched -- on a malformed tree, an index outside tris, or a

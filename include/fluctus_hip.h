@@ -46,7 +46,7 @@ int flx_upload_scene(flx_ctx *ctx, const void *tris, size_t ntris, const uint32_
                      const void *texdesc, size_t ntex, const uint8_t *texdata, size_t texbytes);
 
 /* Moving the triangles of the uploaded scene (no counterpart in the reference, which rebuilds and re-uploads, src/tracer.cpp:574-590;
- * csrc/flx_refit.h, csrc/refit.hip): replaces every triangle by the `ntris` 160-byte wire triangles given -- positions, normals,
+ * csrc/flx_refit.h, csrc/refit.hip -- its passes with every record dirty --): replaces every triangle by the `ntris` 160-byte wire triangles given -- positions, normals,
  * uvs, matId -- and REFITS both traversal trees on the device: new leaf triangle records, shading records and boxes; the index list, the
  * topology of both trees, materials, textures and the environment map stay as uploaded.  A leaf box becomes the union of the full bounds of its
  * triangles (a leaf an SBVH spatial split had clipped becomes unclipped: correct, only looser) and traversal quality decays as the geometry
@@ -57,13 +57,13 @@ int flx_upload_scene(flx_ctx *ctx, const void *tris, size_t ntris, const uint32_
  * FLX_K_REFIT.  Fails -- and leaves the old scene in place, untouched -- when no scene is uploaded, ntris differs from the uploaded count, a
  * position is not finite or beyond +-2^62 (FLX_WIDE_COORD_MAX), or a matId is outside the uploaded materials. */
 int flx_update_triangles(flx_ctx *ctx, const void *tris160, size_t ntris, int src_on_device);
-/* Moving a SUBSET of the triangles (a dragged object; csrc/refit.hip): tris160[k] is the new 160-byte wire triangle for
+/* Moving a SUBSET of the triangles (a dragged object; csrc/refit.hip -- the same passes in their SUBSET mode --): tris160[k] is the new 160-byte wire triangle for
  * triangle indices[k] of the uploaded scene -- positions, normals, uvs and matId may all change.  Only what hangs above the listed triangles is
  * rewritten: their shading records and leaf triangle records, the headers of the wide leaf blocks holding one (the union of the full bounds of the
  * block's triangles), the halves of the binary records and the 4-wide nodes with such a leaf below them.  EVERY OTHER BYTE of the five
  * flx_tree_read arrays stays as it was, so an SBVH leaf a spatial split had clipped stays clipped unless one of its own triangles is listed (moving
  * a triangle back does not re-clip its leaves).  Both pointers are host memory, or device memory when src_on_device != 0 (tris160 16-byte,
- * indices 4-byte aligned).  The boundary is flx_update_triangles': flushes deferred and fused launches against the OLD scene first, clears the
+ * indices 4-byte aligned).  The boundary is flx_update_triangles' (one function, csrc/api_refit.hip): flushes deferred and fused launches against the OLD scene first, clears the
  * adaptive list, marks the G-buffer slots and the captured history not traced, touches no path state, queue or counter, keeps what the upload
  * chose; allocates only at its first call (stamps; the staging buffers at the first call with a host source), one small blocking read (the
  * validation), timed under FLX_K_REFIT.  The wide node test's clamp is re-derived from the whole resulting triangle set (read-only option

@@ -10,6 +10,8 @@ extent) goes in through HipContext.update_triangles_subset.  The reference is ho
               at most 2 x the host quantiser's, unused slots inverted)
   algebra     every index listed = update_triangles; two disjoint calls = one; a repeated call changes nothing; two contexts agree; on the
               unclipped cases arrays 0, 1, 2, 4 equal the full update's (array 3 may keep the upload's host-quantised grid on clean nodes)
+  modes       subset, full, subset in one context = full, subset, checked against host.refit_bvh + host.refit_bvh_subset; the full update again =
+              "upload, full update"; device and host sources mixed (one context's stamps, epoch, staging buffers and triangle copy serve both calls)
   parity      test_gpu_refit._compare against the oracle on host.refit_bvh_subset's nodes and the float64 brute force, fresh upload first
   render      "upload, subset update" = "upload of the result with the subset-refit nodes", bit for bit, both integrators
   cost        the binary figure of flx_tree_cost after the subset update is strictly below the full update's
@@ -194,6 +196,48 @@ def test_subset_algebra_on_the_device(name, builder):
             assert once[0].tobytes() != full[0].tobytes(), "a clipped case equals the full update: the call forwards to it"
     finally:
         a.close(); b.close(); c.close()
+
+
+def test_full_and_subset_updates_interleaved_in_one_context():
+    """The two calls are two modes over one context's stamps, epoch, staging buffers and device copy of the triangles: in either order they leave
+    what the host's BVH::refit / BVH::refitSubset leave, and a full update leaves no history behind, of stamps either."""
+    import torch
+    name = "spatial_splits-o0"                               # clipped leaves: a subset result differs from a full one
+    d = sc.built(name, "sbvh")
+    P = rc.SCENES[name]
+    idx, P2 = sc.S(name)
+    h0, h1 = idx[::2], idx[1::2]
+    first = rc.moved(d, P2).tris[h0]
+    PT = rc.deform(P, "smooth")
+    rT = host.refit_bvh(rc.with_shading(rc.moved(d, PT)))    # T: every triangle moved and re-shaded
+    PF = sc.translated(PT, h1, sc.standard_shift(P))         # then h1 moved again, by the standard shift, and re-shaded with other draws
+    m = copy.copy(rT)
+    m.tris, m.nodes = rT.tris.copy(), rT.nodes.copy()
+    m.tris[h1] = sc.with_shading_on(rc.moved(rT, PF), h1, seed=7).tris[h1]
+    r = host.refit_bvh_subset(m, h1)
+    a, b, f = _ctx(256), _ctx(256), _ctx(256)
+    try:
+        # A: upload, subset(h0) from a device source, full(T) and subset(h1) from host sources (the staging buffers are shared)
+        a.upload_scene(d)
+        t = torch.from_numpy(np.frombuffer(first.tobytes(), np.uint8).copy()).cuda()
+        i = torch.from_numpy(h0.astype(np.int32)).cuda()
+        a.update_triangles_subset(t, i, on_device=True)
+        a.update_triangles(rT.tris)
+        before = _arrays(a)
+        a.update_triangles_subset(r.tris[h1], h1)
+        after = _arrays(a)
+        # B: upload, full(T), the same last call
+        b.upload_scene(d); b.update_triangles(rT.tris); b.update_triangles_subset(r.tris[h1], h1)
+        _same(after, _arrays(b), "subset, full, subset vs full, subset")
+        f.upload_scene(r)
+        nb, nw, _ = _check_subset(before, after, d, r, h1, f.tree_read(2))
+        assert 0 < nb < after[0].shape[0] and 0 < nw
+        # the full call again, on what the subset call left: exactly "upload, full(final triangle set)"
+        a.update_triangles(r.tris)
+        f.upload_scene(d); f.update_triangles(r.tris)
+        _same(_arrays(a), _arrays(f), "full after subset vs upload, full")
+    finally:
+        a.close(); b.close(); f.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
