@@ -40,6 +40,7 @@ def build_host(force=False):
     dep = src + glob.glob(os.path.join(PKG, "host", "*.hpp")) + _headers() + [os.path.join(PKG, "csrc", "flx_wide.h"),   # host_capi.cpp includes the wide-tree builder
                                                                                         os.path.join(PKG, "csrc", "flx_refit.h"),  # ... and the refit's quantiser
                                                                                         os.path.join(PKG, "csrc", "flx_tree_cost.h"),  # ... and the cost sums
+                                                                                        os.path.join(PKG, "csrc", "flx_pose.h"),   # ... and the pose arithmetic
                                                                                         os.path.join(PKG, "csrc", "flx_adaptive.h")]   # hipcontext.hpp: the adaptive defaults
     out = os.path.join(PKG, "libfluctus_host.so")
     if force or _stale(out, dep):

@@ -80,13 +80,19 @@ __global__ __launch_bounds__(AD_BLOCK) void k_ad_scatter(const uint8_t *flags, u
 
 uint32_t adaptive_blocks(uint32_t npix) { return (npix + AD_BLOCK - 1) / AD_BLOCK; }
 
+// the scan on its own, for the other users of this scheme (pose.hip)
+void launch_block_scan(hipStream_t s, uint32_t *blockCounts, uint32_t nb, uint32_t *total)
+{
+    hipLaunchKernelGGL(k_ad_scan, dim3(1), dim3(1024), 0, s, blockCounts, nb, total);
+}
+
 // mom: the moments of W x H pixels; flags: W * H bytes; blockScratch: adaptive_blocks(W * H) words; list: W * H words; count: one word
 void launch_adaptive_update(hipStream_t s, const float4 *mom, int W, int H, const ad_params &ap, uint8_t *flags, uint32_t *blockScratch, uint32_t *list,
                             uint32_t *count)
 {
     const uint32_t npix = (uint32_t)W * (uint32_t)H, nb = adaptive_blocks(npix);
     hipLaunchKernelGGL(k_ad_classify, dim3(nb), dim3(AD_BLOCK), 0, s, mom, W, H, ap, flags, blockScratch);
-    hipLaunchKernelGGL(k_ad_scan, dim3(1), dim3(1024), 0, s, blockScratch, nb, count);
+    launch_block_scan(s, blockScratch, nb, count);
     hipLaunchKernelGGL(k_ad_scatter, dim3(nb), dim3(AD_BLOCK), 0, s, flags, npix, blockScratch, list);
 }
 

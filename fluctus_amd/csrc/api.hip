@@ -202,7 +202,7 @@ int flx_destroy(flx_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) { flx_group_destroy(c); }
-    c->releaseFrameFeatures(); c->gather.release();
+    c->releaseFrameFeatures(); c->gather.release(); c->ob.release();
     freeAll(c->sceneAllocs); freeAll(c->spillAllocs); freeAll(c->envAllocs); freeAll(c->frameAllocs); freeAll(c->aovAllocs); freeAll(c->momAllocs); freeAll(c->fixedAllocs);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pinnedIdx) (void)hipHostFree(c->pinnedIdx);

@@ -2,7 +2,10 @@
 // flx_upload_scene built (kernels: refit.hip; arithmetic and the exactness argument: flx_refit.h), and its test hook
 // flx_tree_read, and flx_tree_cost (kernels: tree_cost.hip; what is summed: flx_tree_cost.h): how far the refits have degraded
 // the trees.  Validation runs on the device BEFORE anything is overwritten, so a refused call leaves the old scene as it was.
+// flx_objects_define / flx_objects_pose (kernels: pose.hip; arithmetic: flx_pose.h): objects over the uploaded triangles, moved by
+// a matrix each -- their triangles are produced on the device and handed to the subset refit as a device source -- and the test hook flx_objects_read.
 #include "flx_ctx.h"
+#include "flx_pose.h"
 #include "flx_wide.h"
 #include "flx_trace4.h"
 #include <cstring>
@@ -15,10 +18,10 @@ int wideFar(const flx_ctx *c) { return c->sc.wideClamp == FLX_WIDE_DINV_FAR ? 1 
 // The boundary of both calls, written once.  flx_update_triangles: every triangle, count must be the scene's.  flx_update_triangles_subset
 // (`subset`): the source is a list, validation also checks the list and reduces the maximum |coordinate| over the unmoved triangles' stored
 // positions (the clamp is that of the WHOLE resulting set, never a running maximum), and the passes rewrite only what is dirty (refit.hip: one
-// set of passes, two modes).  Every message carries the name of the call it refuses.
-static int updateTriangles(flx_ctx *c, bool subset, const void *tris160, const uint32_t *indices, size_t count, int src_on_device)
+// set of passes, two modes).  Every message carries the name of the call it refuses (`as`: flx_objects_pose, which ends in the subset call).
+static int updateTriangles(flx_ctx *c, bool subset, const void *tris160, const uint32_t *indices, size_t count, int src_on_device, const char *as = nullptr)
 {
-    const std::string fn = subset ? "flx_update_triangles_subset: " : "flx_update_triangles: ";
+    const std::string fn = as ? as : subset ? "flx_update_triangles_subset: " : "flx_update_triangles: ";
     ENTER(c, CALL_OBSERVE);                               // deferred and fused launches run against the OLD scene
     NEED(c, c->sc.bnodes, fn + "upload a scene first (flx_upload_scene)");
     RefitTables &rf = c->rf;
@@ -103,6 +106,97 @@ int flx_update_triangles(flx_ctx *c, const void *tris160, size_t ntris, int src_
 int flx_update_triangles_subset(flx_ctx *c, const void *tris160, const uint32_t *indices, size_t count, int src_on_device)
 {
     return updateTriangles(c, true, tris160, indices, count, src_on_device);
+}
+
+int flx_objects_define(flx_ctx *c, const void *tris160_rest, size_t ntris, const uint32_t *object_of_triangle, uint32_t nobjects)
+{
+    const std::string fn = "flx_objects_define: ";
+    ENTER(c, CALL_OBSERVE);
+    NEED(c, c->sc.bnodes, fn + "upload a scene first (flx_upload_scene)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!nobjects) { c->ob.release(); return 0; }
+    NEED(c, tris160_rest && object_of_triangle, fn + "null triangles or object ids");
+    NEED(c, ntris == c->rf.ntris, fn + "the triangle count differs from the uploaded scene's (" + std::to_string(ntris) + " vs " + std::to_string(c->rf.ntris) + ")");
+    flx_ctx::Objects ob;                                  // built aside: a refused or failed call leaves the earlier definition in place
+    ob.counts.resize(nobjects);
+    size_t bad = 0;
+    const size_t members = flx::ps_count_members(object_of_triangle, ntris, nobjects, ob.counts.data(), &bad);
+    NEED(c, members != (size_t)-1, fn + "triangle " + std::to_string(bad) + " has an object id that is neither below the object count nor FLX_NO_OBJECT");
+    std::vector<uint32_t> tri(members), obj(members);
+    std::vector<flx_triangle> rest(members);
+    flx::ps_compact_members(tris160_rest, object_of_triangle, ntris, tri.data(), obj.data(), rest.data());
+    ObjectTables &t = ob.t;
+    t.nobjects = nobjects; t.members = (uint32_t)members;
+    const uint32_t nb = pose_blocks(t.members);
+    struct Guard { flx_ctx::Objects &o; bool keep = false; ~Guard() { if (!keep) freeAll(o.allocs); } } guard{ob};
+    if (dalloc(c, ob.allocs, &t.memberTri, members) || dalloc(c, ob.allocs, &t.memberObj, members) || dalloc(c, ob.allocs, &t.rest, members * FLX_PS_TRI_V4) ||
+        dalloc(c, ob.allocs, &t.stamp, (size_t)nobjects * 2) || dalloc(c, ob.allocs, &t.ids, nobjects) || dalloc(c, ob.allocs, &t.xforms, (size_t)nobjects * 3) ||
+        dalloc(c, ob.allocs, &t.out, members * FLX_PS_TRI_V4) || dalloc(c, ob.allocs, &t.outIdx, members) || dalloc(c, ob.allocs, &t.blockCounts, (size_t)nb + 1)) return 1;
+    t.slot = t.stamp + nobjects; t.total = t.blockCounts + nb;
+    if (members) {
+        HIPCHK(c, hipMemcpy(t.memberTri, tri.data(), members * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(t.memberObj, obj.data(), members * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(t.rest, rest.data(), members * sizeof(flx_triangle), hipMemcpyHostToDevice));
+    }
+    HIPCHK(c, hipMemset(t.stamp, 0, (size_t)nobjects * 8));  // epoch 0 is never a call's
+    ob.have = true;
+    guard.keep = true;
+    c->ob.release();
+    c->ob = std::move(ob);
+    return 0;
+}
+
+int flx_objects_pose(flx_ctx *c, const uint32_t *object_ids, const float *xforms12, uint32_t count)
+{
+    const char *name = "flx_objects_pose: ";
+    const std::string fn = name;
+    ENTER(c, CALL_OBSERVE);                               // deferred and fused launches run against the OLD scene
+    NEED(c, c->sc.bnodes, fn + "upload a scene first (flx_upload_scene)");
+    NEED(c, c->ob.have, fn + "no objects are defined (flx_objects_define)");
+    ObjectTables &t = c->ob.t;
+    NEED(c, count <= t.nobjects, fn + "more objects listed than are defined (" + std::to_string(count) + " vs " + std::to_string(t.nobjects) + ")");
+    NEED(c, count == 0 || (object_ids && xforms12), fn + "null object ids or transforms");
+    size_t n = 0;
+    for (uint32_t k = 0; k < count; k++) {
+        const uint32_t o = object_ids[k];
+        NEED(c, o < t.nobjects, fn + "object id out of range (" + std::to_string(o) + " of " + std::to_string(t.nobjects) + ")");
+        NEED(c, k == 0 || o > object_ids[k - 1], fn + "the object ids are not strictly ascending");
+        NEED(c, flx::ps_xform_finite(xforms12 + 12 * (size_t)k), fn + "the transform of object " + std::to_string(o) + " has a NaN or infinite entry");
+        NEED(c, flx::ps_xform_invertible(xforms12 + 12 * (size_t)k), fn + "the transform of object " + std::to_string(o) + " has a zero or non-finite determinant");
+        n += c->ob.counts[o];
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n) {
+        // the list goes up as flx_update_triangles_subset's host source does: read by the time the validation's blocking read returns
+        HIPCHK(c, hipMemcpyAsync(t.ids, object_ids, (size_t)count * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(t.xforms, xforms12, (size_t)count * 48, hipMemcpyHostToDevice, c->stream));
+        if (++t.epoch == 0) {                             // the counter wrapped: stamps of 2^32 calls ago would read as this call's
+            HIPCHK(c, hipMemsetAsync(t.stamp, 0, (size_t)t.nobjects * 4, c->stream));
+            t.epoch = 1;
+        }
+        {
+            ScopedTimer tm(c, FLX_K_REFIT);               // (the refit's own pair follows the validation: one pose is two timed spans of this id)
+            launch_pose(c->stream, t, count);
+        }
+        LAUNCHED(c);
+    }
+    return updateTriangles(c, true, t.out, t.outIdx, n, 1, name);
+}
+
+int flx_objects_read(flx_ctx *c, uint32_t *out_counts, uint32_t *out_nobjects, uint32_t *out_members)
+{
+    ENTER(c, CALL_QUIET);                                 // a read-back of arrays no deferred launch writes
+    NEED(c, c->ob.have, "flx_objects_read: no objects are defined (flx_objects_define)");
+    NEED(c, out_nobjects, "flx_objects_read: null out_nobjects");
+    const ObjectTables &t = c->ob.t;
+    *out_nobjects = t.nobjects;
+    if (out_counts) memcpy(out_counts, c->ob.counts.data(), (size_t)t.nobjects * 4);
+    if (out_members && t.members) {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipMemcpyAsync(out_members, t.memberTri, (size_t)t.members * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
 }
 
 int flx_tree_read(flx_ctx *c, int which, void *out, size_t bytes, size_t *needed)

@@ -246,6 +246,7 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     freeAll(c->sceneAllocs);
     c->sceneAllocs.swap(fresh);
     c->rf = std::move(rf);
+    c->ob.release();                                      // objects are defined over the triangles of one upload (flx_objects_define)
     if (newSpill) { freeAll(c->spillAllocs); c->spillAllocs.swap(freshSpill); c->spill = sp1; c->spill2 = sp2; c->spillLevels = spillLevels; }
     c->sc.bnodes = dB; c->sc.trirecs = dT; c->sc.shade = dS; c->sc.tris = dTri; c->sc.materials = dM; c->sc.texdesc = dD; c->sc.texdata = dX;
     c->sc.rootRef = 0;

@@ -6,7 +6,8 @@
 //   api_image.hip      post-process, the two denoisers, temporal reprojection, the microkernel integrator and its adaptive render
 //   api_group.hip      the multi-GPU group: RCCL binding, flx_group_*, flx_gather*
 //   api_hooks.hip      measurement and test hooks
-//   api_refit.hip      flx_update_triangles / flx_update_triangles_subset (moved triangles -> refitted trees, refit.hip), their test hook flx_tree_read, flx_tree_cost (tree_cost.hip)
+//   api_refit.hip      flx_update_triangles / flx_update_triangles_subset (moved triangles -> refitted trees, refit.hip), their test hook flx_tree_read, flx_tree_cost (tree_cost.hip),
+//                      flx_objects_define / flx_objects_pose (objects posed on the device, pose.hip, handed to the subset refit) and their test hook flx_objects_read
 // Everything here that is not `struct flx_ctx` (the C header's opaque type) lives in namespace flxd, like the launchers (flx_launch.h), so the
 // library's extern "C" surface is include/fluctus_hip.h and nothing else.
 #pragma once
@@ -153,6 +154,16 @@ struct flx_ctx {
         void release() { freeAll(allocs); *this = Adaptive(); }
     } ad;
     void releaseFrameFeatures() { dn.release(); temporal.release(); ad.release(); }
+    // objects over the uploaded triangles (flx_objects_define / flx_objects_pose; pose.hip): the device tables and, per object,
+    // its member count.  The buffers are sized by the scene: a successful flx_upload_scene, a new definition and flx_destroy release them.
+    // have false = no objects are defined.
+    struct Objects {
+        std::vector<void *> allocs;
+        ObjectTables t;
+        std::vector<uint32_t> counts;
+        bool have = false;
+        void release() { freeAll(allocs); *this = Objects(); }
+    } ob;
     int nodeLayout = 1;         // 1 = sibling-pair record numbering (see flx_upload_scene), 0 = DFS
     int numCUs = 256;
     // multi-GPU group (flx_group_*): RCCL communicator of this rank, root-side staging

@@ -31,6 +31,21 @@ struct RefitTables {
 // (source triangles, index list, listed count: a null list means every triangle of the scene, the full refit)
 void launch_refit_validate(hipStream_t, const void *, const uint32_t *, uint32_t, const Scene &, const RefitTables &, uint32_t *);
 void launch_refit(hipStream_t, const void *, const uint32_t *, uint32_t, const Scene &, const RefitTables &);
+// What flx_objects_define keeps for flx_objects_pose (pose.hip); passed to the kernels by value.  Device arrays live with the
+// scene allocations.  A member is a triangle that belongs to an object; members are kept in ascending triangle order.
+struct ObjectTables {
+    uint32_t nobjects = 0, members = 0;
+    uint32_t *memberTri = nullptr, *memberObj = nullptr;        // per member: its triangle index, its object
+    float4 *rest = nullptr;                                     // per member: its rest triangle, ten float4
+    uint32_t *stamp = nullptr, *slot = nullptr;                 // per object: the epoch of the last call that listed it, its position in that call's list
+    uint32_t *ids = nullptr; float4 *xforms = nullptr;          // a call's list: up to nobjects ids, three float4 (a 3 x 4 matrix) each
+    float4 *out = nullptr; uint32_t *outIdx = nullptr;          // `members` posed wire triangles and their triangle indices: the subset refit's device source
+    uint32_t *blockCounts = nullptr, *total = nullptr;          // pose_blocks(members) words, one word
+    uint32_t epoch = 0;                                         // epoch 0 is never a call's; a wrap of the counter re-zeroes the stamps (as RefitTables::epoch)
+};
+uint32_t pose_blocks(uint32_t members);
+void launch_pose(hipStream_t, const ObjectTables &, uint32_t count);
+void launch_block_scan(hipStream_t, uint32_t *blockCounts, uint32_t nb, uint32_t *total);      // adaptive.hip: in place, counts -> exclusive offsets
 size_t tree_cost_slab_doubles(const RefitTables &);
 double *launch_tree_cost(hipStream_t, const Scene &, const RefitTables &, double *);      // -> where the eight results land in the slab
 void launch_extend(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, unsigned long long *, int);

@@ -24,13 +24,15 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_mk_sample_bsdf", "flx_mk_splat", "flx_mk_splat_preview", "flx_mk_stats_async", "flx_mk_stats_reset", "flx_write_pixels", "flx_denoise",
            "flx_denoise_variance_guided", "flx_gbuffer", "flx_history_capture", "flx_reproject", "flx_gbuffer_read", "flx_gbuffer_write",
            "flx_mk_adaptive_update", "flx_mk_adaptive_clear", "flx_mk_active_read", "flx_mk_active_write",
-           "flx_update_triangles", "flx_update_triangles_subset", "flx_tree_read", "flx_tree_cost"]
+           "flx_update_triangles", "flx_update_triangles_subset", "flx_tree_read", "flx_tree_cost",
+           "flx_objects_define", "flx_objects_pose", "flx_objects_read"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
 K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with HipContext.denoise_profile (not part of profile_get)
 K_GBUFFER, K_REPROJECT = 10, 11      # FLX_K_GBUFFER / FLX_K_REPROJECT: profile level 1, read with HipContext.kernel_profile
 K_REFIT = 12                         # FLX_K_REFIT: the kernels of update_triangles, likewise
 K_TREE_COST = 13                     # FLX_K_TREE_COST: the kernels of tree_cost, likewise
+NO_OBJECT = 0xFFFFFFFF               # FLX_NO_OBJECT: a triangle that belongs to no object (objects_define)
 
 
 def tree_cost_value(sums4):
@@ -179,6 +181,42 @@ class HipContext:
         if t.size != i.size:
             raise ValueError("update_triangles_subset: as many triangles as indices")
         self._chk(self.L.flx_update_triangles_subset(self.h, _p(t), _p(i), C.c_size_t(i.size), 0))
+
+    def objects_define(self, rest_tris, object_of_triangle, nobjects):
+        """flx_objects_define (blocking): objects over the uploaded triangles.  rest_tris: a SceneData or a wire.TRIANGLE array of the uploaded
+        length, the REST pose; object_of_triangle[i] < nobjects is triangle i's object, NO_OBJECT a triangle that never moves.  Replaces an
+        earlier definition; nobjects = 0 drops it (and so does upload_scene).  Changes no byte of any tree."""
+        from . import wire
+        if not nobjects:
+            self._chk(self.L.flx_objects_define(self.h, None, C.c_size_t(0), None, C.c_uint32(0)))
+            return
+        t = np.ascontiguousarray(getattr(rest_tris, "tris", rest_tris), wire.TRIANGLE).reshape(-1)
+        o = np.ascontiguousarray(object_of_triangle, np.uint32).reshape(-1)
+        if t.size != o.size:
+            raise ValueError("objects_define: one object id per triangle")
+        self._chk(self.L.flx_objects_define(self.h, _p(t), C.c_size_t(t.size), _p(o), C.c_uint32(int(nobjects))))
+
+    def objects_pose(self, ids, xforms):
+        """flx_objects_pose: xforms[k] (3 x 4, row-major [M | t]) is the ABSOLUTE rest -> world transform of object ids[k] (strictly ascending);
+        objects not listed keep their pose.  The triangles are posed on the device from the rest pose kept there (host.pose_triangles is the
+        same arithmetic on the CPU) and handed to the subset refit as a device source: update_triangles_subset's boundary, one small blocking
+        read, then asynchronous."""
+        i = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        x = np.ascontiguousarray(xforms, np.float32).reshape(-1)
+        if x.size != 12 * i.size:
+            raise ValueError("objects_pose: one 3 x 4 matrix per listed object")
+        self._chk(self.L.flx_objects_pose(self.h, _p(i), _p(x), C.c_uint32(i.size)))
+
+    def objects_read(self):
+        """test hook (blocking): (counts, members) -- the triangles of each defined object, and the device's ascending list of every object's
+        triangles"""
+        n = C.c_uint32()
+        self._chk(self.L.flx_objects_read(self.h, None, C.byref(n), None))
+        counts = np.zeros(n.value, np.uint32)
+        self._chk(self.L.flx_objects_read(self.h, _p(counts), C.byref(n), None))
+        members = np.zeros(int(counts.sum()), np.uint32)
+        self._chk(self.L.flx_objects_read(self.h, _p(counts), C.byref(n), _p(members)))
+        return counts, members
 
     TREE_ARRAYS = {0: ("bnodes", 64), 1: ("trirecs", 48), 2: ("shade", 64), 3: ("wnodes", 64), 4: ("wleaf", 16)}
 

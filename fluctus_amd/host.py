@@ -42,6 +42,8 @@ class SceneData:
         self.type_bits = 0
         self.world_up = (0.0, 1.0, 0.0)
         self.bvh_metrics = None
+        self.object_of_triangle = None      # per triangle: index into object_names, 0xFFFFFFFF = none (OBJ `o` / `g` statements)
+        self.object_names = []
 
 
 def _scene_to_data(h):
@@ -58,6 +60,13 @@ def _scene_to_data(h):
     up = np.zeros(3, np.float32)
     L.fh_scene_world_up(h, up.ctypes.data_as(C.c_void_p))
     d.world_up = tuple(float(x) for x in up)
+    # Scene::objectOfTriangle / objectNames: the OBJ loader's objects (NO_OBJECT = 0xFFFFFFFF: none)
+    d.object_of_triangle = np.full(nt.value, 0xFFFFFFFF, np.uint32)
+    nobj, need = C.c_uint32(), C.c_uint64()
+    _chk(L.fh_scene_objects(h, _p(d.object_of_triangle), C.byref(nobj), None, C.c_uint64(0), C.byref(need)))
+    buf = C.create_string_buffer(int(need.value))
+    _chk(L.fh_scene_objects(h, None, None, buf, C.c_uint64(need.value), None))
+    d.object_names = buf.value.decode().split("\n")[:-1] if nobj.value else []
     return d
 
 
@@ -163,6 +172,19 @@ def refit_bvh_subset(d, indices):
                                    _p(idx), C.c_uint64(idx.size), C.byref(wr)))
     d.world_radius = wr.value
     return d
+
+
+def pose_triangles(rest_tris, xform):
+    """csrc/flx_pose.h on the CPU -- what HipContext.objects_pose computes on the device, bit for bit: the wire triangles rest_tris posed by
+    the 3 x 4 row-major affine transform xform = [M | t] (positions through [M | t], normals through the cofactor matrix of M, turned round
+    when det M < 0, and renormalised; texcoords, matId and the spare words copied).  Returns a new array."""
+    t = np.ascontiguousarray(rest_tris, TRIANGLE).reshape(-1)
+    x = np.ascontiguousarray(xform, np.float32).reshape(-1)
+    if x.size != 12:
+        raise ValueError("pose_triangles: a 3 x 4 matrix")
+    out = np.zeros(t.size, TRIANGLE)
+    _chk(lib().fh_pose_triangles(_p(t), _p(out), C.c_uint64(t.size), _p(x)))
+    return out
 
 
 def _bvh_arrays(h):

@@ -34,6 +34,11 @@ public:
     void updateTriangles(const std::vector<flx_triangle> &tris);  // flx_update_triangles: the uploaded triangles move, both trees are refitted on the device
     // flx_update_triangles_subset: tris[k] replaces triangle indices[k] (strictly ascending); only the boxes above them are refitted
     void updateTriangles(const std::vector<uint32_t> &indices, const std::vector<flx_triangle> &tris);
+    // flx_objects_define / flx_objects_pose: objects over the uploaded triangles (objectOfTriangle[i] < nobjects, or
+    // FLX_NO_OBJECT), then moved by a 3 x 4 row-major matrix each -- the absolute rest -> world transform of object ids[k] (strictly ascending) at
+    // xforms12[12 k]; the triangles are posed on the device and go through the subset refit
+    void defineObjects(const std::vector<flx_triangle> &rest, const std::vector<uint32_t> &objectOfTriangle, uint32_t nobjects);
+    void poseObjects(const std::vector<uint32_t> &ids, const std::vector<float> &xforms12);
     // flx_tree_cost: {A_root, S_node, S_leaf, S_tri} of the binary tree [0..3] and of the 4-wide tree [4..7] as they stand on the device (blocking);
     // flxTreeCostValue (include/fluctus_hip.h) turns four of them into one figure
     std::array<double, 8> treeCost();

@@ -12,6 +12,7 @@
 #include <array>
 #include "../csrc/flx_refit.h"     // the refit's fp64 quantiser compiles for the host too: the CPU tests run what the kernels run
 #include "../csrc/flx_tree_cost.h" // the cost sums of flx_tree_cost, likewise
+#include "../csrc/flx_pose.h"      // the pose arithmetic of flx_objects_pose, likewise
 #include "../csrc/flx_wide.h"      // the 4-wide tree builder is plain host C++ (flx_upload_scene runs it); exposed here for CPU-side tests
 #include <cstring>
 #include <string>
@@ -242,6 +243,27 @@ int fh_bvh_refit_subset(void *nodes, uint64_t nnodes, const uint32_t *indices, u
     if (worldRadius) *worldRadius = b.worldRadius();
     FH_CATCH
 }
+// flx_pose.h on the CPU: out160[k] = in160[k] posed by the 3 x 4 row-major transform xform12 (in and out may be the same buffer)
+int fh_pose_triangles(const void *in160, void *out160, uint64_t count, const float *xform12)
+{
+    FH_TRY
+    if (!xform12 || (count && (!in160 || !out160))) throw std::runtime_error("fh_pose_triangles: null argument");
+    flx::ps_pose_triangles(xform12, in160, out160, (size_t)count);
+    FH_CATCH
+}
+// Scene::objectOfTriangle / objectNames: ids (room for the scene's triangles) and the names joined by '\n' (*needed: bytes incl. the final 0)
+int fh_scene_objects(void *s, uint32_t *objectOf, uint32_t *nobjects, char *names, uint64_t cap, uint64_t *needed)
+{
+    FH_TRY
+    Scene *sc = (Scene *)s;
+    std::string joined;
+    for (const std::string &n : sc->objectNames()) { joined += n; joined += '\n'; }
+    if (nobjects) *nobjects = (uint32_t)sc->objectNames().size();
+    if (needed) *needed = joined.size() + 1;
+    if (objectOf) { const std::vector<uint32_t> v = sc->objectOfTriangle(); if (!v.empty()) memcpy(objectOf, v.data(), v.size() * 4); }
+    if (names) { if (cap < joined.size() + 1) throw std::runtime_error("fh_scene_objects: buffer too small"); memcpy(names, joined.c_str(), joined.size() + 1); }
+    FH_CATCH
+}
 // the grid of one wide node from its ns child boxes (cmin / cmax: ns x 3 floats): which = 0 build_wide's quantiser (long double), 1 the refit's
 // (fp64 with error-free differences, csrc/flx_refit.h).  out12 = {o.xyz, s.xyz (float bits), qlo.xyz, qhi.xyz}
 int fh_wide_quantise(int which, const float *cmin, const float *cmax, int ns, uint32_t *out12)
@@ -411,6 +433,15 @@ int fh_tracer_update_geometry_subset(void *t, const void *tris, const uint32_t *
     FH_TRY
     ((Tracer *)t)->updateGeometry(std::vector<uint32_t>(indices, indices + count), std::vector<flx_triangle>((const flx_triangle *)tris, (const flx_triangle *)tris + count));
     FH_CATCH
+}
+int fh_tracer_define_objects(void *t, const uint32_t *objectOf, uint64_t ntris, uint32_t nobjects)
+{
+    FH_TRY ((Tracer *)t)->defineObjects(std::vector<uint32_t>(objectOf, objectOf + (objectOf ? ntris : 0)), nobjects); FH_CATCH
+}
+int fh_tracer_define_scene_objects(void *t, uint32_t *nobjects) { FH_TRY ((Tracer *)t)->defineObjects(); if (nobjects) *nobjects = ((Tracer *)t)->numObjects(); FH_CATCH }
+int fh_tracer_pose_objects(void *t, const uint32_t *ids, const float *xforms12, uint32_t count)
+{
+    FH_TRY ((Tracer *)t)->poseObjects(std::vector<uint32_t>(ids, ids + (ids ? count : 0)), std::vector<float>(xforms12, xforms12 + (xforms12 ? 12 * (size_t)count : 0))); FH_CATCH
 }
 int fh_tracer_get_triangles(void *t, void *out, uint64_t capTris, uint64_t *ntris)
 {

@@ -194,6 +194,17 @@ void Scene::loadObjWithMaterials(const std::string &filePath)
     std::map<std::string, int> mtlIndex;
     int matBase = (int)materials.size();   // == 1 for a fresh scene
     int curMat = -1;
+    // objects: every `o` statement (every `g` statement in a file without an `o`) names the object of the faces behind it; a name met again
+    // continues its object.  Both are recorded per triangle, which of the two counts is known at the end of the file.
+    std::vector<std::string> oNames, gNames;
+    std::vector<uint32_t> oOf(triangles.size(), FLX_SCENE_NO_OBJECT), gOf(triangles.size(), FLX_SCENE_NO_OBJECT);
+    uint32_t curO = FLX_SCENE_NO_OBJECT, curG = FLX_SCENE_NO_OBJECT;
+    auto named = [](std::vector<std::string> &names, const std::string &rest) -> uint32_t {
+        std::istringstream iss(rest); std::string nm; iss >> nm;
+        for (size_t i = 0; i < names.size(); i++) if (names[i] == nm) return (uint32_t)i;
+        names.push_back(nm);
+        return (uint32_t)names.size() - 1;
+    };
     std::string line;
     auto texLookup = [&](const std::string &nm) -> int {
         if (nm.empty()) return -1;
@@ -230,8 +241,11 @@ void Scene::loadObjWithMaterials(const std::string &filePath)
                 }
                 if (!allN) n[0] = n[1] = n[2] = normalize(cross(p[1] - p[0], p[2] - p[0]));
                 triangles.push_back(makeTri(p[0], p[1], p[2], n[0], n[1], n[2], t[0], t[1], t[2], curMat + 1 == 0 ? 0 : matBase + curMat));
+                oOf.push_back(curO); gOf.push_back(curG);
             }
         }
+        else if (s[0] == 'o' && (s[1] == ' ' || s[1] == '\t')) curO = named(oNames, line.substr(2));
+        else if (s[0] == 'g' && (s[1] == ' ' || s[1] == '\t')) curG = named(gNames, line.substr(2));
         else if (line.compare(0, 6, "usemtl") == 0) {
             std::istringstream iss(line.substr(6)); std::string nm; iss >> nm;
             auto it = mtlIndex.find(nm);
@@ -247,6 +261,15 @@ void Scene::loadObjWithMaterials(const std::string &filePath)
             }
         }
     }
+    objectOf.swap(oNames.empty() ? gOf : oOf);
+    objectNameList.swap(oNames.empty() ? gNames : oNames);
+}
+
+std::vector<uint32_t> Scene::objectOfTriangle() const
+{
+    std::vector<uint32_t> v = objectOf;
+    v.resize(triangles.size(), FLX_SCENE_NO_OBJECT);      // (triangles of a loader that knows no objects)
+    return v;
 }
 
 void Scene::packTextures(std::vector<flx_texdesc> &descs, std::vector<uint8_t> &blob) const

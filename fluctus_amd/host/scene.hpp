@@ -14,6 +14,8 @@
 
 namespace fluctus {
 
+#define FLX_SCENE_NO_OBJECT 0xFFFFFFFFu     // include/fluctus_hip.h: FLX_NO_OBJECT
+
 struct Texture {            // RGBA8, lower-left origin (reference: src/texture.cpp:16-41)
     std::string name;
     uint32_t width = 0, height = 0;
@@ -41,6 +43,11 @@ public:
     // file (PNG / JPEG); -1 when missing or undecodable
     int tryImportTexture(const std::string &path, const std::string &name);
     flx_vec3 getWorldUp() const { return worldUp; }
+    // OBJ ingest: the object of every triangle -- an index into objectNames(), from the file's `o` statements (its `g` statements where it has
+    // no `o`), FLX_SCENE_NO_OBJECT for a face in front of the first one and for every triangle of the other loaders.  What
+    // Tracer::defineObjects() hands to flx_objects_define.
+    std::vector<uint32_t> objectOfTriangle() const;
+    const std::vector<std::string> &objectNames() const { return objectNameList; }
     int addMaterial(const flx_material &m) { materials.push_back(m); materialTypes |= (uint32_t)m.type; return (int)materials.size() - 1; }
 
     // packTextures (reference: src/clcontext.cpp:570-611): one byte blob + descriptors
@@ -53,6 +60,8 @@ private:
     std::vector<flx_material> materials;
     std::vector<Texture> textures;
     uint32_t materialTypes = 0;
+    std::vector<uint32_t> objectOf;
+    std::vector<std::string> objectNameList;
     flx_vec3 worldUp {0.0f, 1.0f, 0.0f, 0.0f};          // reference: Scene::worldUp, set by the PBRT path from the camera frame
 };
 

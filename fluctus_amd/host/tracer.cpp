@@ -1,5 +1,6 @@
 // tracer.cpp -- see tracer.hpp.
 #include "tracer.hpp"
+#include "../csrc/flx_pose.h"     // the pose arithmetic and the member compaction: what the kernels and flx_objects_define run
 #include <chrono>
 #include <sstream>
 #include <fstream>
@@ -85,6 +86,7 @@ void Tracer::init(int width, int height, const std::string &sceneFile)
 {
     job.discard();                                           // a rebuild in flight belongs to the scene that goes away (joins the worker)
     movedSinceSnapshot = false; haveBaseline = false; lastRatio = std::nan("");
+    nObjects = 0; objMemberTri.clear(); objMemberObj.clear(); objRest.clear();     // (the ranks drop theirs with the upload below)
     resetParams(width, height);
     scene.reset(new Scene());
     sceneName = sceneFile;
@@ -148,6 +150,58 @@ void Tracer::updateGeometry(const std::vector<uint32_t> &indices, const std::vec
     scene->getTriangles().swap(all);
     afterMove();
 }
+// Objects moved by their transforms: updateGeometry(indices, tris) with the triangles made where they are needed -- on every rank
+// by flx_objects_pose, here by the same csrc/flx_pose.h function for the host tree and the scene's copy.
+void Tracer::defineObjects(const std::vector<uint32_t> &objectOfTriangle, uint32_t nobjects)
+{
+    if (!scene || !bvh) throw std::runtime_error("Tracer::defineObjects: no scene (init first)");
+    const std::vector<flx_triangle> &tris = scene->getTriangles();
+    std::vector<uint32_t> counts(nobjects), tri, obj;
+    std::vector<flx_triangle> rest;
+    if (nobjects) {
+        if (objectOfTriangle.size() != tris.size()) throw std::runtime_error("Tracer::defineObjects: one object id per triangle of the scene");
+        size_t bad = 0;
+        const size_t members = flx::ps_count_members(objectOfTriangle.data(), tris.size(), nobjects, counts.data(), &bad);
+        if (members == (size_t)-1) throw std::runtime_error("Tracer::defineObjects: triangle " + std::to_string(bad) + " has an object id that is neither below the object count nor FLX_NO_OBJECT");
+        tri.resize(members); obj.resize(members); rest.resize(members);
+        flx::ps_compact_members(tris.data(), objectOfTriangle.data(), tris.size(), tri.data(), obj.data(), rest.data());
+    }
+    for (auto *c : ranks()) c->defineObjects(nobjects ? tris : std::vector<flx_triangle>(), nobjects ? objectOfTriangle : std::vector<uint32_t>(), nobjects);
+    nObjects = nobjects; objMemberTri.swap(tri); objMemberObj.swap(obj); objRest.swap(rest);
+}
+void Tracer::defineObjects()
+{
+    if (!scene) throw std::runtime_error("Tracer::defineObjects: no scene (init first)");
+    defineObjects(scene->objectOfTriangle(), (uint32_t)scene->objectNames().size());
+}
+void Tracer::defineObjectsOnRanks(const std::vector<flx_triangle> &tris)
+{
+    if (!nObjects) return;
+    std::vector<flx_triangle> rest = tris;
+    std::vector<uint32_t> objectOf(tris.size(), FLX_NO_OBJECT);
+    for (size_t k = 0; k < objMemberTri.size(); k++) { rest[objMemberTri[k]] = objRest[k]; objectOf[objMemberTri[k]] = objMemberObj[k]; }
+    for (auto *c : ranks()) c->defineObjects(rest, objectOf, nObjects);
+}
+void Tracer::poseObjects(const std::vector<uint32_t> &ids, const std::vector<float> &xforms12)
+{
+    if (!scene || !bvh) throw std::runtime_error("Tracer::poseObjects: no scene (init first)");
+    if (!nObjects) throw std::runtime_error("Tracer::poseObjects: no objects are defined (defineObjects)");
+    if (rebuildMode != RebuildOff) adoptFinishedRebuild();
+    for (auto *c : ranks()) c->poseObjects(ids, xforms12);    // refused (a bad list or matrix, a vertex out of range): throws, and everything is still the old geometry's
+    std::vector<uint32_t> slot(nObjects, FLX_NO_OBJECT);     // (the device has checked the list: ascending, in range)
+    for (size_t k = 0; k < ids.size(); k++) slot[ids[k]] = (uint32_t)k;
+    std::vector<flx_triangle> all = scene->getTriangles();
+    std::vector<uint32_t> indices;
+    for (size_t k = 0; k < objMemberTri.size(); k++) {
+        const uint32_t s = slot[objMemberObj[k]];
+        if (s == FLX_NO_OBJECT) continue;
+        flx::ps_pose_triangles(xforms12.data() + 12 * (size_t)s, &objRest[k], &all[objMemberTri[k]], 1);
+        indices.push_back(objMemberTri[k]);
+    }
+    bvh->refitSubset(all, indices);
+    scene->getTriangles().swap(all);
+    afterMove();
+}
 // what follows every move of the triangles: the resets of geometryChanged, then the rebuild policy on the trees as they stand now
 void Tracer::afterMove()
 {
@@ -199,6 +253,7 @@ void Tracer::uploadTopology(BVH *tree, const std::vector<flx_triangle> &tris)
         c->uploadSceneData(tree, scene.get(), tris);
         c->setOption("fuse_set", fuseSet); c->setOption("ext_order", extOrder);
     }
+    defineObjectsOnRanks(tris);                              // the upload has dropped the ranks' objects; the rest pose survives a rebuild
     baselineCost = wideCost(); haveBaseline = true;          // before any refit: the ratio never hides the drift since the snapshot
     rebuilds++;
 }

@@ -38,6 +38,19 @@ public:
     // a background tree that finishes later is refitted to the full current triangle set.  A refused call (bad list or triangle) throws and
     // leaves the old geometry in place.
     void updateGeometry(const std::vector<uint32_t> &indices, const std::vector<flx_triangle> &tris);
+    // Move OBJECTS by their transforms.  defineObjects: objectOfTriangle[i] < nobjects is the object of triangle i,
+    // FLX_NO_OBJECT a triangle that never moves; the REST pose is the scene's triangles at this moment (the Tracer keeps the members' rest
+    // triangles; every rank gets the definition, flx_objects_define).  nobjects == 0 drops the definition, and so does init().  Without
+    // arguments: the objects the OBJ loader found (Scene::objectOfTriangle / objectNames).
+    // poseObjects: xforms12[12 k ..] is the 3 x 4 row-major ABSOLUTE rest -> world transform of object ids[k] (strictly ascending); objects not
+    // listed keep their pose.  Every rank poses the triangles on the device (flx_objects_pose: 48 bytes per object cross the bus); the host's
+    // triangle copy is posed with the same function (csrc/flx_pose.h) and the host tree refitted (BVH::refitSubset) -- worldRadius, the rebuild
+    // policy's snapshots and refits need it.  Otherwise updateGeometry(indices, tris): the rebuild policy takes part unchanged, and the rest pose
+    // survives a rebuild (the ranks are given the definition again behind every topology upload).  A refused call throws and leaves everything as it was.
+    void defineObjects(const std::vector<uint32_t> &objectOfTriangle, uint32_t nobjects);
+    void defineObjects();
+    void poseObjects(const std::vector<uint32_t> &ids, const std::vector<float> &xforms12);
+    uint32_t numObjects() const { return nObjects; }
     // Rebuild policy, default Off: updateGeometry only refits, exactly as described above.  Otherwise every updateGeometry
     // reads the root rank's flx_tree_cost after its refit and forms  ratio = cost of the 4-wide tree now / the same right after the last topology
     // upload  (flxTreeCostValue: (S_node + S_tri) / A_root).  When ratio > threshold and no rebuild is in flight:
@@ -149,6 +162,11 @@ private:
     uint32_t rebuilds = 0;
     bool movedSinceSnapshot = false;                                              // an updateGeometry happened since the job in flight took its snapshot
     RebuildJob job;
+    // objects (defineObjects): per member -- a triangle that belongs to an object, ascending -- its triangle, its object and its rest triangle
+    uint32_t nObjects = 0;
+    std::vector<uint32_t> objMemberTri, objMemberObj;
+    std::vector<flx_triangle> objRest;
+    void defineObjectsOnRanks(const std::vector<flx_triangle> &tris);             // flx_objects_define on every rank: `tris` with the members' rest triangles put in
     double wideCost();                                                            // flxTreeCostValue of the root rank's 4-wide tree now
     void uploadTopology(BVH *tree, const std::vector<flx_triangle> &tris);        // every rank; keeps the first upload's option choices; re-reads the baseline
     void refitAll(const std::vector<flx_triangle> &tris);                         // every rank + the host tree + the scene's triangles

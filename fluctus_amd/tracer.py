@@ -69,6 +69,28 @@ class Tracer:
             raise ValueError("update_geometry_subset: as many triangles as indices")
         host._chk(self.L.fh_tracer_update_geometry_subset(self.h, t.ctypes.data_as(C.c_void_p), i.ctypes.data_as(C.c_void_p), C.c_uint64(i.size)))
 
+    def define_objects(self, object_of_triangle=None, nobjects=None):
+        """Tracer::defineObjects (DESIGN.md 4.10.3): object_of_triangle[i] < nobjects is the object of triangle i, device.NO_OBJECT a triangle that
+        never moves; the rest pose is the scene's triangles at this moment.  Without arguments: the objects the OBJ loader found (`o`
+        statements, `g` where a file has none).  nobjects = 0 drops the definition.  Returns the number of objects."""
+        if object_of_triangle is None:
+            n = C.c_uint32()
+            host._chk(self.L.fh_tracer_define_scene_objects(self.h, C.byref(n)))
+            return int(n.value)
+        o = np.ascontiguousarray(object_of_triangle, np.uint32).reshape(-1)
+        host._chk(self.L.fh_tracer_define_objects(self.h, host._p(o), C.c_uint64(o.size), C.c_uint32(int(nobjects))))
+        return int(nobjects)
+
+    def pose_objects(self, ids, xforms):
+        """Tracer::poseObjects: xforms[k] (3 x 4, row-major [M | t]) is the ABSOLUTE rest -> world transform of object ids[k] (strictly
+        ascending); objects not listed keep their pose.  Every rank poses the triangles on the device and refits only the boxes above them;
+        the host tree and the scene's triangles follow with the same arithmetic.  The rebuild policy applies as in update_geometry."""
+        i = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        x = np.ascontiguousarray(xforms, np.float32).reshape(-1)
+        if x.size != 12 * i.size:
+            raise ValueError("pose_objects: one 3 x 4 matrix per listed object")
+        host._chk(self.L.fh_tracer_pose_objects(self.h, host._p(i), host._p(x), C.c_uint32(i.size)))
+
     REBUILD_MODES = {"off": 0, "blocking": 1, "background": 2}
 
     def set_rebuild_policy(self, mode, threshold=None):

@@ -71,6 +71,30 @@ int flx_update_triangles(flx_ctx *ctx, const void *tris160, size_t ntris, int sr
  * null while count > 0, indices is not strictly ascending (duplicates included) or holds an index outside the uploaded triangles, a position
  * is not finite or beyond +-2^62, or a matId is outside the uploaded materials.  count == 0 is accepted and changes no byte of any tree. */
 int flx_update_triangles_subset(flx_ctx *ctx, const void *tris160, const uint32_t *indices, size_t count, int src_on_device);
+/* Moving OBJECTS by their transforms (csrc/pose.hip, csrc/flx_pose.h).  flx_objects_define, once per upload: host pointers;
+ * tris160_rest are the ntris wire triangles of the REST pose (ntris must be the uploaded count), object_of_triangle[i] < nobjects is the object
+ * triangle i belongs to, FLX_NO_OBJECT a triangle that never moves; an object without a triangle is legal.  The members and their rest triangles
+ * are kept on the device.  Blocking; changes no byte of any tree; replaces an earlier definition; nobjects == 0 drops it, and so does
+ * flx_upload_scene.  Fails -- and keeps the earlier definition -- when no scene is uploaded, ntris differs from the uploaded count, a pointer is
+ * null or an id is neither < nobjects nor FLX_NO_OBJECT.
+ * flx_objects_pose: xforms12 + 12 k is the 3 x 4 row-major affine transform [M | t] of object object_ids[k] (host pointers, ids strictly
+ * ascending and < nobjects) -- the ABSOLUTE rest -> world transform, not an increment: a pose is computed from the rest triangles every time, so
+ * nothing drifts and posing by Y after X gives what Y alone gives.  Objects not listed keep the pose they have.  Positions go through [M | t],
+ * normals through the cofactor matrix of M (turned round when det M < 0) and are renormalised; texcoords, matId and every spare word are the rest
+ * triangle's (the arithmetic, operation by operation: csrc/flx_pose.h).  The triangles are produced on the device -- 48 bytes per object cross
+ * the bus, not 160 per triangle -- and handed to flx_update_triangles_subset as a device source, whose boundary this call has word for word:
+ * deferred and fused launches run against the OLD scene first, the one small blocking read of the validation refuses a posed vertex that is not
+ * finite or beyond +-2^62 before anything is overwritten, the adaptive list and the reprojection history are dropped, "wide_far" is re-derived;
+ * timed under FLX_K_REFIT (two spans: the pose kernels, the refit).  The identity transform gives back the rest triangles (csrc/flx_pose.h says
+ * exactly when bit for bit) but does not re-clip a leaf an earlier pose has unclipped.  count == 0, or a list of objects without triangles,
+ * changes no byte.  Fails -- leaving trees and every object's pose as they were -- when no objects are defined, an id is out of range or the ids
+ * are not strictly ascending, a matrix entry is not finite, or the fp32 determinant of M (csrc/flx_pose.h) is zero or not finite.
+ * flx_objects_read: test hook, blocking.  *out_nobjects, and where not NULL out_counts[nobjects] = the triangles of each object and out_members =
+ * the device's list of all objects' triangles, ascending (room for the uploaded triangle count); fails when no objects are defined. */
+#define FLX_NO_OBJECT 0xFFFFFFFFu
+int flx_objects_define(flx_ctx *ctx, const void *tris160_rest, size_t ntris, const uint32_t *object_of_triangle, uint32_t nobjects);
+int flx_objects_pose(flx_ctx *ctx, const uint32_t *object_ids, const float *xforms12, uint32_t count);
+int flx_objects_read(flx_ctx *ctx, uint32_t *out_counts, uint32_t *out_nobjects, uint32_t *out_members);
 /* test hook, blocking: one device array of the uploaded scene as it is now.  which = 0 the binary tree's 64-byte inner-node records, 1 the
  * 48-byte leaf triangle records (index-list order), 2 the 64-byte shading records, 3 the 64-byte nodes of the 4-wide tree, 4 its leaf data
  * (16-byte units).  *needed = the array's size in bytes; out NULL only reports it, otherwise bytes must be at least that. */
@@ -282,7 +306,7 @@ enum { FLX_K_RESET = 0, FLX_K_RAYGEN = 1, FLX_K_EXTEND = 2, FLX_K_SHADOW = 3, FL
        FLX_K_DENOISE = 9,      /* the whole of one flx_denoise or flx_denoise_variance_guided */
        FLX_K_GBUFFER = 10,     /* flx_gbuffer */
        FLX_K_REPROJECT = 11,   /* flx_reproject */
-       FLX_K_REFIT = 12,       /* the kernels of one flx_update_triangles */
+       FLX_K_REFIT = 12,       /* the kernels of one flx_update_triangles / _subset; flx_objects_pose adds its pose kernels as a span of their own */
        FLX_K_TREE_COST = 13,   /* the kernels of one flx_tree_cost */
        FLX_K_COUNT = 14 };
 /* on: 0 off | 1 time every kernel | 2 time only the two trace kernels (+ their span), as the reference does | 3 only the
