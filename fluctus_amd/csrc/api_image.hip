@@ -3,7 +3,7 @@
 #include "flx_ctx.h"
 #include "flx_denoise.h"
 #include "flx_denoise_vg.h"
-#include "flx_reproject.h"
+#include "flx_reproject_motion.h"
 #include "flx_adaptive.h"
 #include <cstring>
 
@@ -72,19 +72,24 @@ static int temporalReady(flx_ctx *c, const char *fn)
 }
 static int gbufferSlots(flx_ctx *c)
 {
-    if (c->temporal.gb[0]) return 0;
     const size_t n = (size_t)c->fr.localPixels * 2;
-    if (dalloc(c, c->temporal.allocs, &c->temporal.gb[0], n) || dalloc(c, c->temporal.allocs, &c->temporal.gb[1], n)) { c->temporal.release(); return 1; }
+    if (!c->temporal.gb[0] && (dalloc(c, c->temporal.allocs, &c->temporal.gb[0], n) || dalloc(c, c->temporal.allocs, &c->temporal.gb[1], n))) { c->temporal.release(); return 1; }
+    // option "motion_history": one object id per pixel beside each slot; off: nothing is allocated
+    if (c->motionHistory && !c->temporal.objPlane[0] &&
+        (dalloc(c, c->temporal.allocs, &c->temporal.objPlane[0], n / 2) || dalloc(c, c->temporal.allocs, &c->temporal.objPlane[1], n / 2))) { c->temporal.release(); return 1; }
     return 0;
 }
 int flx_gbuffer(flx_ctx *c)
 {
     READY(c, CALL_OBSERVE);
-    if (temporalReady(c, "flx_gbuffer") || gbufferSlots(c)) return 1;
+    if (temporalReady(c, "flx_gbuffer") || gbufferSlots(c) || motionTables(c)) return 1;
+    const bool obj = c->motionHistory && c->ob.have;      // the object plane is written only while the option is on and objects are defined
     { ScopedTimer t(c, FLX_K_GBUFFER);
-      launch_gbuffer(c->stream, c->sc, c->params, c->spill, c->numTasks, (c->extendTree == 4 && c->wideOK) ? 4 : 2, c->temporal.gb[0], c->fr.localPixels); }
+      launch_gbuffer(c->stream, c->sc, c->params, c->spill, c->numTasks, (c->extendTree == 4 && c->wideOK) ? 4 : 2, c->temporal.gb[0], c->fr.localPixels,
+                     obj ? c->temporal.objPlane[0] : nullptr, obj ? c->ob.objectOfTri : nullptr); }
     LAUNCHED(c);
     c->temporal.gbCam[0] = c->params.camera; c->temporal.gbW[0] = c->params.width; c->temporal.gbH[0] = c->params.height; c->temporal.gbTraced[0] = true;
+    c->temporal.objValid[0] = obj;
     return 0;
 }
 int flx_history_capture(flx_ctx *c)
@@ -104,6 +109,9 @@ int flx_history_capture(flx_ctx *c)
     c->temporal.histHasMom = withMom;
     if (c->temporal.histHasMom) HIPCHK(c, hipMemcpyAsync(c->temporal.histMomBuf, c->fr.moments, n * 16, hipMemcpyDeviceToDevice, c->stream));
     std::swap(c->temporal.gb[0], c->temporal.gb[1]);
+    std::swap(c->temporal.objPlane[0], c->temporal.objPlane[1]);
+    c->temporal.objValid[1] = c->temporal.objValid[0]; c->temporal.objValid[0] = false;
+    c->ob.xCap = c->ob.xNow; c->ob.knownCap = c->ob.known;      // every object's pose under this history (flx_reproject_motion.h: X_cap)
     c->temporal.gbCam[1] = c->temporal.gbCam[0]; c->temporal.gbW[1] = c->temporal.gbW[0]; c->temporal.gbH[1] = c->temporal.gbH[0]; c->temporal.gbTraced[1] = true;
     c->temporal.gbTraced[0] = false;
     c->temporal.histHave = true;
@@ -124,9 +132,26 @@ int flx_reproject(flx_ctx *c, const flx_reproject_params *pp)
     const flx_camera &pc = c->temporal.gbCam[1];
     const rp_view vw = rp_make_view(mk3(pc.pos.x, pc.pos.y, pc.pos.z), mk3(pc.dir.x, pc.dir.y, pc.dir.z), mk3(pc.up.x, pc.up.y, pc.up.z), mk3(pc.right.x, pc.right.y, pc.right.z), pc.fov, c->temporal.gbCam[0].fov, (int)c->params.width, (int)c->params.height);
     const bool mom = c->moments && c->fr.moments && c->temporal.histHasMom;
+    // objects posed since the capture (only flx_objects_pose under "motion_history" keeps a history across a move of triangles): the motion-aware
+    // kernel with the table of flx_reproject_motion.h, nobjects x 64 bytes uploaded on the stream; no object moved: k_reproject as ever
+    flx_ctx::Objects &ob = c->ob;
+    bool moved = false;
+    std::vector<rm_row> table;
+    if (ob.have && ob.t.nobjects) {
+        table.resize((size_t)ob.t.nobjects * FLX_RM_ROWS);
+        moved = rm_make_table(ob.t.nobjects, ob.xCap.data(), ob.knownCap.data(), ob.xNow.data(), ob.known.data(), table.data());
+    }
+    if (moved) {
+        NEED(c, c->motionHistory && ob.motion && c->temporal.objValid[0] && c->temporal.objValid[1],
+             "flx_reproject: objects were posed since the capture: needs option \"motion_history\" on and both G-buffers traced with it (flx_gbuffer)");
+        memcpy(ob.motionPinned, table.data(), table.size() * sizeof(rm_row));
+        HIPCHK(c, hipMemcpyAsync(ob.motion, ob.motionPinned, table.size() * sizeof(rm_row), hipMemcpyHostToDevice, c->stream));
+    }
     { ScopedTimer t(c, FLX_K_REPROJECT);
-      launch_reproject(c->stream, vw, rp, c->temporal.gb[0], c->temporal.gb[1], c->temporal.hist, c->temporal.histMomBuf, reinterpret_cast<float4 *>(c->fr.pixels),
-                       mom ? reinterpret_cast<float4 *>(c->fr.moments) : nullptr); }
+      float4 *px = reinterpret_cast<float4 *>(c->fr.pixels), *pm = mom ? reinterpret_cast<float4 *>(c->fr.moments) : nullptr;
+      if (moved) launch_reproject_motion(c->stream, vw, rp, c->temporal.gb[0], c->temporal.gb[1], c->temporal.hist, c->temporal.histMomBuf, px, pm,
+                                         c->temporal.objPlane[0], c->temporal.objPlane[1], ob.motion, ob.t.nobjects);
+      else launch_reproject(c->stream, vw, rp, c->temporal.gb[0], c->temporal.gb[1], c->temporal.hist, c->temporal.histMomBuf, px, pm); }
     LAUNCHED(c);
     return 0;
 }
@@ -154,6 +179,42 @@ int flx_gbuffer_write(flx_ctx *c, int slot, const float *in8, const void *camera
     HIPCHK(c, hipStreamSynchronize(c->stream));
     memcpy(&c->temporal.gbCam[slot], camera80, sizeof(flx_camera));
     c->temporal.gbW[slot] = c->params.width; c->temporal.gbH[slot] = c->params.height; c->temporal.gbTraced[slot] = true;
+    c->temporal.objValid[slot] = false;
+    if (c->motionHistory) {                               // a written G-buffer shows no object until flx_gbuffer_objects_write says otherwise
+        HIPCHK(c, hipMemsetAsync(c->temporal.objPlane[slot], 0xFF, (size_t)c->fr.localPixels * 4, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->temporal.objValid[slot] = true;
+    }
+    return 0;
+}
+// ... and of the slots' object planes (option "motion_history"): one uint32 per pixel, FLX_NO_OBJECT or an object id (an id that is not below
+// the object count is read as FLX_NO_OBJECT, csrc/flx_reproject_motion.h).  Blocking.
+int flx_gbuffer_objects_read(flx_ctx *c, int slot, uint32_t *out)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, slot == 0 || slot == 1, "flx_gbuffer_objects_read: slot must be 0 (current) or 1 (previous)");
+    NEED(c, out, "flx_gbuffer_objects_read: null output");
+    NEED(c, c->temporal.objPlane[slot] && c->temporal.gbTraced[slot] && c->temporal.objValid[slot],
+         "flx_gbuffer_objects_read: the slot holds no object plane (option \"motion_history\" on, objects defined, flx_gbuffer)");
+    HIPCHK(c, hipMemcpyAsync(out, c->temporal.objPlane[slot], (size_t)c->temporal.gbW[slot] * c->temporal.gbH[slot] * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+int flx_gbuffer_objects_write(flx_ctx *c, int slot, const uint32_t *in)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, slot == 0 || slot == 1, "flx_gbuffer_objects_write: slot must be 0 (current) or 1 (previous)");
+    NEED(c, in, "flx_gbuffer_objects_write: null object ids");
+    NEED(c, c->motionHistory, "flx_gbuffer_objects_write: needs flx_set_option(ctx, \"motion_history\", 1)");
+    if (temporalReady(c, "flx_gbuffer_objects_write")) return 1;
+    NEED(c, c->temporal.gb[slot] && c->temporal.gbTraced[slot] && c->temporal.gbW[slot] == c->params.width && c->temporal.gbH[slot] == c->params.height,
+         "flx_gbuffer_objects_write: the slot holds no G-buffer of the current size (flx_gbuffer or flx_gbuffer_write first)");
+    if (gbufferSlots(c)) return 1;
+    HIPCHK(c, hipMemcpyAsync(c->temporal.objPlane[slot], in, (size_t)c->fr.localPixels * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->temporal.objValid[slot] = true;
     return 0;
 }
 

@@ -247,6 +247,8 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     c->sceneAllocs.swap(fresh);
     c->rf = std::move(rf);
     c->ob.release();                                      // objects are defined over the triangles of one upload (flx_objects_define)
+    c->temporal.objValid[0] = c->temporal.objValid[1] = false;      // the object planes name that definition's objects ...
+    if (c->motionHistory) c->temporal.dropHistory();      // ... and with "motion_history" on a captured history belongs to the scene it was rendered from
     if (newSpill) { freeAll(c->spillAllocs); c->spillAllocs.swap(freshSpill); c->spill = sp1; c->spill2 = sp2; c->spillLevels = spillLevels; }
     c->sc.bnodes = dB; c->sc.trirecs = dT; c->sc.shade = dS; c->sc.tris = dTri; c->sc.materials = dM; c->sc.texdesc = dD; c->sc.texdata = dX;
     c->sc.rootRef = 0;

@@ -143,8 +143,13 @@ struct flx_ctx {
         std::vector<void *> allocs;
         float4 *gb[2] = {nullptr, nullptr}; flx_camera gbCam[2] = {}; uint32_t gbW[2] = {0, 0}, gbH[2] = {0, 0}; bool gbTraced[2] = {false, false};
         float4 *hist = nullptr, *histMomBuf = nullptr; bool histHave = false, histHasMom = false;
+        // option "motion_history" (DESIGN.md 4.3.4): one object id per pixel beside each slot, swapped with the slots; allocated by the first
+        // flx_gbuffer / flx_gbuffer_write while the option is on.  objValid: the plane belongs to the slot's G-buffer and to the current definition
+        uint32_t *objPlane[2] = {nullptr, nullptr}; bool objValid[2] = {false, false};
+        void dropHistory() { gbTraced[0] = gbTraced[1] = false; histHave = false; objValid[0] = objValid[1] = false; }
         void release() { freeAll(allocs); *this = Temporal(); }
     } temporal;
+    int motionHistory = 0;      // option "motion_history": flx_objects_pose keeps a captured history, flx_reproject follows the posed objects
     // the adaptive microkernel render (adaptive.hip): the list of active pixels the sample pass's four kernels run over while
     // `have` (`count` entries, ascending; 0 = the calls are no-ops); flag bytes, block counts and the list are allocated by the first
     // flx_mk_adaptive_update / flx_mk_active_write for `pix` pixels and freed with the framebuffers.  have false = every pixel.
@@ -162,7 +167,13 @@ struct flx_ctx {
         ObjectTables t;
         std::vector<uint32_t> counts;
         bool have = false;
-        void release() { freeAll(allocs); *this = Objects(); }
+        // every object's pose now and at the last flx_history_capture (12 floats each) with a `known` byte: unknown until the object has been
+        // posed since the definition -- the uploaded triangles need not be the rest pose.  Kept on the host whatever the options say.
+        std::vector<float> xNow, xCap; std::vector<uint8_t> known, knownCap;
+        // option "motion_history": the object of every triangle (FLX_NO_OBJECT: none) and the per-object motion table of flx_reproject_motion.h
+        // (four float4 per object) with its pinned staging copy; made by the first flx_gbuffer or flx_objects_pose that finds the option on
+        uint32_t *objectOfTri = nullptr; float4 *motion = nullptr, *motionPinned = nullptr;
+        void release() { freeAll(allocs); if (motionPinned) (void)hipHostFree(motionPinned); *this = Objects(); }
     } ob;
     int nodeLayout = 1;         // 1 = sibling-pair record numbering (see flx_upload_scene), 0 = DFS
     int numCUs = 256;
@@ -229,6 +240,7 @@ int enter(flx_ctx *c, Call call);                   // api_wavefront.hip: one st
 void flushExt(flx_ctx *c);                          // api_wavefront.hip: the lazy extension counter
 int fuseSetNow(const flx_ctx *c);                   // api_wavefront.hip: the BSDF set the fused pass inlines now (read-only options)
 float wideClampFor(float maxAbsCoord);              // api_refit.hip: the bound of |1 / dir| in the wide node test for a scene reaching this far (flx_trace4.h: WRay::setup)
+int motionTables(flx_ctx *c);                       // api_refit.hip: objectOfTri and the motion table, made once per definition while "motion_history" is on
 int wideFar(const flx_ctx *c);                      // api_refit.hip: 1 when sc.wideClamp is the far clamp (read-only option "wide_far")
 void pickSchedule(flx_ctx *c);                      // api.hip: the effective overlap / refill_shadow (options, flx_upload_scene)
 }

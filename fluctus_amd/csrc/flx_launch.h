@@ -45,6 +45,7 @@ struct ObjectTables {
 };
 uint32_t pose_blocks(uint32_t members);
 void launch_pose(hipStream_t, const ObjectTables &, uint32_t count);
+void launch_object_of_triangle(hipStream_t, const ObjectTables &, uint32_t *objectOfTri);     // the members' objects scattered into a table the caller has filled with FLX_NO_OBJECT
 void launch_block_scan(hipStream_t, uint32_t *blockCounts, uint32_t nb, uint32_t *total);      // adaptive.hip: in place, counts -> exclusive offsets
 size_t tree_cost_slab_doubles(const RefitTables &);
 double *launch_tree_cost(hipStream_t, const Scene &, const RefitTables &, double *);      // -> where the eight results land in the slab
@@ -89,8 +90,12 @@ void launch_deinterleave(hipStream_t, const float *, float *, uint32_t, uint32_t
 struct DnGuided; struct DnVg;     // the two filters of denoise.hip
 template <class F> void launch_denoise(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float,
                                        float, const flx_render_params &);
-void launch_gbuffer(hipStream_t, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, float4 *, uint32_t);
+// (the last two: the slot's object plane and the object of every triangle -- both null: no plane is written)
+void launch_gbuffer(hipStream_t, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, float4 *, uint32_t, uint32_t *, const uint32_t *);
 void launch_reproject(hipStream_t, const rp_view &, const rp_params &, const float4 *, const float4 *, const float4 *, const float4 *, float4 *, float4 *);
+// (... then the current and the previous object plane, the motion table and the object count)
+void launch_reproject_motion(hipStream_t, const rp_view &, const rp_params &, const float4 *, const float4 *, const float4 *, const float4 *, float4 *, float4 *,
+                             const uint32_t *, const uint32_t *, const float4 *, uint32_t);
 #ifdef FLX_LAB_RSTATS
 extern unsigned long long *g_lab_rstats;
 #endif

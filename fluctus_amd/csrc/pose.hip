@@ -59,6 +59,19 @@ __global__ __launch_bounds__(PS_BLOCK) void k_pose_write(ObjectTables ob)
     ob.outIdx[r] = ob.memberTri[gid];
 }
 
+// option "motion_history": objectOfTri[memberTri[k]] = memberObj[k] (the members are distinct triangles < the table's length: flx_objects_define)
+__global__ __launch_bounds__(PS_BLOCK) void k_object_of_triangle(const uint32_t *__restrict__ memberTri, const uint32_t *__restrict__ memberObj, uint32_t members,
+                                                                 uint32_t *__restrict__ objectOfTri)
+{
+    const uint32_t k = blockIdx.x * PS_BLOCK + threadIdx.x;
+    if (k < members) objectOfTri[memberTri[k]] = memberObj[k];
+}
+void launch_object_of_triangle(hipStream_t s, const ObjectTables &ob, uint32_t *objectOfTri)
+{
+    if (!ob.members) return;
+    hipLaunchKernelGGL(k_object_of_triangle, dim3((ob.members + PS_BLOCK - 1) / PS_BLOCK), dim3(PS_BLOCK), 0, s, ob.memberTri, ob.memberObj, ob.members, objectOfTri);
+}
+
 uint32_t pose_blocks(uint32_t members) { return (members + PS_BLOCK - 1) / PS_BLOCK; }
 
 // ob.ids / ob.xforms hold the call's list (count entries); ob.epoch is the call's.  Afterwards ob.out / ob.outIdx hold the posed triangles of

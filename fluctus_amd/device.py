@@ -25,7 +25,7 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_denoise_variance_guided", "flx_gbuffer", "flx_history_capture", "flx_reproject", "flx_gbuffer_read", "flx_gbuffer_write",
            "flx_mk_adaptive_update", "flx_mk_adaptive_clear", "flx_mk_active_read", "flx_mk_active_write",
            "flx_update_triangles", "flx_update_triangles_subset", "flx_tree_read", "flx_tree_cost",
-           "flx_objects_define", "flx_objects_pose", "flx_objects_read"]
+           "flx_objects_define", "flx_objects_pose", "flx_objects_read", "flx_gbuffer_objects_read", "flx_gbuffer_objects_write"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
 K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with HipContext.denoise_profile (not part of profile_get)
@@ -403,6 +403,19 @@ class HipContext:
         cam = np.frombuffer(np.asarray(camera).tobytes(), wire.CAMERA).copy()      # any 80-byte flx_camera record
         assert cam.size == 1
         self._chk(self.L.flx_gbuffer_write(self.h, int(slot), _p(g), _p(cam)))
+
+    # ... across a pose of objects: set_option("motion_history", 1) (include/fluctus_hip.h)
+    def gbuffer_objects_read(self, slot=0):
+        """test hook: (pixels,) uint32, the object id of every pixel of the slot's G-buffer (NO_OBJECT: a miss, the area light, no object)"""
+        out = np.empty(self.local_pixels(), np.uint32)
+        self._chk(self.L.flx_gbuffer_objects_read(self.h, int(slot), _p(out)))
+        return out
+
+    def gbuffer_objects_write(self, slot, objects):
+        """test hook: one uint32 per pixel into the object plane of slot 0 (current) or 1 (previous); after gbuffer_write, which fills it with NO_OBJECT"""
+        o = np.ascontiguousarray(objects, np.uint32).reshape(-1)
+        assert o.size == self.local_pixels(), (o.size, self.local_pixels())
+        self._chk(self.L.flx_gbuffer_objects_write(self.h, int(slot), _p(o)))
 
     def kernel_profile(self, kernel):
         """(milliseconds, launches) of one FLX_K_* id accumulated while profiling (level 1) since the last profile_reset; after finish()"""

@@ -498,6 +498,8 @@ int fh_tracer_set_denoiser_strength(void *t, float s) { FH_TRY ((Tracer *)t)->se
 int fh_tracer_set_denoiser_mode(void *t, int mode) { FH_TRY ((Tracer *)t)->setDenoiserMode((Tracer::DenoiserMode)mode); FH_CATCH }
 int fh_tracer_set_temporal_reprojection(void *t, int on) { FH_TRY ((Tracer *)t)->setTemporalReprojection(on != 0); FH_CATCH }
 int fh_tracer_get_temporal_reprojection(void *t) { return ((Tracer *)t)->getTemporalReprojection() ? 1 : 0; }
+int fh_tracer_set_motion_reprojection(void *t, int on) { FH_TRY ((Tracer *)t)->setMotionReprojection(on != 0); FH_CATCH }
+int fh_tracer_get_motion_reprojection(void *t) { return ((Tracer *)t)->getMotionReprojection() ? 1 : 0; }
 int fh_tracer_set_max_history(void *t, float n) { FH_TRY ((Tracer *)t)->setMaxHistory(n); FH_CATCH }
 int fh_tracer_toggle_renderer(void *t) { FH_TRY ((Tracer *)t)->toggleRenderer(); FH_CATCH }
 int fh_tracer_uses_wavefront(void *t) { return ((Tracer *)t)->usesWavefront() ? 1 : 0; }

@@ -168,6 +168,7 @@ void Tracer::defineObjects(const std::vector<uint32_t> &objectOfTriangle, uint32
     }
     for (auto *c : ranks()) c->defineObjects(nobjects ? tris : std::vector<flx_triangle>(), nobjects ? objectOfTriangle : std::vector<uint32_t>(), nobjects);
     nObjects = nobjects; objMemberTri.swap(tri); objMemberObj.swap(obj); objRest.swap(rest);
+    if (motionOn) dropHistory();                             // the G-buffer's object plane names the earlier definition's objects (the device has dropped its history too)
 }
 void Tracer::defineObjects()
 {
@@ -187,7 +188,18 @@ void Tracer::poseObjects(const std::vector<uint32_t> &ids, const std::vector<flo
     if (!scene || !bvh) throw std::runtime_error("Tracer::poseObjects: no scene (init first)");
     if (!nObjects) throw std::runtime_error("Tracer::poseObjects: no objects are defined (defineObjects)");
     if (rebuildMode != RebuildOff) adoptFinishedRebuild();
-    for (auto *c : ranks()) c->poseObjects(ids, xforms12);    // refused (a bad list or matrix, a vertex out of range): throws, and everything is still the old geometry's
+    // motion-aware reprojection: with a history by update()'s own conditions, capture it before the ranks are posed -- at most once
+    // per frame -- so that flx_objects_pose keeps it
+    const bool keep = motionOn && temporalOn && useWavefront && haveGbuffer && (poseHistory || framesSinceGbuffer > 0) && gbWidth == params.width &&
+                      gbHeight == params.height && onlyCameraChanged(true);
+    const bool capture = keep && !poseHistory;
+    if (capture) { clctx->historyCapture(); poseHistory = true; }
+    try {
+        for (auto *c : ranks()) c->poseObjects(ids, xforms12);    // refused (a bad list or matrix, a vertex out of range): throws, and everything is still the old geometry's
+    } catch (...) {
+        if (capture) paramsUpdatePending = true;             // the capture has handed the current slot over: the next update() traces it again and reprojects (nothing moved)
+        throw;
+    }
     std::vector<uint32_t> slot(nObjects, FLX_NO_OBJECT);     // (the device has checked the list: ascending, in range)
     for (size_t k = 0; k < ids.size(); k++) slot[ids[k]] = (uint32_t)k;
     std::vector<flx_triangle> all = scene->getTriangles();
@@ -200,7 +212,9 @@ void Tracer::poseObjects(const std::vector<uint32_t> &ids, const std::vector<flo
     }
     bvh->refitSubset(all, indices);
     scene->getTriangles().swap(all);
+    const uint32_t topologies = rebuilds;
     afterMove();
+    if (keep && rebuilds == topologies) { haveGbuffer = true; poseHistory = true; }      // (a rebuild inside afterMove re-defined the objects: the device dropped the history)
 }
 // what follows every move of the triangles: the resets of geometryChanged, then the rebuild policy on the trees as they stand now
 void Tracer::afterMove()
@@ -330,13 +344,24 @@ void Tracer::setTemporalReprojection(bool on)
 {
     if (on && !peers.empty()) throw std::runtime_error("setTemporalReprojection: temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
     temporalOn = on;
-    haveGbuffer = false; temporalFrames = 0;
+    dropHistory(); temporalFrames = 0;
+    if (!on && motionOn) setMotionReprojection(false);
+}
+void Tracer::setMotionReprojection(bool on)
+{
+    if (on && !peers.empty()) throw std::runtime_error("setMotionReprojection: temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
+    if (on && !temporalOn) throw std::runtime_error("setMotionReprojection: needs setTemporalReprojection(true)");
+    for (auto *c : ranks()) c->setOption("motion_history", on ? 1 : 0);
+    motionOn = on;
+    dropHistory();                                           // a G-buffer traced under the other setting has no object plane (or one nobody keeps up)
 }
 // everything of RenderParams that shapes the radiance of a point, i.e. all but the camera (bytes 96..175) and the post-process (exposure,
 // tmOperator: 176..183), equals what the G-buffer's frames were rendered with
-bool Tracer::onlyCameraChanged() const
+bool Tracer::onlyCameraChanged(bool posed) const
 {
-    const char *a = (const char *)&params, *b = (const char *)&gbParams;
+    RenderParams now = params;
+    if (posed) now.worldRadius = gbParams.worldRadius;
+    const char *a = (const char *)&now, *b = (const char *)&gbParams;
     return std::memcmp(a, b, offsetof(RenderParams, camera)) == 0 &&
            std::memcmp(a + offsetof(RenderParams, width), b + offsetof(RenderParams, width), sizeof(RenderParams) - offsetof(RenderParams, width)) == 0;
 }
@@ -485,8 +510,11 @@ void Tracer::update()
         const bool temporal = temporalOn && useWavefront;
         // a history exists: at least one frame rendered since the last G-buffer, at the same size (a resize frees the device's slots)
         // and with nothing but the camera changed since (lights, bounces, sampling switches: the kept radiance would be stale)
-        const bool history = temporal && haveGbuffer && framesSinceGbuffer > 0 && gbWidth == params.width && gbHeight == params.height && onlyCameraChanged();
-        if (history) clctx->historyCapture();                            // under the old camera's slot
+        // (poseObjects under motion-aware reprojection has captured it already: a camera change pending in the same frame shares that capture)
+        const bool history = temporal && haveGbuffer && (poseHistory || framesSinceGbuffer > 0) && gbWidth == params.width && gbHeight == params.height &&
+                             onlyCameraChanged(poseHistory);
+        if (history && !poseHistory) clctx->historyCapture();            // under the old camera's slot
+        poseHistory = false;
         for (auto *c : R) c->updateParams(params);
         paramsUpdatePending = false; iteration = 0;
         if (temporal) {

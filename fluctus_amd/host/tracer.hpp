@@ -116,8 +116,15 @@ public:
     void setTemporalReprojection(bool on);
     bool getTemporalReprojection() const { return temporalOn; }
     void setMaxHistory(float n);                                                  // flx_reproject's max_history (>= 1; default 32)
+    // Motion-aware reprojection, default off; needs setTemporalReprojection(true) and throws without it or on a multi-rank
+    // Tracer.  On: poseObjects on the WAVEFRONT integrator no longer throws the accumulation away -- it captures the history (at most once per
+    // frame, shared with a camera change pending in the same frame), poses, and arms the next update() to trace the G-buffer, run the reset
+    // sequence unchanged and reproject, each posed object's pixels looking their history up where the object was.  Everything else that changes
+    // the geometry restarts as ever: updateGeometry in either form, a rebuild the policy runs or adopts, the microkernel branch, renderSingle.
+    void setMotionReprojection(bool on);
+    bool getMotionReprojection() const { return motionOn; }
     float getMaxHistory() const { return maxHistory; }
-    void toggleRenderer() { useWavefront = !useWavefront; iteration = 0; haveGbuffer = false; }   // src/tracer.cpp:881-886 (no history across integrators)
+    void toggleRenderer() { useWavefront = !useWavefront; iteration = 0; dropHistory(); }   // src/tracer.cpp:881-886 (no history across integrators)
     void setOption(const std::string &name, int value) { for (auto *c : ranks()) c->setOption(name, value); }   // every rank (HipContext::setOption)
     bool usesWavefront() const { return useWavefront; }
     void saveImage(const std::string &filename) { clctx->saveImage(filename, params); }
@@ -187,8 +194,10 @@ private:
     // wherever parameters reach the device without flx_gbuffer (dropHistory)
     bool haveGbuffer = false;
     RenderParams gbParams {};
-    void dropHistory() { haveGbuffer = false; }
-    bool onlyCameraChanged() const;                                               // params against gbParams, the camera and the post-process aside
+    void dropHistory() { haveGbuffer = false; poseHistory = false; }
+    bool onlyCameraChanged(bool posed = false) const;                             // params against gbParams, the camera and the post-process aside (posed: and worldRadius, which a pose re-derives)
+    bool motionOn = false;
+    bool poseHistory = false;                                                     // poseObjects has captured the history of this frame: the next update() reprojects it
     uint32_t gbWidth = 0, gbHeight = 0;                                           // ... traced at this size
     uint32_t framesSinceGbuffer = 0;                                              // > 0: there is an accumulation worth capturing
     uint32_t temporalFrames = 0;                                                  // frames since the last discarded history (the denoiser schedule while temporalOn)

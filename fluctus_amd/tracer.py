@@ -215,6 +215,15 @@ class Tracer:
     def temporal_reprojection(self):
         return bool(self.L.fh_tracer_get_temporal_reprojection(self.h))
 
+    def set_motion_reprojection(self, on):
+        """Tracer::setMotionReprojection (default off; needs set_temporal_reprojection(True)): pose_objects on the wavefront integrator keeps the
+        accumulated image -- a posed object's pixels look their history up where the object was.  Single-GPU."""
+        host._chk(self.L.fh_tracer_set_motion_reprojection(self.h, int(bool(on))))
+
+    @property
+    def motion_reprojection(self):
+        return bool(self.L.fh_tracer_get_motion_reprojection(self.h))
+
     def set_max_history(self, n):
         """Tracer::setMaxHistory: the sample count a reprojected pixel may keep (flx_reproject's max_history, >= 1; default 32)"""
         host._chk(self.L.fh_tracer_set_max_history(self.h, C.c_float(float(n))))

@@ -84,7 +84,8 @@ int flx_update_triangles_subset(flx_ctx *ctx, const void *tris160, const uint32_
  * triangle's (the arithmetic, operation by operation: csrc/flx_pose.h).  The triangles are produced on the device -- 48 bytes per object cross
  * the bus, not 160 per triangle -- and handed to flx_update_triangles_subset as a device source, whose boundary this call has word for word:
  * deferred and fused launches run against the OLD scene first, the one small blocking read of the validation refuses a posed vertex that is not
- * finite or beyond +-2^62 before anything is overwritten, the adaptive list and the reprojection history are dropped, "wide_far" is re-derived;
+ * finite or beyond +-2^62 before anything is overwritten, the adaptive list and the reprojection history are dropped (the history is kept under
+ * option "motion_history", see flx_reproject), "wide_far" is re-derived;
  * timed under FLX_K_REFIT (two spans: the pose kernels, the refit).  The identity transform gives back the rest triangles (csrc/flx_pose.h says
  * exactly when bit for bit) but does not re-clip a leaf an earlier pose has unclipped.  count == 0, or a list of objects without triangles,
  * changes no byte.  Fails -- leaving trees and every object's pose as they were -- when no objects are defined, an id is out of range or the ids
@@ -224,6 +225,31 @@ int flx_history_capture(flx_ctx *ctx);
 int flx_reproject(flx_ctx *ctx, const flx_reproject_params *params);
 int flx_gbuffer_read(flx_ctx *ctx, int slot, float *out_8_floats_per_pixel, void *camera80);
 int flx_gbuffer_write(flx_ctx *ctx, int slot, const float *in_8_floats_per_pixel, const void *camera80);
+/* ---- ... across a pose of objects: flx_set_option(ctx, "motion_history", 1)  (csrc/flx_reproject_motion.h).  Off (the
+ * default) every call does what it does without the option.  On, with objects defined (flx_objects_define), the sequence is
+ *     ... render under pose A, camera A ...
+ *     flx_gbuffer; flx_history_capture         (the capture also notes every object's current pose)
+ *     flx_objects_pose(B)                      (keeps the PREVIOUS slot and the captured history; only the current slot becomes "not traced")
+ *     [flx_set_params(camera B)]               (camera and objects may move in the same frame)
+ *     flx_gbuffer; flx_wf_reset or flx_mk_reset (unchanged); flx_reproject; ... render on ...
+ * What the option changes:
+ * flx_gbuffer also writes one object id per pixel beside the slot (the object of the hit triangle; FLX_NO_OBJECT on a miss, on the implicit
+ * area-light quad and on a triangle of no object); G0 / G1 are the same bytes.  flx_history_capture swaps these planes with the slots.
+ * flx_objects_pose keeps a captured history whose G-buffer has such a plane; without one, and in flx_update_triangles /
+ * flx_update_triangles_subset always, the history is dropped as without the option.  flx_upload_scene and flx_objects_define drop it.
+ * flx_reproject (same signature, same parameters): where no object's pose differs from its pose at the capture it is the call above, bit for
+ * bit.  Otherwise a pixel of a posed object looks its history up where that surface point WAS: P' = D P, N' = the normal through D's
+ * cofactors, D = X_capture X_now^-1 (one 3 x 4 matrix per object, inverse and product in float64, rounded once), and a tap showing another
+ * object is refused when either of the two moved.  An object posed for the first time since its definition has no known pose at the capture
+ * (the uploaded triangles need not be the rest pose): its pixels get no history.  Per-triangle motion is not followed.  A moved object changes
+ * shadows and reflections on surfaces that did not move: their history is stale and decays only through max_history.
+ * The object of every triangle, the two planes and the per-object table are allocated by the first flx_gbuffer or flx_objects_pose that finds
+ * the option on and objects defined; turning the option off invalidates the planes.
+ * flx_gbuffer_objects_read / flx_gbuffer_objects_write: test hooks beside flx_gbuffer_read / _write, one uint32 per pixel, blocking.  The write
+ * needs the option on and the slot traced at the current size; while the option is on flx_gbuffer_write fills the slot's plane with
+ * FLX_NO_OBJECT, so a test writes G first and objects second.  An id that is not below the object count reads as FLX_NO_OBJECT. */
+int flx_gbuffer_objects_read(flx_ctx *ctx, int slot, uint32_t *out_1_uint32_per_pixel);
+int flx_gbuffer_objects_write(flx_ctx *ctx, int slot, const uint32_t *in_1_uint32_per_pixel);
 
 /* ---- microkernel integrator (the reference's second integrator).  One path per pixel (needs
  * num_tasks >= width*height to cover the image), `phase` state machine, exactly one sample per pixel per pass.
