@@ -230,7 +230,7 @@ int flx_set_params(flx_ctx *c, const void *p240)
     const uint32_t oldW = c->params.width, oldH = c->params.height;
     memcpy(&c->params, p240, sizeof(flx_render_params));   // kernels receive the struct by value at launch = in-order semantics
     NEED(c, c->params.width > 0 && c->params.height > 0, "flx_set_params: zero-sized framebuffer");
-    if (c->params.width != oldW || c->params.height != oldH) c->ad.have = false;      // the list of active pixels indexes the old image
+    if (c->params.width != oldW || c->params.height != oldH) c->ad.state.dropped();      // the list of active pixels indexes the old image
     c->haveParams = true;
     return allocFrame(c);
 }
@@ -240,7 +240,7 @@ int flx_set_partition(flx_ctx *c, uint32_t rank, uint32_t nranks)
     ENTER(c, CALL_OBSERVE);
     NEED(c, nranks >= 1 && rank < nranks, "flx_set_partition: bad rank");
     c->fr.rank = rank; c->fr.nranks = nranks;
-    c->ad.have = false;
+    c->ad.state.dropped();                               // the list of active pixels indexes the pixels of the old partition
     return c->haveParams ? allocFrame(c) : 0;
 }
 uint32_t flx_local_pixels(flx_ctx *c) { return c->fr.localPixels; }
@@ -371,13 +371,13 @@ int flx_set_option(flx_ctx *c, const char *name, int value)
     }
     if (name && strcmp(name, "moments") == 0 && (value == 0 || value == 1)) {
         ENTER(c, CALL_OBSERVE);
-        if (!value) c->ad.have = false;                    // the list of active pixels is derived from the moments
+        if (!value) c->ad.state.dropped();                   // the list of active pixels is derived from the moments
         if (c->moments != value) { c->moments = value; HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipStreamSynchronize(c->stream)); return allocMoments(c); }
         return 0;
     }
     if (name && strcmp(name, "motion_history") == 0 && (value == 0 || value == 1)) {
         ENTER(c, CALL_OBSERVE);
-        if (!value) c->temporal.objValid[0] = c->temporal.objValid[1] = false;      // planes not kept up while the option is off are nobody's
+        if (!value) c->temporal.state.motionHistoryOff();
         c->motionHistory = value;
         return 0;
     }

@@ -88,8 +88,7 @@ int flx_gbuffer(flx_ctx *c)
       launch_gbuffer(c->stream, c->sc, c->params, c->spill, c->numTasks, (c->extendTree == 4 && c->wideOK) ? 4 : 2, c->temporal.gb[0], c->fr.localPixels,
                      obj ? c->temporal.objPlane[0] : nullptr, obj ? c->ob.objectOfTri : nullptr); }
     LAUNCHED(c);
-    c->temporal.gbCam[0] = c->params.camera; c->temporal.gbW[0] = c->params.width; c->temporal.gbH[0] = c->params.height; c->temporal.gbTraced[0] = true;
-    c->temporal.objValid[0] = obj;
+    c->temporal.state.traced(c->params.camera, c->params.width, c->params.height, obj);
     return 0;
 }
 int flx_history_capture(flx_ctx *c)
@@ -97,8 +96,8 @@ int flx_history_capture(flx_ctx *c)
     ENTER(c, CALL_OBSERVE);
     HIPCHK(c, hipSetDevice(c->device));
     if (temporalReady(c, "flx_history_capture")) return 1;
-    NEED(c, c->temporal.gb[0] && c->temporal.gbTraced[0], "flx_history_capture: no G-buffer has been traced for the current slot (flx_gbuffer first)");
-    NEED(c, c->temporal.gbW[0] == c->params.width && c->temporal.gbH[0] == c->params.height, "flx_history_capture: the image size differs from the G-buffer's");
+    NEED(c, c->temporal.gb[0] && c->temporal.state.holds(0), "flx_history_capture: no G-buffer has been traced for the current slot (flx_gbuffer first)");
+    NEED(c, c->temporal.state.holdsSized(0, c->params.width, c->params.height), "flx_history_capture: the image size differs from the G-buffer's");
     const size_t n = c->fr.localPixels;
     const bool withMom = c->moments && c->fr.moments;
     // (the moments' copy is allocated when first needed; a failed allocation releases slots and history together, so a retry starts clean)
@@ -106,15 +105,11 @@ int flx_history_capture(flx_ctx *c)
         const std::string why = c->err; c->temporal.release(); c->err = "flx_history_capture: " + why; return 1;
     }
     HIPCHK(c, hipMemcpyAsync(c->temporal.hist, c->fr.pixels, n * 16, hipMemcpyDeviceToDevice, c->stream));
-    c->temporal.histHasMom = withMom;
-    if (c->temporal.histHasMom) HIPCHK(c, hipMemcpyAsync(c->temporal.histMomBuf, c->fr.moments, n * 16, hipMemcpyDeviceToDevice, c->stream));
+    if (withMom) HIPCHK(c, hipMemcpyAsync(c->temporal.histMomBuf, c->fr.moments, n * 16, hipMemcpyDeviceToDevice, c->stream));
     std::swap(c->temporal.gb[0], c->temporal.gb[1]);
     std::swap(c->temporal.objPlane[0], c->temporal.objPlane[1]);
-    c->temporal.objValid[1] = c->temporal.objValid[0]; c->temporal.objValid[0] = false;
-    c->ob.xCap = c->ob.xNow; c->ob.knownCap = c->ob.known;      // every object's pose under this history (flx_reproject_motion.h: X_cap)
-    c->temporal.gbCam[1] = c->temporal.gbCam[0]; c->temporal.gbW[1] = c->temporal.gbW[0]; c->temporal.gbH[1] = c->temporal.gbH[0]; c->temporal.gbTraced[1] = true;
-    c->temporal.gbTraced[0] = false;
-    c->temporal.histHave = true;
+    c->temporal.state.captured(withMom);
+    c->ob.pose.captured();
     return 0;
 }
 int flx_reproject(flx_ctx *c, const flx_reproject_params *pp)
@@ -125,13 +120,13 @@ int flx_reproject(flx_ctx *c, const flx_reproject_params *pp)
     rp_params rp = {FLX_RP_DEFAULT_MAX_HISTORY, FLX_RP_DEFAULT_PLANE_TOLERANCE_PX, FLX_RP_DEFAULT_NORMAL_COS, FLX_RP_DEFAULT_MIN_WEIGHT};
     if (pp) { rp.max_history = pp->max_history; rp.plane_tolerance_px = pp->plane_tolerance_px; rp.normal_cos = pp->normal_cos; rp.min_weight = pp->min_weight; }
     NEED(c, rp_params_ok(rp), "flx_reproject: parameters must be finite with max_history >= 1, plane_tolerance_px > 0, normal_cos in [-1, 1], min_weight in (0, 1]");
-    NEED(c, c->temporal.histHave && c->temporal.gbTraced[1], "flx_reproject: no captured history (flx_history_capture first)");
-    NEED(c, c->temporal.gbTraced[0], "flx_reproject: no G-buffer has been traced for the current camera (flx_gbuffer first)");
-    NEED(c, c->temporal.gbW[0] == c->params.width && c->temporal.gbH[0] == c->params.height && c->temporal.gbW[1] == c->temporal.gbW[0] && c->temporal.gbH[1] == c->temporal.gbH[0],
-         "flx_reproject: the image size changed between the capture and the reprojection");
-    const flx_camera &pc = c->temporal.gbCam[1];
-    const rp_view vw = rp_make_view(mk3(pc.pos.x, pc.pos.y, pc.pos.z), mk3(pc.dir.x, pc.dir.y, pc.dir.z), mk3(pc.up.x, pc.up.y, pc.up.z), mk3(pc.right.x, pc.right.y, pc.right.z), pc.fov, c->temporal.gbCam[0].fov, (int)c->params.width, (int)c->params.height);
-    const bool mom = c->moments && c->fr.moments && c->temporal.histHasMom;
+    const TemporalState &ts = c->temporal.state;
+    NEED(c, ts.hasHistory(), "flx_reproject: no captured history (flx_history_capture first)");
+    NEED(c, ts.holds(0), "flx_reproject: no G-buffer has been traced for the current camera (flx_gbuffer first)");
+    NEED(c, ts.historyFits(c->params.width, c->params.height), "flx_reproject: the image size changed between the capture and the reprojection");
+    const flx_camera &pc = ts.slot[1].cam;
+    const rp_view vw = rp_make_view(mk3(pc.pos.x, pc.pos.y, pc.pos.z), mk3(pc.dir.x, pc.dir.y, pc.dir.z), mk3(pc.up.x, pc.up.y, pc.up.z), mk3(pc.right.x, pc.right.y, pc.right.z), pc.fov, ts.slot[0].cam.fov, (int)c->params.width, (int)c->params.height);
+    const bool mom = c->moments && c->fr.moments && ts.histMom;
     // objects posed since the capture (only flx_objects_pose under "motion_history" keeps a history across a move of triangles): the motion-aware
     // kernel with the table of flx_reproject_motion.h, nobjects x 64 bytes uploaded on the stream; no object moved: k_reproject as ever
     flx_ctx::Objects &ob = c->ob;
@@ -139,10 +134,11 @@ int flx_reproject(flx_ctx *c, const flx_reproject_params *pp)
     std::vector<rm_row> table;
     if (ob.have && ob.t.nobjects) {
         table.resize((size_t)ob.t.nobjects * FLX_RM_ROWS);
-        moved = rm_make_table(ob.t.nobjects, ob.xCap.data(), ob.knownCap.data(), ob.xNow.data(), ob.known.data(), table.data());
+        const PoseState::Poses p = ob.pose.sinceCapture();
+        moved = rm_make_table(ob.t.nobjects, p.atCapture, p.atCaptureKnown, p.now, p.nowKnown, table.data());
     }
     if (moved) {
-        NEED(c, c->motionHistory && ob.motion && c->temporal.objValid[0] && c->temporal.objValid[1],
+        NEED(c, c->motionHistory && ob.motion && ts.holdsObjects(0) && ts.holdsObjects(1),
              "flx_reproject: objects were posed since the capture: needs option \"motion_history\" on and both G-buffers traced with it (flx_gbuffer)");
         memcpy(ob.motionPinned, table.data(), table.size() * sizeof(rm_row));
         HIPCHK(c, hipMemcpyAsync(ob.motion, ob.motionPinned, table.size() * sizeof(rm_row), hipMemcpyHostToDevice, c->stream));
@@ -162,10 +158,11 @@ int flx_gbuffer_read(flx_ctx *c, int slot, float *out8, void *camera80)
     HIPCHK(c, hipSetDevice(c->device));
     NEED(c, slot == 0 || slot == 1, "flx_gbuffer_read: slot must be 0 (current) or 1 (previous)");
     NEED(c, out8, "flx_gbuffer_read: null output");
-    NEED(c, c->temporal.gb[slot] && c->temporal.gbTraced[slot], "flx_gbuffer_read: the slot holds no G-buffer");
-    HIPCHK(c, hipMemcpyAsync(out8, c->temporal.gb[slot], (size_t)c->temporal.gbW[slot] * c->temporal.gbH[slot] * 32, hipMemcpyDeviceToHost, c->stream));
+    NEED(c, c->temporal.gb[slot] && c->temporal.state.holds(slot), "flx_gbuffer_read: the slot holds no G-buffer");
+    const TemporalState::Slot &s = c->temporal.state.slot[slot];
+    HIPCHK(c, hipMemcpyAsync(out8, c->temporal.gb[slot], (size_t)s.W * s.H * 32, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (camera80) memcpy(camera80, &c->temporal.gbCam[slot], sizeof(flx_camera));
+    if (camera80) memcpy(camera80, &s.cam, sizeof(flx_camera));
     return 0;
 }
 int flx_gbuffer_write(flx_ctx *c, int slot, const float *in8, const void *camera80)
@@ -177,14 +174,12 @@ int flx_gbuffer_write(flx_ctx *c, int slot, const float *in8, const void *camera
     if (temporalReady(c, "flx_gbuffer_write") || gbufferSlots(c)) return 1;
     HIPCHK(c, hipMemcpyAsync(c->temporal.gb[slot], in8, (size_t)c->fr.localPixels * 32, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(&c->temporal.gbCam[slot], camera80, sizeof(flx_camera));
-    c->temporal.gbW[slot] = c->params.width; c->temporal.gbH[slot] = c->params.height; c->temporal.gbTraced[slot] = true;
-    c->temporal.objValid[slot] = false;
     if (c->motionHistory) {                               // a written G-buffer shows no object until flx_gbuffer_objects_write says otherwise
         HIPCHK(c, hipMemsetAsync(c->temporal.objPlane[slot], 0xFF, (size_t)c->fr.localPixels * 4, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->temporal.objValid[slot] = true;
     }
+    flx_camera cam; memcpy(&cam, camera80, sizeof(flx_camera));
+    c->temporal.state.written(slot, cam, c->params.width, c->params.height, c->motionHistory);
     return 0;
 }
 // ... and of the slots' object planes (option "motion_history"): one uint32 per pixel, FLX_NO_OBJECT or an object id (an id that is not below
@@ -195,9 +190,10 @@ int flx_gbuffer_objects_read(flx_ctx *c, int slot, uint32_t *out)
     HIPCHK(c, hipSetDevice(c->device));
     NEED(c, slot == 0 || slot == 1, "flx_gbuffer_objects_read: slot must be 0 (current) or 1 (previous)");
     NEED(c, out, "flx_gbuffer_objects_read: null output");
-    NEED(c, c->temporal.objPlane[slot] && c->temporal.gbTraced[slot] && c->temporal.objValid[slot],
+    NEED(c, c->temporal.objPlane[slot] && c->temporal.state.holdsObjects(slot),
          "flx_gbuffer_objects_read: the slot holds no object plane (option \"motion_history\" on, objects defined, flx_gbuffer)");
-    HIPCHK(c, hipMemcpyAsync(out, c->temporal.objPlane[slot], (size_t)c->temporal.gbW[slot] * c->temporal.gbH[slot] * 4, hipMemcpyDeviceToHost, c->stream));
+    const TemporalState::Slot &s = c->temporal.state.slot[slot];
+    HIPCHK(c, hipMemcpyAsync(out, c->temporal.objPlane[slot], (size_t)s.W * s.H * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -209,47 +205,47 @@ int flx_gbuffer_objects_write(flx_ctx *c, int slot, const uint32_t *in)
     NEED(c, in, "flx_gbuffer_objects_write: null object ids");
     NEED(c, c->motionHistory, "flx_gbuffer_objects_write: needs flx_set_option(ctx, \"motion_history\", 1)");
     if (temporalReady(c, "flx_gbuffer_objects_write")) return 1;
-    NEED(c, c->temporal.gb[slot] && c->temporal.gbTraced[slot] && c->temporal.gbW[slot] == c->params.width && c->temporal.gbH[slot] == c->params.height,
+    NEED(c, c->temporal.gb[slot] && c->temporal.state.holdsSized(slot, c->params.width, c->params.height),
          "flx_gbuffer_objects_write: the slot holds no G-buffer of the current size (flx_gbuffer or flx_gbuffer_write first)");
     if (gbufferSlots(c)) return 1;
     HIPCHK(c, hipMemcpyAsync(c->temporal.objPlane[slot], in, (size_t)c->fr.localPixels * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->temporal.objValid[slot] = true;
+    c->temporal.state.objectsWritten(slot);
     return 0;
 }
 
 // ---- microkernel integrator.  One path per pixel, framebuffers indexed by the path id: single-GPU only, the pixel
 // partition belongs to the wavefront path (allocFrame sizes the buffers for the rank's LOCAL pixels).
 #define MK_READY(c) do { READY(c, CALL_OBSERVE); NEED(c, (c)->fr.nranks == 1, "the microkernel integrator is single-GPU: flx_set_partition(ctx, 0, 1) first"); } while (0)
-int flx_mk_reset(flx_ctx *c) { MK_READY(c); c->ad.have = false; launch_mk_reset(c->stream, c->st, c->fr, c->params); LAUNCHED(c); return 0; }
+int flx_mk_reset(flx_ctx *c) { MK_READY(c); c->ad.state.dropped(); launch_mk_reset(c->stream, c->st, c->fr, c->params); LAUNCHED(c); return 0; }
 // with a list of active pixels installed (flx_mk_adaptive_update / flx_mk_active_write) the four kernels of a sample pass run their list-driven
 // instances over it; an empty list makes them no-ops
 int flx_mk_raygen(flx_ctx *c)
 {
     MK_READY(c);
-    if (!c->ad.have) launch_mk_raygen(c->stream, c->st, c->params);
-    else if (c->ad.count) launch_mk_raygen_list(c->stream, c->st, c->params, c->ad.list, c->ad.count);
+    if (!c->ad.state.have) launch_mk_raygen(c->stream, c->st, c->params);
+    else if (c->ad.state.count) launch_mk_raygen_list(c->stream, c->st, c->params, c->ad.list, c->ad.state.count);
     LAUNCHED(c); return 0;
 }
 int flx_mk_next_vertex(flx_ctx *c)
 {
     MK_READY(c);
-    if (!c->ad.have) launch_mk_next_vertex(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
-    else if (c->ad.count) launch_mk_next_vertex_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ad.list, c->ad.count);
+    if (!c->ad.state.have) launch_mk_next_vertex(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
+    else if (c->ad.state.count) launch_mk_next_vertex_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ad.list, c->ad.state.count);
     LAUNCHED(c); return 0;
 }
 int flx_mk_sample_bsdf(flx_ctx *c)
 {
     MK_READY(c);
-    if (!c->ad.have) launch_mk_sample_bsdf(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
-    else if (c->ad.count) launch_mk_sample_bsdf_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ad.list, c->ad.count);
+    if (!c->ad.state.have) launch_mk_sample_bsdf(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
+    else if (c->ad.state.count) launch_mk_sample_bsdf_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ad.list, c->ad.state.count);
     LAUNCHED(c); return 0;
 }
 int flx_mk_splat(flx_ctx *c)
 {
     MK_READY(c);
-    if (!c->ad.have) launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 0);
-    else if (c->ad.count) launch_mk_splat_list(c->stream, c->st, c->fr, c->params, c->mkStats, c->ad.list, c->ad.count);
+    if (!c->ad.state.have) launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 0);
+    else if (c->ad.state.count) launch_mk_splat_list(c->stream, c->st, c->fr, c->params, c->mkStats, c->ad.list, c->ad.state.count);
     LAUNCHED(c); return 0;
 }
 int flx_mk_splat_preview(flx_ctx *c) { MK_READY(c); launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 1); LAUNCHED(c); return 0; }
@@ -260,12 +256,12 @@ static int adaptiveReady(flx_ctx *c, const char *fn)
     NEED(c, c->fr.nranks == 1, std::string(fn) + ": the microkernel integrator is single-GPU: flx_set_partition(ctx, 0, 1) first");
     const uint64_t npix = (uint64_t)c->params.width * c->params.height;
     NEED(c, npix <= c->numTasks, std::string(fn) + ": needs one path per pixel: width * height <= num_tasks");
-    if (c->ad.pix != (uint32_t)npix || !c->ad.list) {
+    if (c->ad.state.pix != (uint32_t)npix || !c->ad.list) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->ad.release();
         if (dalloc(c, c->ad.allocs, &c->ad.flags, (size_t)npix) || dalloc(c, c->ad.allocs, &c->ad.scratch, (size_t)adaptive_blocks((uint32_t)npix)) ||
             dalloc(c, c->ad.allocs, &c->ad.list, (size_t)npix) || dalloc(c, c->ad.allocs, &c->ad.countDev, 1)) { c->ad.release(); return 1; }
-        c->ad.pix = (uint32_t)npix;
+        c->ad.state.pix = (uint32_t)npix;
     }
     return 0;
 }
@@ -284,22 +280,22 @@ int flx_mk_adaptive_update(flx_ctx *c, const flx_adaptive_params *pp, uint32_t *
     uint32_t n = 0;
     HIPCHK(c, hipMemcpyAsync(&n, c->ad.countDev, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    NEED(c, n <= c->ad.pix, "flx_mk_adaptive_update: the device returned an impossible count");
-    c->ad.count = n; c->ad.have = true;
+    NEED(c, n <= c->ad.state.pix, "flx_mk_adaptive_update: the device returned an impossible count");
+    c->ad.state.installed(n);
     *out_active = n;
     return 0;
 }
-int flx_mk_adaptive_clear(flx_ctx *c) { ENTER(c, CALL_OBSERVE); c->ad.have = false; return 0; }
+int flx_mk_adaptive_clear(flx_ctx *c) { ENTER(c, CALL_OBSERVE); c->ad.state.dropped(); return 0; }
 // test hooks in the spirit of flx_gbuffer_read / flx_gbuffer_write.  Blocking.
 int flx_mk_active_read(flx_ctx *c, uint32_t *out_list, uint32_t *out_count, uint8_t *out_flags)
 {
     ENTER(c, CALL_OBSERVE);
     HIPCHK(c, hipSetDevice(c->device));
     NEED(c, out_count, "flx_mk_active_read: null count");
-    NEED(c, c->ad.have, "flx_mk_active_read: no list of active pixels is installed");
-    *out_count = c->ad.count;
-    if (out_list && c->ad.count) HIPCHK(c, hipMemcpyAsync(out_list, c->ad.list, (size_t)c->ad.count * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_flags) HIPCHK(c, hipMemcpyAsync(out_flags, c->ad.flags, (size_t)c->ad.pix, hipMemcpyDeviceToHost, c->stream));
+    NEED(c, c->ad.state.have, "flx_mk_active_read: no list of active pixels is installed");
+    *out_count = c->ad.state.count;
+    if (out_list && c->ad.state.count) HIPCHK(c, hipMemcpyAsync(out_list, c->ad.list, (size_t)c->ad.state.count * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_flags) HIPCHK(c, hipMemcpyAsync(out_flags, c->ad.flags, (size_t)c->ad.state.pix, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -314,10 +310,10 @@ int flx_mk_active_write(flx_ctx *c, const uint32_t *in_list, uint32_t n)
         NEED(c, i == 0 || in_list[i] > in_list[i - 1], "flx_mk_active_write: the list must be strictly ascending");
     }
     if (adaptiveReady(c, "flx_mk_active_write")) return 1;
-    HIPCHK(c, hipMemsetAsync(c->ad.flags, 0, c->ad.pix, c->stream));       // (the flags describe a classification; a written list has none)
+    HIPCHK(c, hipMemsetAsync(c->ad.flags, 0, c->ad.state.pix, c->stream));       // (the flags describe a classification; a written list has none)
     if (n) HIPCHK(c, hipMemcpyAsync(c->ad.list, in_list, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->ad.count = n; c->ad.have = true;
+    c->ad.state.installed(n);
     return 0;
 }
 

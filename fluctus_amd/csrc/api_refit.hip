@@ -9,7 +9,6 @@
 #include "flx_wide.h"
 #include "flx_trace4.h"
 #include <cstring>
-#include <algorithm>
 
 namespace flxd {
 float wideClampFor(float maxAbsCoord) { return maxAbsCoord < 67108864.0f ? FLX_WIDE_DINV_MAX : FLX_WIDE_DINV_FAR; }
@@ -36,10 +35,10 @@ int motionTables(flx_ctx *c)
 // The boundary of both calls, written once.  flx_update_triangles: every triangle, count must be the scene's.  flx_update_triangles_subset
 // (`subset`): the source is a list, validation also checks the list and reduces the maximum |coordinate| over the unmoved triangles' stored
 // positions (the clamp is that of the WHOLE resulting set, never a running maximum), and the passes rewrite only what is dirty (refit.hip: one
-// set of passes, two modes).  Every message carries the name of the call it refuses (`as`: flx_objects_pose, which ends in the subset call).
-// as == flx_objects_pose with option "motion_history" on and a history captured whose object plane is valid: the PREVIOUS slot and the history stay
-// (flx_reproject follows the posed objects), only the current slot becomes "not traced".
-static int updateTriangles(flx_ctx *c, bool subset, const void *tris160, const uint32_t *indices, size_t count, int src_on_device, const char *as = nullptr)
+// set of passes, two modes).  Every message carries the name of the call it refuses (`as`: flx_objects_pose, which ends in the subset call and says
+// so with `byPose`: what a pose keeps of a captured history, TemporalState::trianglesMoved).
+static int updateTriangles(flx_ctx *c, bool subset, const void *tris160, const uint32_t *indices, size_t count, int src_on_device, const char *as = nullptr,
+                           bool byPose = false)
 {
     const std::string fn = as ? as : subset ? "flx_update_triangles_subset: " : "flx_update_triangles: ";
     ENTER(c, CALL_OBSERVE);                               // deferred and fused launches run against the OLD scene
@@ -105,10 +104,9 @@ static int updateTriangles(flx_ctx *c, bool subset, const void *tris160, const u
         c->sc.wideClamp = wideClampFor(maxAbs);
     }
     // what flx_upload_scene clears: a list of active pixels and a G-buffer belong to the render of one geometry
-    c->ad.have = false;
-    if (as && c->motionHistory && c->temporal.histHave && c->temporal.gbTraced[1] && c->temporal.objValid[1]) { c->temporal.gbTraced[0] = false; c->temporal.objValid[0] = false; }
-    else c->temporal.dropHistory();
-    if (!as) std::fill(c->ob.known.begin(), c->ob.known.end(), (uint8_t)0);     // triangles set one by one: no object is where its last pose put it
+    c->ad.state.dropped();
+    c->temporal.state.trianglesMoved(byPose, c->motionHistory);
+    if (!byPose) c->ob.pose.trianglesSetDirectly();
     if (subset && !count) return 0;
     {
         ScopedTimer t(c, FLX_K_REFIT);
@@ -136,7 +134,7 @@ int flx_objects_define(flx_ctx *c, const void *tris160_rest, size_t ntris, const
     ENTER(c, CALL_OBSERVE);
     NEED(c, c->sc.bnodes, fn + "upload a scene first (flx_upload_scene)");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!nobjects) { c->ob.release(); c->temporal.objValid[0] = c->temporal.objValid[1] = false; if (c->motionHistory) c->temporal.dropHistory(); return 0; }
+    if (!nobjects) { c->ob.release(); c->temporal.state.definitionChanged(c->motionHistory); return 0; }
     NEED(c, tris160_rest && object_of_triangle, fn + "null triangles or object ids");
     NEED(c, ntris == c->rf.ntris, fn + "the triangle count differs from the uploaded scene's (" + std::to_string(ntris) + " vs " + std::to_string(c->rf.ntris) + ")");
     flx_ctx::Objects ob;                                  // built aside: a refused or failed call leaves the earlier definition in place
@@ -162,13 +160,11 @@ int flx_objects_define(flx_ctx *c, const void *tris160_rest, size_t ntris, const
     }
     HIPCHK(c, hipMemset(t.stamp, 0, (size_t)nobjects * 8));  // epoch 0 is never a call's
     ob.have = true;
-    ob.xNow.assign((size_t)nobjects * 12, 0.0f); ob.xCap = ob.xNow; ob.known.assign(nobjects, 0); ob.knownCap = ob.known;     // every pose unknown
+    ob.pose.defined(nobjects);                            // every pose unknown
     guard.keep = true;
     c->ob.release();
     c->ob = std::move(ob);
-    // the object planes name the objects of the earlier definition; with "motion_history" on the history goes with it
-    c->temporal.objValid[0] = c->temporal.objValid[1] = false;
-    if (c->motionHistory) c->temporal.dropHistory();
+    c->temporal.state.definitionChanged(c->motionHistory);
     return 0;
 }
 
@@ -207,11 +203,8 @@ int flx_objects_pose(flx_ctx *c, const uint32_t *object_ids, const float *xforms
         }
         LAUNCHED(c);
     }
-    if (updateTriangles(c, true, t.out, t.outIdx, n, 1, name)) return 1;
-    for (uint32_t k = 0; k < count; k++) {                // accepted: these are the listed objects' poses now
-        memcpy(c->ob.xNow.data() + 12 * (size_t)object_ids[k], xforms12 + 12 * (size_t)k, 48);
-        c->ob.known[object_ids[k]] = 1;
-    }
+    if (updateTriangles(c, true, t.out, t.outIdx, n, 1, name, true)) return 1;
+    c->ob.pose.posed(object_ids, xforms12, count);        // accepted: these are the listed objects' poses now
     return 0;
 }
 

@@ -19,7 +19,7 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
                      const void *texdesc, size_t ntex, const uint8_t *texdata, size_t texbytes)
 {
     ENTER(c, CALL_OBSERVE);
-    c->ad.have = false;                                   // a list of active pixels belongs to the render of one scene (flx_mk_adaptive_clear)
+    c->ad.state.dropped();                                // a list of active pixels belongs to the render of one scene (flx_mk_adaptive_clear)
     NEED(c, trisv && ntris && indices && nidx && nodesv && nnodes, "flx_upload_scene: empty scene");
     NEED(c, materials && nmat, "flx_upload_scene: at least the default material is required");
     HIPCHK(c, hipSetDevice(c->device));
@@ -247,8 +247,7 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     c->sceneAllocs.swap(fresh);
     c->rf = std::move(rf);
     c->ob.release();                                      // objects are defined over the triangles of one upload (flx_objects_define)
-    c->temporal.objValid[0] = c->temporal.objValid[1] = false;      // the object planes name that definition's objects ...
-    if (c->motionHistory) c->temporal.dropHistory();      // ... and with "motion_history" on a captured history belongs to the scene it was rendered from
+    c->temporal.state.definitionChanged(c->motionHistory);
     if (newSpill) { freeAll(c->spillAllocs); c->spillAllocs.swap(freshSpill); c->spill = sp1; c->spill2 = sp2; c->spillLevels = spillLevels; }
     c->sc.bnodes = dB; c->sc.trirecs = dT; c->sc.shade = dS; c->sc.tris = dTri; c->sc.materials = dM; c->sc.texdesc = dD; c->sc.texdata = dX;
     c->sc.rootRef = 0;

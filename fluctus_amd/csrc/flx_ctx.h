@@ -8,10 +8,13 @@
 //   api_hooks.hip      measurement and test hooks
 //   api_refit.hip      flx_update_triangles / flx_update_triangles_subset (moved triangles -> refitted trees, refit.hip), their test hook flx_tree_read, flx_tree_cost (tree_cost.hip),
 //                      flx_objects_define / flx_objects_pose (objects posed on the device, pose.hip, handed to the subset refit) and their test hook flx_objects_read
+// The state of the image features -- G-buffer slots and history, poses, the list of active pixels -- and which call invalidates what: flx_feature_state.h;
+// the units above call its transitions and ask its predicates, none of them writes one of its flags.
 // Everything here that is not `struct flx_ctx` (the C header's opaque type) lives in namespace flxd, like the launchers (flx_launch.h), so the
 // library's extern "C" surface is include/fluctus_hip.h and nothing else.
 #pragma once
 #include "flx_launch.h"
+#include "flx_feature_state.h"
 #include "../../include/fluctus_hip.h"
 #include <string>
 #include <vector>
@@ -136,26 +139,22 @@ struct flx_ctx {
     } dn;
     int moments = 0;            // option "moments": the splats accumulate the luminance moments (Frame::moments, which = 7)
     std::vector<void *> momAllocs;
-    // temporal reprojection (reproject.hip).  Two G-buffer slots of 2 float4 per pixel, [0] current, [1] previous, each with the
-    // camera and the size it was traced with; allocated by the first flx_gbuffer / flx_gbuffer_write, freed with the framebuffers.
-    // hist / histMomBuf: the accumulation and the moments as flx_history_capture copied them (histMomBuf null: "moments" was off then)
+    // temporal reprojection (TemporalState): the two G-buffer slots of 2 float4 per pixel, allocated by the first flx_gbuffer / flx_gbuffer_write; the
+    // accumulation and the moments as flx_history_capture copied them (histMomBuf null: "moments" was never on at a capture); one object id per
+    // pixel beside each slot, swapped with the slots, allocated by the first of those calls that finds "motion_history" on.  Freed with the framebuffers.
     struct Temporal {
         std::vector<void *> allocs;
-        float4 *gb[2] = {nullptr, nullptr}; flx_camera gbCam[2] = {}; uint32_t gbW[2] = {0, 0}, gbH[2] = {0, 0}; bool gbTraced[2] = {false, false};
-        float4 *hist = nullptr, *histMomBuf = nullptr; bool histHave = false, histHasMom = false;
-        // option "motion_history" (DESIGN.md 4.3.4): one object id per pixel beside each slot, swapped with the slots; allocated by the first
-        // flx_gbuffer / flx_gbuffer_write while the option is on.  objValid: the plane belongs to the slot's G-buffer and to the current definition
-        uint32_t *objPlane[2] = {nullptr, nullptr}; bool objValid[2] = {false, false};
-        void dropHistory() { gbTraced[0] = gbTraced[1] = false; histHave = false; objValid[0] = objValid[1] = false; }
+        float4 *gb[2] = {nullptr, nullptr}, *hist = nullptr, *histMomBuf = nullptr; uint32_t *objPlane[2] = {nullptr, nullptr};
+        TemporalState state;
         void release() { freeAll(allocs); *this = Temporal(); }
     } temporal;
     int motionHistory = 0;      // option "motion_history": flx_objects_pose keeps a captured history, flx_reproject follows the posed objects
-    // the adaptive microkernel render (adaptive.hip): the list of active pixels the sample pass's four kernels run over while
-    // `have` (`count` entries, ascending; 0 = the calls are no-ops); flag bytes, block counts and the list are allocated by the first
-    // flx_mk_adaptive_update / flx_mk_active_write for `pix` pixels and freed with the framebuffers.  have false = every pixel.
+    // the adaptive microkernel render (ActiveListState): flag bytes, block counts and the list of active pixels, allocated by the first
+    // flx_mk_adaptive_update / flx_mk_active_write for state.pix pixels and freed with the framebuffers
     struct Adaptive {
         std::vector<void *> allocs;
-        uint8_t *flags = nullptr; uint32_t *scratch = nullptr, *list = nullptr, *countDev = nullptr; uint32_t pix = 0, count = 0; bool have = false;
+        uint8_t *flags = nullptr; uint32_t *scratch = nullptr, *list = nullptr, *countDev = nullptr;
+        ActiveListState state;
         void release() { freeAll(allocs); *this = Adaptive(); }
     } ad;
     void releaseFrameFeatures() { dn.release(); temporal.release(); ad.release(); }
@@ -167,9 +166,7 @@ struct flx_ctx {
         ObjectTables t;
         std::vector<uint32_t> counts;
         bool have = false;
-        // every object's pose now and at the last flx_history_capture (12 floats each) with a `known` byte: unknown until the object has been
-        // posed since the definition -- the uploaded triangles need not be the rest pose.  Kept on the host whatever the options say.
-        std::vector<float> xNow, xCap; std::vector<uint8_t> known, knownCap;
+        PoseState pose;
         // option "motion_history": the object of every triangle (FLX_NO_OBJECT: none) and the per-object motion table of flx_reproject_motion.h
         // (four float4 per object) with its pinned staging copy; made by the first flx_gbuffer or flx_objects_pose that finds the option on
         uint32_t *objectOfTri = nullptr; float4 *motion = nullptr, *motionPinned = nullptr;

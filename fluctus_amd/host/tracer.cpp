@@ -190,8 +190,7 @@ void Tracer::poseObjects(const std::vector<uint32_t> &ids, const std::vector<flo
     if (rebuildMode != RebuildOff) adoptFinishedRebuild();
     // motion-aware reprojection: with a history by update()'s own conditions, capture it before the ranks are posed -- at most once
     // per frame -- so that flx_objects_pose keeps it
-    const bool keep = motionOn && temporalOn && useWavefront && haveGbuffer && (poseHistory || framesSinceGbuffer > 0) && gbWidth == params.width &&
-                      gbHeight == params.height && onlyCameraChanged(true);
+    const bool keep = motionOn && historyExists(true);
     const bool capture = keep && !poseHistory;
     if (capture) { clctx->historyCapture(); poseHistory = true; }
     try {
@@ -357,6 +356,13 @@ void Tracer::setMotionReprojection(bool on)
 }
 // everything of RenderParams that shapes the radiance of a point, i.e. all but the camera (bytes 96..175) and the post-process (exposure,
 // tmOperator: 176..183), equals what the G-buffer's frames were rendered with
+// a history exists: at least one frame rendered since the last G-buffer (or poseObjects has captured it already), at the same size (a resize frees
+// the device's slots) and with nothing but the camera changed since (lights, bounces, sampling switches: the kept radiance would be stale)
+bool Tracer::historyExists(bool posed) const
+{
+    return temporalOn && useWavefront && haveGbuffer && (poseHistory || framesSinceGbuffer > 0) && gbWidth == params.width && gbHeight == params.height &&
+           onlyCameraChanged(posed);
+}
 bool Tracer::onlyCameraChanged(bool posed) const
 {
     RenderParams now = params;
@@ -508,11 +514,8 @@ void Tracer::update()
     bool reprojectNow = false;
     if (paramsUpdatePending) {
         const bool temporal = temporalOn && useWavefront;
-        // a history exists: at least one frame rendered since the last G-buffer, at the same size (a resize frees the device's slots)
-        // and with nothing but the camera changed since (lights, bounces, sampling switches: the kept radiance would be stale)
         // (poseObjects under motion-aware reprojection has captured it already: a camera change pending in the same frame shares that capture)
-        const bool history = temporal && haveGbuffer && (poseHistory || framesSinceGbuffer > 0) && gbWidth == params.width && gbHeight == params.height &&
-                             onlyCameraChanged(poseHistory);
+        const bool history = historyExists(poseHistory);
         if (history && !poseHistory) clctx->historyCapture();            // under the old camera's slot
         poseHistory = false;
         for (auto *c : R) c->updateParams(params);

@@ -195,6 +195,7 @@ private:
     bool haveGbuffer = false;
     RenderParams gbParams {};
     void dropHistory() { haveGbuffer = false; poseHistory = false; }
+    bool historyExists(bool posed) const;                                         // update()'s conditions for a history worth capturing, shared with poseObjects
     bool onlyCameraChanged(bool posed = false) const;                             // params against gbParams, the camera and the post-process aside (posed: and worldRadius, which a pose re-derives)
     bool motionOn = false;
     bool poseHistory = false;                                                     // poseObjects has captured the history of this frame: the next update() reprojects it
