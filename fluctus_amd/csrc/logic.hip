@@ -26,6 +26,7 @@
 #include "flx_trace.h"          // hit_values_raw: the commit of traceExtension for RAW hit records
 #include "flx_denoise.h"        // flx_lum: the luminance moments (option "moments")
 #include "flx_launch.h"
+#include "flx_splat.h"         // wave_add4: a terminating path's pixel as one 16-byte piece of one atomic instruction
 
 namespace flxd {
 
@@ -305,23 +306,21 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
         f3 hitP = rawP, orig = mk3(0.0f), Lnee = mk3(0.0f), neeLi = mk3(0.0f);
         float hitT = rawT, neeLen = 0.0f, neePdf = 0.0f, neeCos = 0.0f, neePick = 0.0f;
         uint32_t ml = 0u;
-        auto splat = [&]() {                                          // splat + regenerate, :163-177
-#ifndef FLX_LAB_LOGIC_NOSPLAT      // lab build only (RESULTS INVALID: no image): the pass without its 4 float atomics per terminating path
-            if (len > 0u) {
-                float *px = fr.pixels + (size_t)pixIdx * 4;
-                unsafeAtomicAdd(px + 0, Ei.x); unsafeAtomicAdd(px + 1, Ei.y);
-                unsafeAtomicAdd(px + 2, Ei.z); unsafeAtomicAdd(px + 3, 1.0f);
-                if (fr.moments) {                                     // option "moments": (sum l, sum l^2, 0, n), opt-in scattered atomics
-                    const float l = flx_lum(Ei);
-                    float *m = fr.moments + (size_t)pixIdx * 4;
-                    unsafeAtomicAdd(m + 0, l); unsafeAtomicAdd(m + 1, l * l); unsafeAtomicAdd(m + 3, 1.0f);
-                }
+        // splat + regenerate, :163-177.  Every lane of the wave calls it, where the wave is convergent (flx_splat.h: the four sums of a pixel travel as one
+        // 16-byte piece of one atomic instruction, four adjacent lanes per terminating path); `len > 0` as in the reference.
+        auto splat = [&]() {
+#ifndef FLX_LAB_LOGIC_NOSPLAT      // lab build only (RESULTS INVALID: no image): the pass without the float atomics of its terminating paths
+            const bool add = terminate && len > 0u;
+            wave_add4(fr.pixels, add, pixIdx, Ei.x, Ei.y, Ei.z, 1.0f, 0xFu);
+            if (fr.moments) {                                         // option "moments": (sum l, sum l^2, 0, n), opt-in; word 2 is never touched
+                const float l = flx_lum(Ei);
+                wave_add4(fr.moments, add, pixIdx, l, l * l, 0.0f, 1.0f, 0xBu);
             }
 #endif
         };
+        if (!FULL) splat();
         if (terminate) {
             if (!FULL) {
-                splat();
                 wr4(st.at(S_EI, gid), mk4(Ei, ei4.w));
                 wr4(st.at(S_THR, gid), mk4u(T, seed));
                 if (RAW && isRaw) wr4(st.at(S_HITUV, gid), make_float4(hitUV.x, hitUV.y, __int_as_float(hitI), __int_as_float(hitMat)));      // (clears the raw marker)
@@ -343,19 +342,6 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
                 }
             }
             orig = hitP - 1e-3f * rayDir;
-            if (fr.aovNormal) {                                       // denoiser features, :186-209
-                if (len == 1u) {
-                    const f3 n = camera_space_normal(p, hitN);
-                    float *px = fr.aovNormal + (size_t)pixIdx * 4;
-                    unsafeAtomicAdd(px + 0, n.x); unsafeAtomicAdd(px + 1, n.y); unsafeAtomicAdd(px + 2, n.z); unsafeAtomicAdd(px + 3, 1.0f);
-                }
-                if (!FLX_BXDF_IS_SINGULAR(mat.type) && !st.firstDiffuse[gid]) {
-                    st.firstDiffuse[gid] = 1u;
-                    const f3 albedo = mat_float3(sc, V(mat.Kd), hitUV, mat.map_Kd);              // not gamma-corrected
-                    float *px = fr.aovAlbedo + (size_t)pixIdx * 4;
-                    unsafeAtomicAdd(px + 0, albedo.x); unsafeAtomicAdd(px + 1, albedo.y); unsafeAtomicAdd(px + 2, albedo.z); unsafeAtomicAdd(px + 3, 1.0f);
-                }
-            }
             if (!FULL) wr4(st.at(S_HITN, gid), mk4u(hitN, (hflags & 1u) | (backface ? 2u : 0u)));   // :212-213
 
             if (p.sampleExpl && !FLX_BXDF_IS_SINGULAR(mat.type)) {    // next event estimation, :217-302
@@ -422,6 +408,24 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
             ml = material_list(mat.type, p.wfSeparateQueues);
             member |= ml << 2;
             inlined = FUSE != 0 && fuse_inlines_list(FUSE, ml);
+        }
+        if (fr.aovNormal) {                                           // denoiser features, :186-209 -- out of the branch above: the whole wave adds (flx_splat.h)
+            // (nothing is carried across the NEE code: the normal is the one the store below writes, the material record is read again -- only with the option on)
+            const bool addN = !terminate && len == 1u;
+            f3 n = mk3(0.0f);
+            if (addN) n = camera_space_normal(p, hitN);
+            wave_add4(fr.aovNormal, addN, pixIdx, n.x, n.y, n.z, 1.0f, 0xFu);
+            bool addA = false;
+            f3 albedo = mk3(0.0f);
+            if (!terminate) {
+                const flx_material m = FUSE == USE_ALL ? sc.materials[hitMat] : mat;             // (all types: the record is re-read at the material step too)
+                if (!FLX_BXDF_IS_SINGULAR(m.type) && !st.firstDiffuse[gid]) {
+                    st.firstDiffuse[gid] = 1u;
+                    albedo = mat_float3(sc, V(m.Kd), hitUV, m.map_Kd);                           // not gamma-corrected
+                    addA = true;
+                }
+            }
+            wave_add4(fr.aovAlbedo, addA, pixIdx, albedo.x, albedo.y, albedo.z, 1.0f, 0xFu);
         }
 
         f3 Lold = mk3(0.0f);                                          // the stored light direction of a lane without a new one
@@ -590,7 +594,7 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
             wr4(st.at(S_THR, gid), thr4);
             wr4(st.at(S_ORIG, gid), or4);
             wr4(st.at(S_DIR, gid), dr4);
-            if (terminate) splat();
+            splat();
         }
     }
 
