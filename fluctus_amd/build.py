@@ -41,6 +41,7 @@ def build_host(force=False):
                                                                                         os.path.join(PKG, "csrc", "flx_refit.h"),  # ... and the refit's quantiser
                                                                                         os.path.join(PKG, "csrc", "flx_tree_cost.h"),  # ... and the cost sums
                                                                                         os.path.join(PKG, "csrc", "flx_pose.h"),   # ... and the pose arithmetic
+                                                                                        os.path.join(PKG, "csrc", "flx_mesh_light.h"),   # ... and the table of emissive triangles
                                                                                         os.path.join(PKG, "csrc", "flx_adaptive.h")]   # hipcontext.hpp: the adaptive defaults
     out = os.path.join(PKG, "libfluctus_host.so")
     if force or _stale(out, dep):

@@ -230,14 +230,22 @@ int flx_mk_raygen(flx_ctx *c)
 int flx_mk_next_vertex(flx_ctx *c)
 {
     MK_READY(c);
-    if (!c->ad.state.have) launch_mk_next_vertex(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
+    if (c->ml.state.lit()) {                                // option "mesh_lights" and emissive triangles: the MESH instances
+        if (!c->ad.state.have || c->ad.state.count)
+            launch_mk_next_vertex_mesh(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ml.t, c->ad.state.have ? c->ad.list : nullptr, c->ad.state.count);
+    }
+    else if (!c->ad.state.have) launch_mk_next_vertex(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
     else if (c->ad.state.count) launch_mk_next_vertex_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ad.list, c->ad.state.count);
     LAUNCHED(c); return 0;
 }
 int flx_mk_sample_bsdf(flx_ctx *c)
 {
     MK_READY(c);
-    if (!c->ad.state.have) launch_mk_sample_bsdf(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
+    if (c->ml.state.lit()) {
+        if (!c->ad.state.have || c->ad.state.count)
+            launch_mk_sample_bsdf_mesh(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ml.t, c->ad.state.have ? c->ad.list : nullptr, c->ad.state.count);
+    }
+    else if (!c->ad.state.have) launch_mk_sample_bsdf(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
     else if (c->ad.state.count) launch_mk_sample_bsdf_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ad.list, c->ad.state.count);
     LAUNCHED(c); return 0;
 }

@@ -113,7 +113,8 @@ static int updateTriangles(flx_ctx *c, bool subset, const void *tris160, const u
         launch_refit(c->stream, src, idx, (uint32_t)count, c->sc, rf);
     }
     LAUNCHED(c);
-    return 0;
+    c->ml.state.trianglesMoved();                         // option "mesh_lights": a moved lamp has another area; rebuilt on the stream behind the refit
+    return meshLightsSync(c);
 }
 
 extern "C" {

@@ -3,6 +3,7 @@
 #include "flx_ctx.h"
 #include "flx_wide.h"
 #include "flx_refit.h"
+#include "flx_mesh_light.h"
 #include "flx_trace.h"
 #include "flx_trace4.h"
 #include <cmath>
@@ -247,6 +248,13 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     c->sceneAllocs.swap(fresh);
     c->rf = std::move(rf);
     c->ob.release();                                      // objects are defined over the triangles of one upload (flx_objects_define)
+    {   // the emissive triangles, ascending (flx_mesh_light.h): the list depends on the materials, which only this call brings
+        const flx_material *mats = (const flx_material *)materials;
+        c->ml.releaseBuffers();
+        c->ml.list.clear();
+        for (size_t i = 0; i < ntris; i++) { const flx_vec3 &ke = mats[tris[i].matId].Ke; if (flxml::ml_is_emissive(ke.x, ke.y, ke.z)) c->ml.list.push_back((uint32_t)i); }
+        c->ml.state.sceneUploaded((uint32_t)c->ml.list.size());
+    }
     c->temporal.state.definitionChanged(c->motionHistory);
     if (newSpill) { freeAll(c->spillAllocs); c->spillAllocs.swap(freshSpill); c->spill = sp1; c->spill2 = sp2; c->spillLevels = spillLevels; }
     c->sc.bnodes = dB; c->sc.trirecs = dT; c->sc.shade = dS; c->sc.tris = dTri; c->sc.materials = dM; c->sc.texdesc = dD; c->sc.texdata = dX;
@@ -264,7 +272,7 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     c->wideInfo[0] = (uint32_t)wide.nodes.size(); c->wideInfo[1] = (uint32_t)(wide.leafdata.size()); c->wideInfo[2] = wide.maxStack; c->wideInfo[3] = wide.nested ? 1u : 0u;
     c->wideInfo[4] = binDepth; c->wideInfo[5] = spillLevels; c->wideInfo[6] = (uint32_t)bnodes.size(); c->wideInfo[7] = wide.maxLeafCount;
     pickSchedule(c);
-    return 0;
+    return meshLightsSync(c);                             // option "mesh_lights": the table of the new scene, on the stream
 }
 
 int flx_upload_envmap(flx_ctx *c, const float *rgb, int w, int h, const float *prob, const int *alias, const float *pdf)

@@ -8,6 +8,7 @@
 //   api_hooks.hip      measurement and test hooks
 //   api_refit.hip      flx_update_triangles / flx_update_triangles_subset (moved triangles -> refitted trees, refit.hip), their test hook flx_tree_read, flx_tree_cost (tree_cost.hip),
 //                      flx_objects_define / flx_objects_pose (objects posed on the device, pose.hip, handed to the subset refit) and their test hook flx_objects_read
+//   api_mesh_light.hip flx_mesh_lights_read / flx_mesh_lights_sample and the rebuild of the table of emissive triangles (option "mesh_lights", mesh_light.hip)
 // The state of the image features -- G-buffer slots and history, poses, the list of active pixels -- and which call invalidates what: flx_feature_state.h;
 // the units above call its transitions and ask its predicates, none of them writes one of its flags.
 // Everything here that is not `struct flx_ctx` (the C header's opaque type) lives in namespace flxd, like the launchers (flx_launch.h), so the
@@ -172,6 +173,16 @@ struct flx_ctx {
         uint32_t *objectOfTri = nullptr; float4 *motion = nullptr, *motionPinned = nullptr;
         void release() { freeAll(allocs); if (motionPinned) (void)hipHostFree(motionPinned); *this = Objects(); }
     } ob;
+    // the emissive triangles as lights (MeshLightState; flx_mesh_light.h, mesh_light.hip): the host's ascending list (made by every
+    // flx_upload_scene, whatever the option says) and the device table, allocated by the first build for this scene.  The buffers are sized by the
+    // scene: a successful flx_upload_scene and flx_destroy release them; the option and the state survive an upload.
+    struct MeshLight {
+        std::vector<void *> allocs;
+        std::vector<uint32_t> list;
+        MeshLights t;
+        MeshLightState state;
+        void releaseBuffers() { freeAll(allocs); t = MeshLights(); }
+    } ml;
     int nodeLayout = 1;         // 1 = sibling-pair record numbering (see flx_upload_scene), 0 = DFS
     int numCUs = 256;
     // multi-GPU group (flx_group_*): RCCL communicator of this rank, root-side staging
@@ -238,6 +249,7 @@ void flushExt(flx_ctx *c);                          // api_wavefront.hip: the la
 int fuseSetNow(const flx_ctx *c);                   // api_wavefront.hip: the BSDF set the fused pass inlines now (read-only options)
 float wideClampFor(float maxAbsCoord);              // api_refit.hip: the bound of |1 / dir| in the wide node test for a scene reaching this far (flx_trace4.h: WRay::setup)
 int motionTables(flx_ctx *c);                       // api_refit.hip: objectOfTri and the motion table, made once per definition while "motion_history" is on
+int meshLightsSync(flx_ctx *c);                     // api_mesh_light.hip: (re)build the table of emissive triangles on the stream when the option is on and it is stale
 int wideFar(const flx_ctx *c);                      // api_refit.hip: 1 when sc.wideClamp is the far clamp (read-only option "wide_far")
 void pickSchedule(flx_ctx *c);                      // api.hip: the effective overlap / refill_shadow (options, flx_upload_scene)
 }

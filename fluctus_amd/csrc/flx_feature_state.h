@@ -1,7 +1,8 @@
 // flx_feature_state.h -- what the context knows about the data derived from the framebuffers and the scene, and WHICH CALL INVALIDATES WHAT
-// (DESIGN.md 4.3.5): the logical state of the G-buffer slots and the captured history, of the objects' poses and of the list of active pixels,
+// (DESIGN.md 4.3.5): the logical state of the G-buffer slots and the captured history, of the objects' poses, of the list of active pixels and of
+// the table of emissive triangles,
 // each with its transitions named after what happened.  The entry points (csrc/api*.hip) call a transition and ask a predicate; none writes a
-// flag.  Plain C++17, no HIP, nothing that owns device memory: the buffers stay in flx_ctx (flx_ctx.h), whose Temporal, Objects and Adaptive embed
+// flag.  Plain C++17, no HIP, nothing that owns device memory: the buffers stay in flx_ctx (flx_ctx.h), whose Temporal, Objects, Adaptive and MeshLight embed
 // these types and release them to their defaults with the buffers.  tests/feature_state_cpu.cpp runs the table of tests/feature_state_cases.py
 // through this header without a GPU, tests/test_gpu_feature_state.py the same table through the C ABI.
 #pragma once
@@ -67,5 +68,20 @@ struct ActiveListState {
     uint32_t pix = 0, count = 0; bool have = false;
     void installed(uint32_t n) { count = n; have = true; }
     void dropped() { have = false; }
+};
+
+// the table of emissive triangles (option "mesh_lights"; mesh_light.hip).  `listed`: the uploaded scene's `lights` emissive
+// triangles are known (the list depends on the materials, which only flx_upload_scene brings).  `built`: the device table was built from the
+// triangles as they stand.  Every call that moves triangles makes it stale; while the option is on the same call rebuilds it before it returns
+// (api_mesh_light.hip: meshLightsSync), so between two calls the table is never stale with the option on.
+struct MeshLightState {
+    bool on = false, listed = false, built = false; uint32_t lights = 0;
+    void optionSet(bool v) { on = v; if (!v) built = false; }           // kept up only while the option is on: switching it on builds
+    void sceneUploaded(uint32_t n) { listed = true; built = false; lights = n; }
+    void trianglesMoved() { built = false; }
+    void rebuilt() { built = true; }
+    bool needsBuild() const { return on && listed && !built; }
+    bool usable() const { return on && listed && built; }
+    bool lit() const { return usable() && lights > 0; }             // the MESH instances of the microkernels run; otherwise the plain ones do
 };
 }

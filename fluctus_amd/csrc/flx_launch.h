@@ -43,6 +43,26 @@ struct ObjectTables {
     uint32_t *blockCounts = nullptr, *total = nullptr;          // pose_blocks(members) words, one word
     uint32_t epoch = 0;                                         // epoch 0 is never a call's; a wrap of the counter re-zeroes the stamps (as RefitTables::epoch)
 };
+// The table of emissive triangles (option "mesh_lights"; what each array holds and in which order it is summed: flx_mesh_light.h; kernels:
+// mesh_light.hip); passed to the kernels by value.  Device arrays live with the scene allocations (flx_ctx::MeshLight).
+struct MeshLights {
+    uint32_t n = 0;                                             // lights listed (ascending triangle indices in `tri`)
+    uint32_t *tri = nullptr;
+    float *w = nullptr, *cdf = nullptr, *pick = nullptr;        // per light
+    double *local = nullptr;                                    // per light: the prefix sum inside its run
+    double *runSum = nullptr, *off = nullptr; uint32_t *runLast = nullptr;      // per run (off: runs + 1)
+    double *total = nullptr;                                    // total64; 0 = no lights
+    uint32_t *hdr = nullptr;                                    // [0] the last light with w > 0, [1] the last light with pick > 0 (ML_NONE: none)
+};
+__device__ __forceinline__ void ml_vertices(const Scene &sc, uint32_t tri, f3 *p0, f3 *p1, f3 *p2)
+{
+    const float4 *t = reinterpret_cast<const float4 *>(sc.tris + tri);
+    *p0 = ld3(t[0]); *p1 = ld3(t[3]); *p2 = ld3(t[6]);
+}
+__device__ __forceinline__ int ml_material(const Scene &sc, uint32_t tri) { return sc.tris[tri].matId; }
+uint32_t mesh_light_runs(uint32_t n);
+void launch_mesh_light_build(hipStream_t, const Scene &, const MeshLights &);
+void launch_mesh_light_probe(hipStream_t, const Scene &, const MeshLights &, const float *, uint32_t, uint32_t *, float *);
 uint32_t pose_blocks(uint32_t members);
 void launch_pose(hipStream_t, const ObjectTables &, uint32_t count);
 void launch_object_of_triangle(hipStream_t, const ObjectTables &, uint32_t *objectOfTri);     // the members' objects scattered into a table the caller has filled with FLX_NO_OBJECT
@@ -82,6 +102,9 @@ void launch_mk_raygen_list(hipStream_t, const State &, const flx_render_params &
 void launch_mk_next_vertex_list(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const uint32_t *, uint32_t);
 void launch_mk_sample_bsdf_list(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const uint32_t *, uint32_t);
 void launch_mk_splat_list(hipStream_t, const State &, const Frame &, const flx_render_params &, uint32_t *, const uint32_t *, uint32_t);
+// the MESH instances of the two kernels that see lights (option "mesh_lights"); a null list = every pixel
+void launch_mk_next_vertex_mesh(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const MeshLights &, const uint32_t *, uint32_t);
+void launch_mk_sample_bsdf_mesh(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const MeshLights &, const uint32_t *, uint32_t);
 uint32_t adaptive_blocks(uint32_t);
 void launch_adaptive_update(hipStream_t, const float4 *, int, int, const ad_params &, uint8_t *, uint32_t *, uint32_t *, uint32_t *);
 void launch_end_iteration(hipStream_t, uint32_t *, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t *);

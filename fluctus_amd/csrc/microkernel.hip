@@ -10,6 +10,7 @@
 #include "flx_bsdf.h"
 #include "flx_denoise.h"        // flx_lum: the luminance moments (option "moments")
 #include "flx_launch.h"
+#include "flx_mesh_light.h"      // option "mesh_lights": the MESH instances of mk_next_vertex / mk_sample_bsdf
 
 namespace flxd {
 
@@ -94,9 +95,11 @@ __device__ __forceinline__ void mk_raygen(State st, flx_render_params p, const u
 __global__ __launch_bounds__(256) void k_mk_raygen(State st, flx_render_params p) { mk_raygen<false>(st, p, nullptr, 0u); }
 __global__ __launch_bounds__(256) void k_mk_raygen_list(State st, flx_render_params p, const uint32_t *list, uint32_t count) { mk_raygen<true>(st, p, list, count); }
 
-template <bool LIST>
+// MESH (option "mesh_lights"): emissive triangles are lights -- their emission is collected here on an implicit hit and sampled in
+// mk_sample_bsdf, MIS-weighted against each other through the table `ml`.  The MESH = false instances are the reference's kernels.
+template <bool LIST, bool MESH>
 __device__ __forceinline__ void mk_next_vertex(uint32_t *s_stack, State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill,
-                                               uint32_t totalThreads, uint32_t *stats, const uint32_t *list, uint32_t count)
+                                               uint32_t totalThreads, uint32_t *stats, const uint32_t *list, uint32_t count, const MeshLights &ml)
 {
     const uint32_t tid = blockIdx.x * MK_BLOCK + threadIdx.x;
     uint32_t gid;
@@ -161,6 +164,29 @@ __device__ __forceinline__ void mk_next_vertex(uint32_t *s_stack, State st, Scen
             const float4 ei = rd4(st.at(S_EI, gid));
             wr4(st.at(S_EI, gid), mk4(ld3(ei) + T * misWeight * V(p.areaLight.E), ei.w));
             phase = MK_SPLAT_SAMPLE;
+        } else if (MESH) {                                           // a triangle whose material emits, seen from the side its geometric normal faces
+            const f3 Ke = V(sc.materials[matId].Ke);
+            if (flxml::ml_is_emissive(Ke.x, Ke.y, Ke.z) && (len == 1u || p.sampleImpl)) {       // (counted as the environment is, above)
+                f3 p0, p1, p2;
+                ml_vertices(sc, (uint32_t)tri, &p0, &p1, &p2);
+                const f3 ng = flxml::ml_normal(p0, p1, p2);
+                if (dot(ng, dir) < 0.0f) {
+                    float misWeight = 1.0f;
+                    const bool lastSpecular = __float_as_uint(rd4(st.at(S_LT, gid)).w) != 0u;
+                    if (p.sampleExpl && len > 1u && !lastSpecular && ml.n && ml.hdr[1] != ML_NONE) {
+                        const uint32_t k = flxml::ml_find(ml.tri, ml.n, (uint32_t)tri);
+                        if (k != ML_NONE) {                          // the pdf mk_sample_bsdf would have sampled this point with
+                            const float directPdfA = flxml::ml_pdf_area(ml.pick[k], flxml::ml_area(p0, p1, p2));
+                            const float directPdfW = pdf_a_to_w(directPdfA, length(P - orig), dot(normalize(-dir), ng));
+                            const float lastPdfW = o4.w;
+                            misWeight = lastPdfW / (lastPdfW + directPdfW);
+                        }
+                    }
+                    const f3 T = ld3(rd4(st.at(S_THR, gid)));
+                    const float4 ei = rd4(st.at(S_EI, gid));
+                    wr4(st.at(S_EI, gid), mk4(ld3(ei) + T * misWeight * Ke, ei.w));
+                }
+            }                                                        // the path goes on: a lamp with a black BSDF ends it in mk_sample_bsdf (is_zero(bsdf))
         }
         st.phase[gid] = phase;
     }
@@ -170,18 +196,25 @@ __device__ __forceinline__ void mk_next_vertex(uint32_t *s_stack, State st, Scen
 __global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats)
 {
     __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    mk_next_vertex<false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, nullptr, 0u);
+    mk_next_vertex<false, false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, nullptr, 0u, MeshLights());
 }
 __global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex_list(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
                                                                   const uint32_t *list, uint32_t count)
 {
     __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    mk_next_vertex<true>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count);
+    mk_next_vertex<true, false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count, MeshLights());
+}
+template <bool LIST>
+__global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex_mesh(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
+                                                                  const uint32_t *list, uint32_t count, MeshLights ml)
+{
+    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
+    mk_next_vertex<LIST, true>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count, ml);
 }
 
-template <bool LIST>
+template <bool LIST, bool MESH>
 __device__ __forceinline__ void mk_sample_bsdf(uint32_t *s_stack, State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill,
-                                               uint32_t totalThreads, uint32_t *stats, const uint32_t *list, uint32_t count)
+                                               uint32_t totalThreads, uint32_t *stats, const uint32_t *list, uint32_t count, const MeshLights &ml)
 {
     const uint32_t tid = blockIdx.x * MK_BLOCK + threadIdx.x;
     uint32_t gid;
@@ -255,6 +288,32 @@ __device__ __forceinline__ void mk_sample_bsdf(uint32_t *s_stack, State st, Scen
                     Ei = Ei + brdf * T * V(p.areaLight.E) * weight * cosTh / (lightPickProb * directPdfW);
                 }
             }
+            // the emissive triangles: the quad's block line for line, three draws (pick, r1, r2) and none without a pickable light
+            if (MESH && ml.n && ml.hdr[1] != ML_NONE) {
+                const uint32_t k = flxml::ml_pick(ml.cdf, ml.n, ml.hdr[1], rand01(&seed));
+                const float r1 = rand01(&seed);
+                const float r2 = rand01(&seed);
+                const uint32_t ltri = ml.tri[k];
+                f3 p0, p1, p2;
+                ml_vertices(sc, ltri, &p0, &p1, &p2);
+                const float directPdfA = flxml::ml_pdf_area(ml.pick[k], flxml::ml_area(p0, p1, p2));
+                f3 L = flxml::ml_sample_triangle(p0, p1, p2, r1, r2) - orig;
+                const float lenL = length(L);
+                L = normalize(L);
+                float t = 0.995f * lenL, u, v; int tri; uint32_t a = 0, b = 0;        // the lamp is in the tree: stop short of it (the reference's factor for its own light, src/wf_logic.cl)
+                const bool occluded = traverse<true, false>(sc, stk, orig, L, t, u, v, tri, a, b);
+                nShadow++;
+                const float cosLight = fmaxf_(dot(flxml::ml_normal(p0, p1, p2), -L), 0.0f);
+                if (!occluded && cosLight > 0.0f) {
+                    const f3 brdf = bxdf_eval(sc, h, m, backface, rayDir, L);
+                    const float cosTh = fmaxf_(0.0f, dot(L, h.N));
+                    const float directPdfW = pdf_a_to_w(directPdfA, lenL, cosLight);
+                    const float bsdfPdfW = fmaxf_(0.0f, bxdf_pdf(sc, h, m, backface, rayDir, L));
+                    float weight = 1.0f;
+                    if (p.sampleImpl) weight = (directPdfW * lightPickProb) / (directPdfW * lightPickProb + bsdfPdfW);
+                    Ei = Ei + brdf * T * V(sc.materials[ml_material(sc, ltri)].Ke) * weight * cosTh / (lightPickProb * directPdfW);
+                }
+            }
         }
         float contProb = 1.0f;
         const uint32_t len = __float_as_uint(d4.w);
@@ -283,13 +342,20 @@ __device__ __forceinline__ void mk_sample_bsdf(uint32_t *s_stack, State st, Scen
 __global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats)
 {
     __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    mk_sample_bsdf<false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, nullptr, 0u);
+    mk_sample_bsdf<false, false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, nullptr, 0u, MeshLights());
 }
 __global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf_list(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
                                                                   const uint32_t *list, uint32_t count)
 {
     __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    mk_sample_bsdf<true>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count);
+    mk_sample_bsdf<true, false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count, MeshLights());
+}
+template <bool LIST>
+__global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf_mesh(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
+                                                                  const uint32_t *list, uint32_t count, MeshLights ml)
+{
+    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
+    mk_sample_bsdf<LIST, true>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count, ml);
 }
 
 // (the list-driven instance is never a preview: flx_mk_splat_preview covers every pixel)
@@ -359,6 +425,20 @@ void launch_mk_sample_bsdf_list(hipStream_t s, const State &st, const Scene &sc,
 {
     uint32_t blocks = (count + MK_BLOCK - 1) / MK_BLOCK;
     hipLaunchKernelGGL(k_mk_sample_bsdf_list, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, count);
+}
+void launch_mk_next_vertex_mesh(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats, const MeshLights &ml,
+                                const uint32_t *list, uint32_t count)
+{
+    const uint32_t blocks = ((list ? count : mkThreads(st, p)) + MK_BLOCK - 1) / MK_BLOCK;
+    if (list) hipLaunchKernelGGL(k_mk_next_vertex_mesh<true>, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, count, ml);
+    else hipLaunchKernelGGL(k_mk_next_vertex_mesh<false>, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, 0u, ml);
+}
+void launch_mk_sample_bsdf_mesh(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats, const MeshLights &ml,
+                                const uint32_t *list, uint32_t count)
+{
+    const uint32_t blocks = ((list ? count : mkThreads(st, p)) + MK_BLOCK - 1) / MK_BLOCK;
+    if (list) hipLaunchKernelGGL(k_mk_sample_bsdf_mesh<true>, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, count, ml);
+    else hipLaunchKernelGGL(k_mk_sample_bsdf_mesh<false>, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, 0u, ml);
 }
 void launch_mk_splat_list(hipStream_t s, const State &st, const Frame &fr, const flx_render_params &p, uint32_t *stats, const uint32_t *list, uint32_t count)
 { hipLaunchKernelGGL(k_mk_splat_list, dim3((count + 255) / 256), dim3(256), 0, s, st, fr, p, stats, list, count); }

@@ -25,7 +25,8 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_denoise_variance_guided", "flx_gbuffer", "flx_history_capture", "flx_reproject", "flx_gbuffer_read", "flx_gbuffer_write",
            "flx_mk_adaptive_update", "flx_mk_adaptive_clear", "flx_mk_active_read", "flx_mk_active_write",
            "flx_update_triangles", "flx_update_triangles_subset", "flx_tree_read", "flx_tree_cost",
-           "flx_objects_define", "flx_objects_pose", "flx_objects_read", "flx_gbuffer_objects_read", "flx_gbuffer_objects_write"]
+           "flx_objects_define", "flx_objects_pose", "flx_objects_read", "flx_gbuffer_objects_read", "flx_gbuffer_objects_write",
+           "flx_mesh_lights_read", "flx_mesh_lights_sample"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
 K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with HipContext.denoise_profile (not part of profile_get)
@@ -217,6 +218,24 @@ class HipContext:
         members = np.zeros(int(counts.sum()), np.uint32)
         self._chk(self.L.flx_objects_read(self.h, _p(counts), C.byref(n), _p(members)))
         return counts, members
+
+    # emissive triangles as lights: set_option("mesh_lights", 1) (include/fluctus_hip.h)
+    def mesh_lights_read(self):
+        """flx_mesh_lights_read (blocking): (tris uint32 ascending, cdf float32, pick float32, total float64) -- the table of emissive triangles
+        as it stands on the device; host.mesh_light_table gives the same bytes on the CPU.  All empty when the scene has no light."""
+        n, total = C.c_uint32(), C.c_double()
+        self._chk(self.L.flx_mesh_lights_read(self.h, C.byref(n), None, None, None, C.byref(total)))
+        tri, cdf, pick = np.zeros(n.value, np.uint32), np.zeros(n.value, np.float32), np.zeros(n.value, np.float32)
+        self._chk(self.L.flx_mesh_lights_read(self.h, C.byref(n), _p(tri), _p(cdf), _p(pick), C.byref(total)))
+        return tri, cdf, pick, float(total.value)
+
+    def mesh_lights_sample(self, r3):
+        """test hook (blocking): ml_pick + ml_sample_triangle on the device for (n, 3) float32 triples (pick, r1, r2) ->
+        (light (n,) uint32, out8 (n, 8) float32 = P.xyz, pdfA, n_g.xyz, area)"""
+        r = np.ascontiguousarray(r3, np.float32).reshape(-1, 3)
+        light, out8 = np.zeros(r.shape[0], np.uint32), np.zeros((r.shape[0], 8), np.float32)
+        self._chk(self.L.flx_mesh_lights_sample(self.h, _p(r), C.c_uint32(r.shape[0]), _p(light), _p(out8)))
+        return light, out8
 
     TREE_ARRAYS = {0: ("bnodes", 64), 1: ("trirecs", 48), 2: ("shade", 64), 3: ("wnodes", 64), 4: ("wleaf", 16)}
 

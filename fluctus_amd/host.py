@@ -187,6 +187,50 @@ def pose_triangles(rest_tris, xform):
     return out
 
 
+def _tris_mats(d):
+    from .wire import TRIANGLE as T, MATERIAL as M
+    return np.ascontiguousarray(d.tris, T).reshape(-1), np.ascontiguousarray(d.materials, M).reshape(-1)
+
+
+def mesh_light_table(d):
+    """csrc/flx_mesh_light.h on the CPU -- what HipContext.mesh_lights_read returns for the same triangles and materials, byte for byte:
+    (tris uint32 ascending, cdf float32, pick float32, total float64) of the emissive triangles of d; four empty / zero results when d has no
+    light (no emissive triangle with a positive weight)."""
+    t, m = _tris_mats(d)
+    n, total = C.c_uint32(), C.c_double()
+    _chk(lib().fh_mesh_light_table(_p(t), C.c_uint64(t.size), _p(m), C.c_uint64(m.size), C.byref(n), None, None, None, C.byref(total)))
+    tri, cdf, pick = np.zeros(n.value, np.uint32), np.zeros(n.value, np.float32), np.zeros(n.value, np.float32)
+    _chk(lib().fh_mesh_light_table(_p(t), C.c_uint64(t.size), _p(m), C.c_uint64(m.size), C.byref(n), _p(tri), _p(cdf), _p(pick), C.byref(total)))
+    return tri, cdf, pick, float(total.value)
+
+
+def mesh_light_pick(cdf, pick, r):
+    """ml_pick of csrc/flx_mesh_light.h over a table: the light picked for every r (float32)"""
+    cdf, pick = np.ascontiguousarray(cdf, np.float32), np.ascontiguousarray(pick, np.float32)
+    r = np.ascontiguousarray(r, np.float32).reshape(-1)
+    out = np.zeros(r.size, np.uint32)
+    _chk(lib().fh_mesh_light_pick(_p(cdf), _p(pick), C.c_uint32(cdf.size), _p(r), C.c_uint64(r.size), _p(out)))
+    return out
+
+
+def mesh_light_find(tris, query):
+    """ml_find of csrc/flx_mesh_light.h: the position of every queried triangle in the ascending list, 0xFFFFFFFF = not a light"""
+    lst, q = np.ascontiguousarray(tris, np.uint32), np.ascontiguousarray(query, np.uint32).reshape(-1)
+    out = np.zeros(q.size, np.uint32)
+    _chk(lib().fh_mesh_light_find(_p(lst), C.c_uint32(lst.size), _p(q), C.c_uint64(q.size), _p(out)))
+    return out
+
+
+def mesh_light_sample(d, r3):
+    """What HipContext.mesh_lights_sample computes on the device, on the CPU: r3 (n, 3) float32 triples (pick, r1, r2) ->
+    (light (n,) uint32, out8 (n, 8) float32 = P.xyz, pdfA, n_g.xyz, area, bary (n, 3) float32 the coefficients of P)"""
+    t, m = _tris_mats(d)
+    r = np.ascontiguousarray(r3, np.float32).reshape(-1, 3)
+    light, out8, bary = np.zeros(r.shape[0], np.uint32), np.zeros((r.shape[0], 8), np.float32), np.zeros((r.shape[0], 3), np.float32)
+    _chk(lib().fh_mesh_light_sample(_p(t), C.c_uint64(t.size), _p(m), C.c_uint64(m.size), _p(r), C.c_uint64(r.shape[0]), _p(light), _p(out8), _p(bary)))
+    return light, out8, bary
+
+
 def _bvh_arrays(h):
     """(nodes, indices, world radius) of a BVH handle"""
     L = lib()

@@ -18,7 +18,7 @@ struct HipContext::Api {
     FN(flx_mk_stats_async) FN(flx_mk_stats_reset) FN(flx_set_option) FN(flx_get_option) FN(flx_group_init_local) FN(flx_gather_local)
     FN(flx_denoise) FN(flx_denoise_variance_guided) FN(flx_gbuffer) FN(flx_history_capture) FN(flx_reproject)
     FN(flx_mk_adaptive_update) FN(flx_mk_adaptive_clear) FN(flx_update_triangles) FN(flx_update_triangles_subset) FN(flx_tree_cost) FN(flx_tree_read)
-    FN(flx_objects_define) FN(flx_objects_pose)
+    FN(flx_objects_define) FN(flx_objects_pose) FN(flx_mesh_lights_read)
 #undef FN
 };
 
@@ -48,7 +48,7 @@ HipContext::HipContext(int device, uint32_t numTasks, const std::string &libPath
     BIND(flx_mk_stats_async) BIND(flx_mk_stats_reset) BIND(flx_set_option) BIND(flx_get_option) BIND(flx_group_init_local) BIND(flx_gather_local)
     BIND(flx_denoise) BIND(flx_denoise_variance_guided) BIND(flx_gbuffer) BIND(flx_history_capture) BIND(flx_reproject)
     BIND(flx_mk_adaptive_update) BIND(flx_mk_adaptive_clear) BIND(flx_update_triangles) BIND(flx_update_triangles_subset) BIND(flx_tree_cost) BIND(flx_tree_read)
-    BIND(flx_objects_define) BIND(flx_objects_pose)
+    BIND(flx_objects_define) BIND(flx_objects_pose) BIND(flx_mesh_lights_read)
 #undef BIND
     if (api->flx_create(device, numTasks, &ctx) != 0)
         throw std::runtime_error(std::string("HipContext: ") + api->flx_last_error(nullptr));
@@ -94,6 +94,12 @@ void HipContext::poseObjects(const std::vector<uint32_t> &ids, const std::vector
 {
     if (xforms12.size() != ids.size() * 12) throw std::runtime_error("poseObjects: twelve floats per listed object");
     check(api->flx_objects_pose(ctx, ids.data(), xforms12.data(), (uint32_t)ids.size()), "poseObjects");
+}
+uint32_t HipContext::meshLightCount()
+{
+    uint32_t n = 0;
+    check(api->flx_mesh_lights_read(ctx, &n, nullptr, nullptr, nullptr, nullptr), "meshLightCount");
+    return n;
 }
 std::array<double, 8> HipContext::treeCost()
 {

@@ -42,6 +42,7 @@ public:
     // flx_tree_cost: {A_root, S_node, S_leaf, S_tri} of the binary tree [0..3] and of the 4-wide tree [4..7] as they stand on the device (blocking);
     // flxTreeCostValue (include/fluctus_hip.h) turns four of them into one figure
     std::array<double, 8> treeCost();
+    uint32_t meshLightCount();                                 // flx_mesh_lights_read: the emissive triangles listed as lights (option "mesh_lights" on)
     void treeRead(int which, std::vector<uint8_t> &out);          // flx_tree_read (test hook): device array `which` of the uploaded scene
     void createEnvMap(EnvironmentMap *map);                       // src/clcontext.cpp:467-511
     void updateParams(const RenderParams &params);                // src/clcontext.cpp:703-707

@@ -13,6 +13,7 @@
 #include "../csrc/flx_refit.h"     // the refit's fp64 quantiser compiles for the host too: the CPU tests run what the kernels run
 #include "../csrc/flx_tree_cost.h" // the cost sums of flx_tree_cost, likewise
 #include "../csrc/flx_pose.h"      // the pose arithmetic of flx_objects_pose, likewise
+#include "../csrc/flx_mesh_light.h" // the table of emissive triangles (option "mesh_lights"), likewise
 #include "../csrc/flx_wide.h"      // the 4-wide tree builder is plain host C++ (flx_upload_scene runs it); exposed here for CPU-side tests
 #include <cstring>
 #include <string>
@@ -249,6 +250,81 @@ int fh_pose_triangles(const void *in160, void *out160, uint64_t count, const flo
     FH_TRY
     if (!xform12 || (count && (!in160 || !out160))) throw std::runtime_error("fh_pose_triangles: null argument");
     flx::ps_pose_triangles(xform12, in160, out160, (size_t)count);
+    FH_CATCH
+}
+// ---- emissive triangles as lights on the CPU (csrc/flx_mesh_light.h: the functions the kernels run, in the order the kernels sum)
+// the ascending list of the triangles whose material emits
+static std::vector<uint32_t> meshLightList(const flx_triangle *t, uint64_t ntris, const flx_material *m, uint64_t nmat)
+{
+    std::vector<uint32_t> list;
+    for (uint64_t i = 0; i < ntris; i++) {
+        if (t[i].matId < 0 || (uint64_t)t[i].matId >= nmat) throw std::runtime_error("fh_mesh_light: triangle material id out of range");
+        const flx_vec3 &ke = m[t[i].matId].Ke;
+        if (flxml::ml_is_emissive(ke.x, ke.y, ke.z)) list.push_back((uint32_t)i);
+    }
+    return list;
+}
+static flx::f3 meshLightVertex(const flx_triangle &t, int v) { const flx_vertex &x = v == 0 ? t.v0 : v == 1 ? t.v1 : t.v2; return flx::mk3(x.p.x, x.p.y, x.p.z); }
+struct MeshLightTable { std::vector<uint32_t> list; std::vector<float> cdf, pick; double total = 0.0; uint32_t lastPick = ML_NONE; };
+static MeshLightTable meshLightTable(const flx_triangle *t, uint64_t ntris, const flx_material *m, uint64_t nmat)
+{
+    MeshLightTable T;
+    T.list = meshLightList(t, ntris, m, nmat);
+    const uint32_t n = (uint32_t)T.list.size();
+    T.cdf.assign(n, 0.0f); T.pick.assign(n, 0.0f);
+    T.total = flxml::ml_build_table(T.list.data(), n, [&](uint32_t i, int v) { return meshLightVertex(t[i], v); },
+                                    [&](uint32_t i) { const flx_vec3 &ke = m[t[i].matId].Ke; return flx::mk3(ke.x, ke.y, ke.z); }, T.cdf.data(), T.pick.data(), &T.lastPick);
+    return T;
+}
+// what flx_mesh_lights_read returns for the same triangles and materials, byte for byte; null arrays = the count only
+int fh_mesh_light_table(const void *tris160, uint64_t ntris, const void *mats80, uint64_t nmat, uint32_t *outCount, uint32_t *outTris, float *outCdf, float *outPick,
+                        double *outTotal)
+{
+    FH_TRY
+    const MeshLightTable T = meshLightTable((const flx_triangle *)tris160, ntris, (const flx_material *)mats80, nmat);
+    const size_t n = T.total > 0.0 ? T.list.size() : 0;
+    if (outCount) *outCount = (uint32_t)n;
+    if (outTotal) *outTotal = T.total;
+    if (n && outTris) memcpy(outTris, T.list.data(), n * 4);
+    if (n && outCdf) memcpy(outCdf, T.cdf.data(), n * 4);
+    if (n && outPick) memcpy(outPick, T.pick.data(), n * 4);
+    FH_CATCH
+}
+// ml_pick over a given table for m values of r (lastPick: the last entry of pick that is > 0); ml_find over a given list for m triangles
+int fh_mesh_light_pick(const float *cdf, const float *pick, uint32_t n, const float *r, uint64_t m, uint32_t *out)
+{
+    FH_TRY
+    uint32_t lastPick = ML_NONE;
+    for (uint32_t k = 0; k < n; k++) if (pick[k] > 0.0f) lastPick = k;
+    if (lastPick == ML_NONE) throw std::runtime_error("fh_mesh_light_pick: the table has no light with pick > 0");
+    for (uint64_t i = 0; i < m; i++) out[i] = flxml::ml_pick(cdf, n, lastPick, r[i]);
+    FH_CATCH
+}
+int fh_mesh_light_find(const uint32_t *list, uint32_t n, const uint32_t *tri, uint64_t m, uint32_t *out)
+{
+    FH_TRY
+    for (uint64_t i = 0; i < m; i++) out[i] = flxml::ml_find(list, n, tri[i]);
+    FH_CATCH
+}
+// what flx_mesh_lights_sample returns: m triples (pick, r1, r2) -> the light, out8 = {P.xyz, pdfA, n_g.xyz, area}, and (where not null) the
+// three barycentric coefficients of P
+int fh_mesh_light_sample(const void *tris160, uint64_t ntris, const void *mats80, uint64_t nmat, const float *r3, uint64_t m, uint32_t *outLight, float *out8, float *outBary3)
+{
+    FH_TRY
+    const flx_triangle *t = (const flx_triangle *)tris160;
+    const MeshLightTable T = meshLightTable(t, ntris, (const flx_material *)mats80, nmat);
+    if (T.lastPick == ML_NONE) throw std::runtime_error("fh_mesh_light_sample: the scene has no light (no emissive triangle with a positive weight)");
+    for (uint64_t i = 0; i < m; i++) {
+        const uint32_t k = flxml::ml_pick(T.cdf.data(), (uint32_t)T.list.size(), T.lastPick, r3[3 * i]);
+        const flx_triangle &tr = t[T.list[k]];
+        const flx::f3 p0 = meshLightVertex(tr, 0), p1 = meshLightVertex(tr, 1), p2 = meshLightVertex(tr, 2);
+        const flx::f3 P = flxml::ml_sample_triangle(p0, p1, p2, r3[3 * i + 1], r3[3 * i + 2]), ng = flxml::ml_normal(p0, p1, p2);
+        const float area = flxml::ml_area(p0, p1, p2);
+        outLight[i] = k;
+        float *o = out8 + 8 * i;
+        o[0] = P.x; o[1] = P.y; o[2] = P.z; o[3] = flxml::ml_pdf_area(T.pick[k], area); o[4] = ng.x; o[5] = ng.y; o[6] = ng.z; o[7] = area;
+        if (outBary3) { const flx::f3 b = flxml::ml_bary(r3[3 * i + 1], r3[3 * i + 2]); outBary3[3 * i] = b.x; outBary3[3 * i + 1] = b.y; outBary3[3 * i + 2] = b.z; }
+    }
     FH_CATCH
 }
 // Scene::objectOfTriangle / objectNames: ids (room for the scene's triangles) and the names joined by '\n' (*needed: bytes incl. the final 0)
@@ -501,6 +577,8 @@ int fh_tracer_get_temporal_reprojection(void *t) { return ((Tracer *)t)->getTemp
 int fh_tracer_set_motion_reprojection(void *t, int on) { FH_TRY ((Tracer *)t)->setMotionReprojection(on != 0); FH_CATCH }
 int fh_tracer_get_motion_reprojection(void *t) { return ((Tracer *)t)->getMotionReprojection() ? 1 : 0; }
 int fh_tracer_set_max_history(void *t, float n) { FH_TRY ((Tracer *)t)->setMaxHistory(n); FH_CATCH }
+int fh_tracer_set_mesh_lights(void *t, int on) { FH_TRY ((Tracer *)t)->setMeshLights(on != 0); FH_CATCH }
+int fh_tracer_mesh_light_count(void *t, uint32_t *out) { FH_TRY *out = ((Tracer *)t)->meshLightCount(); FH_CATCH }
 int fh_tracer_toggle_renderer(void *t) { FH_TRY ((Tracer *)t)->toggleRenderer(); FH_CATCH }
 int fh_tracer_uses_wavefront(void *t) { return ((Tracer *)t)->usesWavefront() ? 1 : 0; }
 int fh_tracer_stats(void *t, uint64_t *out4)

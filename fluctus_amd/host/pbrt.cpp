@@ -121,7 +121,7 @@ struct Params {
     std::string tex(const std::string &name) const { const Param *p = find(name); return p && p->type == "texture" && !p->strs.empty() ? p->strs[0] : std::string(); }
 };
 
-struct PMaterial { std::string type; Params params; };
+struct PMaterial { std::string type; Params params; V3 Ke{}; };         // Ke: the AreaLightSource the shape was made under (L * scale), else 0
 typedef std::shared_ptr<PMaterial> MatRef;
 struct PTexture { std::string cls, filename; };
 
@@ -132,7 +132,8 @@ struct Mesh {                                   // one trianglemesh / plymesh, o
 struct Instance { std::string object; M4 xform; };
 struct Object { std::vector<Mesh> meshes; std::vector<Instance> instances; };
 
-struct GState { M4 ctm = M4::identity(); MatRef material; };
+// areaLight: AreaLightSource "diffuse" is part of the attribute state, like the material (pbrt-v3 s. B.3.4): pushed and popped with it
+struct GState { M4 ctm = M4::identity(); MatRef material; bool areaLight = false; V3 L{}; };
 
 // ---- PLY (plymesh): ascii / binary_little_endian / binary_big_endian; x y z [nx ny nz] [u v | s t]; faces as index lists
 void loadPlyMesh(const std::string &path, Mesh &mesh)
@@ -261,9 +262,22 @@ struct Parser {
         if (bracket && t.kind != Token::RBracket) throw std::runtime_error(lx.file + ": expected ] at line " + std::to_string(lx.line));
     }
 
+    // a copy of `base` (none: the default material's parameters) that emits Ke; one copy per (material, Ke), so a lamp of many shapes is one material
+    struct Emissive { MatRef base; V3 Ke; MatRef copy; };
+    std::vector<Emissive> emissives;
+    MatRef emissive(const MatRef &base, const V3 &Ke)
+    {
+        for (const Emissive &e : emissives) if (e.base == base && e.Ke.x == Ke.x && e.Ke.y == Ke.y && e.Ke.z == Ke.z) return e.copy;
+        auto m = std::make_shared<PMaterial>();
+        if (base) *m = *base; else m->type = "default";
+        m->Ke = Ke;
+        emissives.push_back({base, Ke, m});
+        return m;
+    }
+
     void addShape(const std::string &type, const Params &ps)
     {
-        Mesh mesh; mesh.xform = gs.ctm; mesh.material = gs.material;
+        Mesh mesh; mesh.xform = gs.ctm; mesh.material = gs.areaLight ? emissive(gs.material, gs.L) : gs.material;
         if (type == "trianglemesh") {
             const Param *P = ps.find("P"), *I = ps.find("indices"), *N = ps.find("N"), *UV = ps.find("uv");
             if (!UV) UV = ps.find("st");
@@ -355,9 +369,17 @@ struct Parser {
                 (void)n; (void)ps;
                 if (!haveCamera) { cameraToWorld = gs.ctm.inverse(); haveCamera = true; }
                 namedCS["camera"] = cameraToWorld;
+            } else if (d == "AreaLightSource") {
+                // "diffuse" with "rgb L" / "color L" (default 1 1 1) and an optional "float scale": the shapes made under it emit Ke = L * scale
+                // on the side their geometric normal faces (option "mesh_lights").  "twosided" is IGNORED: lamps are one-sided.
+                Token n = lx.next(); Params ps = readParams(lx, look); haveLook = true;
+                if (n.text == "diffuse" || n.text == "area") {
+                    const V3 L = ps.rgb("L", {1.0f, 1.0f, 1.0f}); const float sc = ps.f("scale", 1.0f);
+                    gs.areaLight = true; gs.L = {L.x * sc, L.y * sc, L.z * sc};
+                }
             } else if (d == "MediumInterface") { Token a = lx.next(); look = lx.next(); if (look.kind == Token::String) look = lx.next(); haveLook = true; (void)a; }
             else {
-                // Film, Sampler, Integrator, PixelFilter, Accelerator, LightSource, AreaLightSource, MakeNamedMedium, ...:
+                // Film, Sampler, Integrator, PixelFilter, Accelerator, LightSource, MakeNamedMedium, ...:
                 // one type string + a parameter list, none of which reaches the triangle / material arrays
                 Token n = lx.next(); (void)n;
                 (void)readParams(lx, look); haveLook = true;
@@ -453,6 +475,7 @@ struct Parser {
                 m.Ni = (eta.x + eta.y + eta.z) / 3.0f; m.Ks = W(ps.rgb("k", {1.0f, 1.0f, 1.0f}));
                 m.Ns = rough(ps.f("roughness", 0.01f), ps.b("remaproughness", true), ps.f("uroughness", 0.0f), ps.f("vroughness", 0.0f));
             }                                                                                  // fourier, hair, ...: default material (:807-818)
+            m.Ke = W(pm->Ke);
             scene.addMaterial(m);
         }
     }

@@ -371,6 +371,20 @@ bool Tracer::onlyCameraChanged(bool posed) const
     return std::memcmp(a, b, offsetof(RenderParams, camera)) == 0 &&
            std::memcmp(a + offsetof(RenderParams, width), b + offsetof(RenderParams, width), sizeof(RenderParams) - offsetof(RenderParams, width)) == 0;
 }
+void Tracer::toggleRenderer()
+{
+    if (!useWavefront && meshLightsOn)
+        throw std::runtime_error("toggleRenderer: mesh lights are on and the wavefront integrator does not see emissive triangles -- the scene's lamps would go dark; setMeshLights(false) first");
+    useWavefront = !useWavefront; iteration = 0; dropHistory();
+}
+void Tracer::setMeshLights(bool on)
+{
+    if (on && !peers.empty()) throw std::runtime_error("setMeshLights: emissive triangles light the microkernel integrator, which is single-GPU");
+    if (on && useWavefront) toggleRenderer();                            // as renderSingle does
+    clctx->setOption("mesh_lights", on ? 1 : 0);
+    meshLightsOn = on;
+    iteration = 0; dropHistory();                                        // the accumulation was lit differently
+}
 void Tracer::setMaxHistory(float n)
 {
     if (!(n >= 1.0f) || !std::isfinite(n)) throw std::runtime_error("setMaxHistory: must be finite and >= 1");

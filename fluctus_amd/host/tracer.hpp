@@ -124,7 +124,13 @@ public:
     void setMotionReprojection(bool on);
     bool getMotionReprojection() const { return motionOn; }
     float getMaxHistory() const { return maxHistory; }
-    void toggleRenderer() { useWavefront = !useWavefront; iteration = 0; dropHistory(); }   // src/tracer.cpp:881-886 (no history across integrators)
+    // Emissive triangles as lights, default off: only the microkernel integrator sees them, so while this is on update() takes
+    // its microkernel branch (as renderSingle forces it) and toggleRenderer() to the wavefront loop THROWS -- lamps never go silently dark.
+    // Single-GPU like that integrator: throws on a multi-rank Tracer.  meshLightCount: the lights listed on the device (throws while off).
+    void setMeshLights(bool on);
+    bool getMeshLights() const { return meshLightsOn; }
+    uint32_t meshLightCount() { return clctx->meshLightCount(); }
+    void toggleRenderer();                                                        // src/tracer.cpp:881-886 (no history across integrators)
     void setOption(const std::string &name, int value) { for (auto *c : ranks()) c->setOption(name, value); }   // every rank (HipContext::setOption)
     bool usesWavefront() const { return useWavefront; }
     void saveImage(const std::string &filename) { clctx->saveImage(filename, params); }
@@ -202,6 +208,7 @@ private:
     uint32_t gbWidth = 0, gbHeight = 0;                                           // ... traced at this size
     uint32_t framesSinceGbuffer = 0;                                              // > 0: there is an accumulation worth capturing
     uint32_t temporalFrames = 0;                                                  // frames since the last discarded history (the denoiser schedule while temporalOn)
+    bool meshLightsOn = false;
     bool useWavefront = true;                                                     // this library's default; the reference starts on MK (src/tracer.cpp:11)
     QueueCounters lastCnt {};
     std::string sceneName;

@@ -232,6 +232,17 @@ class Tracer:
         """HipContext::setOption -> flx_set_option (e.g. "extend_tree", 2 for the reference's bit-exact visit order)."""
         host._chk(self.L.fh_tracer_set_option(self.h, name.encode(), int(value)))
 
+    def set_mesh_lights(self, on):
+        """Tracer::setMeshLights (default off): the scene's emissive triangles light the microkernel integrator (DESIGN.md 4.2.2).  While on,
+        update() renders with that integrator and toggle_renderer() to the wavefront loop raises.  Single-GPU."""
+        host._chk(self.L.fh_tracer_set_mesh_lights(self.h, int(bool(on))))
+
+    def mesh_light_count(self):
+        """Tracer::meshLightCount: the emissive triangles listed as lights on the device (raises while mesh lights are off)"""
+        n = C.c_uint32()
+        host._chk(self.L.fh_tracer_mesh_light_count(self.h, C.byref(n)))
+        return int(n.value)
+
     def toggle_renderer(self):
         host._chk(self.L.fh_tracer_toggle_renderer(self.h))
 

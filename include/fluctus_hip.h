@@ -96,6 +96,22 @@ int flx_update_triangles_subset(flx_ctx *ctx, const void *tris160, const uint32_
 int flx_objects_define(flx_ctx *ctx, const void *tris160_rest, size_t ntris, const uint32_t *object_of_triangle, uint32_t nobjects);
 int flx_objects_pose(flx_ctx *ctx, const uint32_t *object_ids, const float *xforms12, uint32_t count);
 int flx_objects_read(flx_ctx *ctx, uint32_t *out_counts, uint32_t *out_nobjects, uint32_t *out_members);
+/* Emissive triangles as lights (csrc/flx_mesh_light.h, csrc/mesh_light.hip): flx_set_option(ctx, "mesh_lights", 1), default 0,
+ * readable through flx_get_option.  While it is on, every triangle whose material has a Ke component > 0 is a one-sided light (it emits Ke on the
+ * side its geometric normal (p1 - p0) x (p2 - p0) faces) for the MICROKERNEL integrator: flx_mk_next_vertex collects the emission of a hit,
+ * flx_mk_sample_bsdf samples one light per vertex from a table by power (area x luminance(Ke)), both MIS-weighted as the parametric quad is; the
+ * list-driven (adaptive) instances do the same.  The table is built on the stream when the option is switched on and rebuilt at the end of every
+ * call that moves triangles -- flx_upload_scene, flx_update_triangles, flx_update_triangles_subset, flx_objects_pose -- so the next sample sees the
+ * lamps where and as large as they are.  The option survives flx_upload_scene.  With the option off, or on with no emissive triangle, every entry
+ * point launches the kernels it launches without it and returns the same bits.  THE flx_wf_* CALLS IGNORE THE OPTION: the wavefront integrator
+ * does not see emissive triangles.
+ * flx_mesh_lights_read, blocking: *out_count = the lights listed (0 when their total weight is 0: no lights), and where not NULL (room for the
+ * count a first call reported) out_tris = their ascending triangle indices, out_cdf / out_pick = the table, *out_total = the fp64 total weight.
+ * flx_mesh_lights_sample: test hook beside flx_math_probe, blocking.  r3 = n triples (pick, r1, r2) of host floats; out_light[i] = the light picked,
+ * out8 + 8 i = {P.xyz, pdfA, n_g.xyz, area} of the point sampled on it.  Fails when the table holds no light.
+ * Both fail, with a message, while the option is off or no scene is uploaded. */
+int flx_mesh_lights_read(flx_ctx *ctx, uint32_t *out_count, uint32_t *out_tris, float *out_cdf, float *out_pick, double *out_total);
+int flx_mesh_lights_sample(flx_ctx *ctx, const float *r3, uint32_t n, uint32_t *out_light, float *out8);
 /* test hook, blocking: one device array of the uploaded scene as it is now.  which = 0 the binary tree's 64-byte inner-node records, 1 the
  * 48-byte leaf triangle records (index-list order), 2 the 64-byte shading records, 3 the 64-byte nodes of the 4-wide tree, 4 its leaf data
  * (16-byte units).  *needed = the array's size in bytes; out NULL only reports it, otherwise bytes must be at least that. */
