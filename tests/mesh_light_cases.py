@@ -116,11 +116,53 @@ def degenerate_lamps_scene():
 FLOOR = quad((0.0, 0.0, 0.0), (1.0, 0.0, 0.0), (0.0, 0.0, 1.0), 2.0, 2.0, 0, (0.0, 1.0, 0.0))
 
 
-def lamp_field(nlights=SCAN_BLOCK + 3, seed=5):
+# the materials of lamp_field(steps=...): TABLE_MATS, two more emitters and a receiver of every BSDF type but the floor's
+STEP_DIM, STEP_DOMINANT, STEP_GLOSSY, STEP_GGX_REFL, STEP_GGX_REFR, STEP_MIRROR, STEP_DIELECTRIC = range(5, 12)
+STEP_MATS = TABLE_MATS + [emissive((1e-6, 1e-6, 1e-6)), emissive((40.0, 50.0, 30.0)),
+                          common.make_material(BXDF.GLOSSY, kd=(0.2, 0.5, 0.7), ks=(0.3, 0.3, 0.3), ns=300.0, ni=1.5),
+                          common.make_material(BXDF.GGX_ROUGH_REFLECTION, ks=(0.9, 0.8, 0.5), ns=60.0, ni=1.5),
+                          common.make_material(BXDF.GGX_ROUGH_DIELECTRIC, ks=(0.95, 0.9, 0.85), ns=40.0, ni=1.5),
+                          common.make_material(BXDF.IDEAL_REFLECTION, ks=(0.9, 0.9, 0.9)),
+                          common.make_material(BXDF.IDEAL_DIELECTRIC, ks=(0.9, 0.95, 1.0), ni=1.5)]
+STEP_RECEIVER_MATS = (0, STEP_GLOSSY, STEP_GGX_REFL, STEP_GGX_REFR, STEP_MIRROR, STEP_DIELECTRIC)
+
+
+def _step_extras(tris, obj, lamps, names):
+    """the part of lamp_field that tests/mesh_light_step_cases.py aims at, beside the floor (x in 2.4 .. 6.2): six receiver quads at y = 0,
+    one per BSDF type, under lamps that face down unless said otherwise.  `names` receives the triangle indices by name."""
+    def add(name, new, lamp):
+        names[name] = list(range(len(tris), len(tris) + len(new)))
+        if lamp:
+            lamps.extend(names[name])
+        tris.extend(new); obj.extend([NO_OBJECT] * len(new))
+    X, Z, DOWN, UP = (1.0, 0.0, 0.0), (0.0, 0.0, 1.0), (0.0, -1.0, 0.0), (0.0, 1.0, 0.0)
+    for j, m in enumerate(STEP_RECEIVER_MATS):
+        add(f"receiver{j}", quad((2.75 + 0.6 * j, 0.0, 0.0), X, Z, 0.25, 0.6, m, UP), False)
+    add("back", quad((2.8, 1.4, 0.1), X, Z, 0.2, 0.2, 1, UP), True)                  # shows the receivers its back
+    add("half", quad((3.5, 1.5, 0.0), X, Z, 0.25, 0.25, 2, DOWN), True)               # half of it (x > 3.5) behind a plate that is no light
+    add("half_plate", quad((3.8, 1.2, 0.0), X, Z, 0.3, 0.5, 0, DOWN), False)
+    add("front", quad((4.3, 1.3, 0.0), X, Z, 0.15, 0.15, 1, DOWN), True)              # a lamp in front of a larger lamp
+    add("behind", quad((4.3, 1.6, 0.0), X, Z, 0.3, 0.3, 2, DOWN), True)
+    add("veiled", quad((5.0, 1.5, 0.0), X, Z, 0.2, 0.2, 1, DOWN), True)               # a plate 3 mm before it: past 0.995 |L| from the receivers
+    add("veil", quad((5.0, 1.497, 0.0), X, Z, 0.4, 0.4, 0, DOWN), False)
+    add("gains", [tri((5.4, 1.2, 0.3), (5.4, 1.2, -0.3), (5.9, 1.2, 0.0), 0)], False)  # gets an emissive matId after the upload: seen, never listed
+    add("quad_lamp", quad((5.7, 1.7, 0.0), X, Z, 0.2, 0.2, 2, DOWN), True)            # the parametric quad is put before this one
+    add("tiny", [tri((3.0, 1.8, 0.5), (3.05, 1.8, 0.5), (3.0, 1.8, 0.45), STEP_DIM)], True)             # pick rounds to 0 ...
+    add("dominant", quad((3.1, 1.8, -0.1), X, Z, 0.5, 0.5, STEP_DOMINANT, DOWN), True)                   # ... beside the light that outweighs the field
+    add("last", [tri((4.0, 1.9, 0.5), (4.05, 1.9, 0.5), (4.0, 1.9, 0.45), STEP_DIM)], True)             # the last light: cdf 1, pick 0
+    for name in ("half", "front", "veiled", "quad_lamp", "dominant"):                 # shading normals that lean 30 degrees off n_g: a light's side,
+        for i in names[name]:                                                         # cosine and pdf are the GEOMETRIC normal's business
+            for v in ("v0", "v1", "v2"):
+                tris[i][v]["n"]["x"], tris[i][v]["n"]["y"], tris[i][v]["n"]["z"] = 0.5, float(tris[i][v]["n"]["y"]) * np.sqrt(0.75), 0.0
+
+
+def lamp_field(nlights=SCAN_BLOCK + 3, seed=5, steps=None):
     """a floor under `nlights` emissive triangles of four objects (lamp j belongs to object j % 4; the floor and the Ke = 0 triangles to none),
     sizes over two decades; one run of the prefix sums plus three lights by default, so that the seam between two runs is crossed.  The lamps
     are right-angled: their fp32 area is then within an ulp or two of the real one, which the sampling test's 4 ulp on pdfA presumes (a thin
     triangle's cross product cancels, and no fp32 area is close to the float64 one; tests/test_mesh_lights.py has those).
+    steps (a dict, filled with name -> triangle indices): the same field with STEP_MATS and, behind it in the list, the arrangements of
+    _step_extras -- the scene of the per-path tests of the integrator's two vertex steps.
     Returns (scene with hierarchy, object_of_triangle, lamp triangle indices)."""
     rng = np.random.RandomState(seed)
     tris, obj, lamps = list(FLOOR), [NO_OBJECT, NO_OBJECT], []
@@ -129,7 +171,9 @@ def lamp_field(nlights=SCAN_BLOCK + 3, seed=5):
             tris.append(_random_tri(rng, 0.2, 3)); obj.append(NO_OBJECT)
         lamps.append(len(tris))
         tris.append(_random_tri(rng, 10.0 ** rng.uniform(-2.0, -0.3), 1 + j % 2, right_angle=True)); obj.append(j % 4)
-    return scene(tris, TABLE_MATS), np.array(obj, np.uint32), np.array(lamps, np.uint32)
+    if steps is not None:
+        _step_extras(tris, obj, lamps, steps)
+    return scene(tris, TABLE_MATS if steps is None else STEP_MATS), np.array(obj, np.uint32), np.array(lamps, np.uint32)
 
 
 # ---- the rendered scenes: a floor, a box that shadows part of it, one diffuse and one glossy material, no singular one
