@@ -104,9 +104,13 @@ FLX_HD float atanf_(float x)
 
 FLX_HD float atan2f_(float y, float x)
 {
-    if (x == 0.0f) return y > 0.0f ? FLX_PIO2 : (y < 0.0f ? -FLX_PIO2 : 0.0f);
+    /* the signed zeros as OpenCL 1.2 s7.5.1 (= C99 F.9.1.4) has them: atan2(+-0, -0) = +-pi, atan2(+-0, +0) = +-0, atan2(+-0, x < 0) = +-pi.
+     * directionToUV (src/env_map.cl:19) meets them on exact axis directions: a ray along +-y has x = 0 and -z = -+0, one along +z with x = -0
+     * lies on the u = 0 side of the seam (tests/logic_step_cases.py: the miss group). */
+    const bool yneg = (f2u(y) >> 31) != 0u;
+    if (x == 0.0f) return y > 0.0f ? FLX_PIO2 : (y < 0.0f ? -FLX_PIO2 : ((f2u(x) >> 31) != 0u ? (yneg ? -FLX_PI : FLX_PI) : y));
     float z = atanf_(y / x);
-    if (x < 0.0f) z = (y < 0.0f) ? z - FLX_PI : z + FLX_PI;
+    if (x < 0.0f) z = yneg ? z - FLX_PI : z + FLX_PI;
     return z;
 }
 

@@ -601,7 +601,7 @@ def test_prepared_regeneration_is_bit_identical_to_genrays(workload):
     """Option `regen_prep` (default on; logic.hip: PREPARED REGENERATION): the fused RAW pass computes the seed-only half of genRays for its terminating lanes
     (jitter, thin-lens origin, throughput + new seed, the reset scalars: stored with its full-line stores) and the k_raygen of the chain only the direction and
     the pixel -- against the whole of genRays in k_raygen.  Two contexts free-run the workload at 1 M paths: counters after every iteration, the whole state after
-    3 and 12 iterations (the first export happens right behind a chain that used the split), the framebuffers."""
+    3 and 6 iterations (the first export happens right behind a chain that used the split) and once more behind the chain after the 12th, the framebuffers."""
     from fluctus_amd.device import HipContext
     import bench
     d, p, env = bench.build_workload(name=workload)
