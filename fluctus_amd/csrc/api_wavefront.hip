@@ -86,7 +86,8 @@ static int runLogic(flx_ctx *c, int first, int fused, int raygenFirst)
     c->prepDone = prep != 0;
     if (++c->logicEpoch == 0u) c->logicEpoch = 1u;     // (epoch 0 = the zero-filled words of a fresh context)
     { ScopedTimer t(c, fused ? FLX_K_LOGIC_FUSED : FLX_K_LOGIC); launch_logic(c->stream, c->st, c->qs, c->sc, c->fr, c->params, c->member, c->blockCounts, c->blockOffsets, first, fused, raygenFirst, order, raw,
-                                                                                c->lookback, c->logicEpoch, regen ? 1 : (prep ? 2 : 0), order == 2 ? 0 : 1, c->logicError, c->regroup); }
+                                                                                c->lookback, c->logicEpoch, regen ? 1 : (prep ? 2 : 0), order == 2 ? 0 : 1, c->logicError, c->regroup,
+                                                                                (!fused && c->ml.state.litWavefront()) ? &c->ml.t : nullptr); }      // the lamps light this pass: its MESH instance
     LAUNCHED(c);
     c->matQueuesEmpty = false; c->raygenQueueEmpty = false;
     if (c->overlap == 2) HIPCHK(c, hipEventRecord(c->evPostLogic, c->stream));
@@ -215,7 +216,9 @@ int flx_wf_logic(flx_ctx *c, int first)
     const uint32_t allMat = (1u << FLX_Q_DIFFUSE) | (1u << FLX_Q_GLOSSY) | (1u << FLX_Q_GGX_REFL) | (1u << FLX_Q_GGX_REFR) | (1u << FLX_Q_DELTA);
     // (with a single material queue every BSDF type sits in the diffuse list: only a pass that inlines them all can serve it)
     const bool fusable = c->params.wfSeparateQueues || fused_queue_mask(fuseSetNow(c)) == allMat;      // (always: see fuseSetNow)
-    if (c->fuse && c->matQueuesEmpty && fusable) { c->phase = PH_DEFER_LOGIC; c->pendFirst = first; }
+    // ... and not while the lamps light this integrator (option "mesh_lights_wavefront"): only the plain pass has a MESH instance, so the chain is the
+    // unfused one whatever "fuse" says -- RAW records committed first, the separate material kernels behind
+    if (c->fuse && c->matQueuesEmpty && fusable && !c->ml.state.litWavefront()) { c->phase = PH_DEFER_LOGIC; c->pendFirst = first; }
     else { if (runLogic(c, first, 0, 0)) return 1; c->phase = PH_CHAIN; }
     return 0;
 }

@@ -74,14 +74,18 @@ struct ActiveListState {
 // triangles are known (the list depends on the materials, which only flx_upload_scene brings).  `built`: the device table was built from the
 // triangles as they stand.  Every call that moves triangles makes it stale; while the option is on the same call rebuilds it before it returns
 // (api_mesh_light.hip: meshLightsSync), so between two calls the table is never stale with the option on.
+// `wavefront` (option "mesh_lights_wavefront"): the wavefront integrator's logic pass sees the lamps too.  A wish of its own: set
+// and cleared by its option alone, in either order with "mesh_lights", kept across uploads; it takes effect only while lit() holds.
 struct MeshLightState {
-    bool on = false, listed = false, built = false; uint32_t lights = 0;
+    bool on = false, listed = false, built = false, wavefront = false; uint32_t lights = 0;
     void optionSet(bool v) { on = v; if (!v) built = false; }           // kept up only while the option is on: switching it on builds
+    void wavefrontSet(bool v) { wavefront = v; }
     void sceneUploaded(uint32_t n) { listed = true; built = false; lights = n; }
     void trianglesMoved() { built = false; }
     void rebuilt() { built = true; }
     bool needsBuild() const { return on && listed && !built; }
     bool usable() const { return on && listed && built; }
     bool lit() const { return usable() && lights > 0; }             // the MESH instances of the microkernels run; otherwise the plain ones do
+    bool litWavefront() const { return lit() && wavefront; }        // the MESH instance of the plain logic pass runs, and no pass is fused (api_wavefront.hip)
 };
 }

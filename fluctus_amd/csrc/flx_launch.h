@@ -78,7 +78,7 @@ uint32_t shadow_split_lists(); uint32_t shadow_split_count_words();
 void launch_extend4r(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, uint32_t *);
 void launch_shadow4r(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, uint32_t *);
 void launch_logic(hipStream_t, const State &, const Queues &, const Scene &, const Frame &, const flx_render_params &, uint8_t *, uint32_t *, uint32_t *, int, int, int, int, int,
-                  unsigned long long *, uint32_t, int, int, uint32_t *, int);
+                  unsigned long long *, uint32_t, int, int, uint32_t *, int, const MeshLights *);     // (the last: non-null = the MESH instance of the plain pass)
 void launch_env_nee_table(hipStream_t, const Scene &, float4 *, uint32_t);
 int logic_can_regenerate();
 uint32_t logic_lookback_words(uint32_t numTasks);

@@ -27,6 +27,7 @@
 #include "flx_denoise.h"        // flx_lum: the luminance moments (option "moments")
 #include "flx_launch.h"
 #include "flx_splat.h"         // wave_add4: a terminating path's pixel as one 16-byte piece of one atomic instruction
+#include "flx_mesh_light.h"    // option "mesh_lights_wavefront": the MESH instance of the plain pass
 
 namespace flxd {
 
@@ -169,9 +170,16 @@ __device__ __forceinline__ uint32_t material_list(int type, uint32_t separate)
 #ifndef LOGIC_MIN_BLOCKS        // blocks per CU the register allocator must leave room for (x LOGIC_BLOCK / 256 waves per SIMD); 0: whatever it needs
 #define LOGIC_MIN_BLOCKS 0
 #endif
-template <int FUSE, bool RAW = false, bool REGROUP = false>
-__global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : LOGIC_MIN_BLOCKS) > 0 ? (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : LOGIC_MIN_BLOCKS) : 1) void k_logic(State st, Scene sc, Frame fr, flx_render_params p, LogicAux aux, Queues qs, uint32_t firstIteration)
+// MESH (option "mesh_lights_wavefront"): emissive triangles are a third KIND of light beside the environment map and the quad -- one
+// more outcome of the one kind draw, sampled through the table `mesh` (flx_mesh_light.h) into the same light-sample columns, and collected on an implicit
+// hit with the MIS weight of that very pdf.  One instance, of the plain pass (k_logic<0, false, false, true>); with MESH = false every `if (MESH ...)`
+// folds away, the last argument is an empty struct, and the kernels are the shipped ones.
+template <bool MESH> struct MeshArg { __device__ MeshLights get() const { return MeshLights(); } };
+template <> struct MeshArg<true> { MeshLights t; __device__ MeshLights get() const { return t; } };
+template <int FUSE, bool RAW = false, bool REGROUP = false, bool MESH = false>
+__global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : LOGIC_MIN_BLOCKS) > 0 ? (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : LOGIC_MIN_BLOCKS) : 1) void k_logic(State st, Scene sc, Frame fr, flx_render_params p, LogicAux aux, Queues qs, uint32_t firstIteration, MeshArg<MESH> meshArg)
 {
+    const MeshLights mesh = meshArg.get();
     const uint32_t gid = blockIdx.x * LOGIC_BLOCK + threadIdx.x;
     uint32_t maxId = st.numTasks;
     if (firstIteration) { uint32_t npix = p.width * p.height; maxId = npix < maxId ? npix : maxId; }
@@ -222,6 +230,9 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
 
         // russian roulette (src/wf_logic.cl:60-69)
         bool terminate = (len >= p.maxBounces + 1u);
+        // MESH: a path that ends at the bounce limit ALONE (no roulette verdict, throughput left) still collects the lamp it has just hit -- the microkernel's
+        // rule (mk_next_vertex collects, mk_sample_bsdf ends the path), without which the last vertex' light sample would never meet its MIS partner
+        const bool meshCut = MESH && terminate && !p.useRoulette;
         if (terminate && p.useRoulette) {
             float contProb = clampf(luminance(T), 0.01f, 0.5f);
             terminate = (rand01(&seed) > contProb);
@@ -239,6 +250,13 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
                 float lightPickProb = st.pickProb[gid];
                 float directPdfW = env_map_pdf(sc, rayDir);
                 weight = (lastPdfW * lightPickProb) / (lastPdfW * lightPickProb + directPdfW);
+                // MESH, the lamps a kind of their own: the reference's weight above is the complement of the NEE weight (directPdfW pick) / (directPdfW pick + bsdfPdfW)
+                // only for pick = 1 -- with a second kind the loop loses environment light under MIS, with the lamps as a third (pick 1/3) a third more.  The
+                // instance that brings the third kind weighs the implicit environment hit like the quad's and the lamps': against pdf x kind probability
+                if (MESH && mesh.n && mesh.hdr[1] != ML_NONE) {
+                    const float kindProb = (float)p.useEnvMap / (float)(p.useEnvMap + p.useAreaLight + 1u);
+                    weight = lastPdfW / (lastPdfW + directPdfW * kindProb);
+                }
             }
             Ei = Ei + weight * T * bg;
             terminate = true;
@@ -254,6 +272,28 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
             }
             Ei = Ei + T * misWeight * V(p.areaLight.E);
             terminate = true;
+        } else if (MESH && hitI >= 0 && !(hflags & 1u) && (!terminate || (meshCut && !is_zero(T) && lastPdfW != 0.0f))) {   // implicit hit on a lamp, seen from the side its geometric normal faces
+            const f3 Ke = V(sc.materials[hitMat].Ke);
+            if (flxml::ml_is_emissive(Ke.x, Ke.y, Ke.z) && (len == 1u || p.sampleImpl)) {       // (counted as the environment is, above)
+                f3 p0, p1, p2;
+                ml_vertices(sc, (uint32_t)hitI, &p0, &p1, &p2);
+                const f3 ng = flxml::ml_normal(p0, p1, p2);
+                if (dot(ng, rayDir) < 0.0f) {
+                    float misWeight = 1.0f;
+                    const bool lastSpecular = fresh || __float_as_uint(rd4(st.at(S_LT, gid)).w) != 0u;
+                    if (p.sampleExpl && len > 1u && !lastSpecular && mesh.n && mesh.hdr[1] != ML_NONE) {
+                        const uint32_t k = flxml::ml_find(mesh.tri, mesh.n, (uint32_t)hitI);
+                        if (k != ML_NONE) {                           // the pdf the light choice below would have sampled this point with: area pdf x kind probability
+                            const f3 hitP = (RAW && isRaw) ? rawP : ld3(rd4(st.at(S_HITP, gid)));
+                            const float directPdfA = flxml::ml_pdf_area(mesh.pick[k], flxml::ml_area(p0, p1, p2));
+                            const float directPdfW = pdf_a_to_w(directPdfA, length(hitP - rayOrig), dot(normalize(-rayDir), ng));
+                            const float kindProb = 1.0f / (float)(p.useEnvMap + p.useAreaLight + 1u);      // from the parameters, not from lastLightPickProb
+                            misWeight = lastPdfW / (lastPdfW + directPdfW * kindProb);
+                        }
+                    }
+                    Ei = Ei + T * misWeight * Ke;
+                }
+            }                                                         // the path goes on: the lamp's own BSDF decides, as in the microkernel
         }
 
         // consume the light sample generated at the previous vertex (:135-156)
@@ -345,10 +385,14 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
             if (!FULL) wr4(st.at(S_HITN, gid), mk4u(hitN, (hflags & 1u) | (backface ? 2u : 0u)));   // :212-213
 
             if (p.sampleExpl && !FLX_BXDF_IS_SINGULAR(mat.type)) {    // next event estimation, :217-302
-                uint32_t den = p.useEnvMap + p.useAreaLight; if (den < 1u) den = 1u;
+                // MESH: the lamps are a third kind while the table has a pickable light -- ONE kind draw all the same
+                const bool meshKind = MESH && mesh.n && mesh.hdr[1] != ML_NONE;
+                uint32_t den = p.useEnvMap + p.useAreaLight + (meshKind ? 1u : 0u); if (den < 1u) den = 1u;
                 const float envMapProb = (float)p.useEnvMap / (float)den;
-                const bool useEnvMap = rand01(&seed) < envMapProb;
-                const bool useAreaLight = !useEnvMap && p.useAreaLight;
+                const float kindDraw = rand01(&seed);
+                const bool useEnvMap = kindDraw < envMapProb;
+                const bool useAreaLight = !useEnvMap && p.useAreaLight && (!meshKind || kindDraw < (float)(p.useEnvMap + p.useAreaLight) / (float)den);
+                const bool useMesh = meshKind && !useEnvMap && !useAreaLight;
                 if (useEnvMap && p.useEnvMap) {
                     f3 L; float directPdfW = 0.0f;
 #ifdef FLX_LAB_LOGIC_NONEE          // lab build only (RESULTS INVALID: radiance and the shadow rays' directions; the paths' flow is untouched): the pass without
@@ -371,7 +415,7 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
                     haveL = true; Lnee = L;
                 }
                 if (useAreaLight) {
-                    const float lightPickProb = 1.0f - envMapProb;
+                    const float lightPickProb = meshKind ? (float)p.useAreaLight / (float)den : 1.0f - envMapProb;
                     const float directPdfA = 1.0f / (4.0f * p.areaLight.size.x * p.areaLight.size.y);
                     f3 posL = V(p.areaLight.pos);
                     const float r1 = 2.0f * rand01(&seed) - 1.0f;
@@ -391,7 +435,28 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
                         neeBlocked = true;
                     }
                 }
-                if (haveL) {                                          // the light sample (:262-268 / :289-295)
+                if (MESH && useMesh) {                                // the lamps: three more draws (pick, r1, r2); the quad's block with the table's triangle
+                    const float pk = rand01(&seed);
+                    const float r1 = rand01(&seed);
+                    const float r2 = rand01(&seed);
+                    const uint32_t k = flxml::ml_pick(mesh.cdf, mesh.n, mesh.hdr[1], pk);
+                    const uint32_t ltri = mesh.tri[k];
+                    f3 p0, p1, p2;
+                    ml_vertices(sc, ltri, &p0, &p1, &p2);
+                    f3 L = flxml::ml_sample_triangle(p0, p1, p2, r1, r2) - orig;
+                    const float lenL = length(L);                     // the TRUE distance: it enters the pdf; the shadow ray stops short of the lamp, which is in the tree
+                    L = normalize(L);
+                    const float cosLight = fmaxf_(dot(flxml::ml_normal(p0, p1, p2), -L), 0.0f);
+                    if (cosLight > 0.0f) {
+                        const float directPdfW = pdf_a_to_w(flxml::ml_pdf_area(mesh.pick[k], flxml::ml_area(p0, p1, p2)), lenL, cosLight);
+                        const float cosTh = fmaxf_(0.0f, dot(L, hitN));
+                        neeLen = 0.995f * lenL; neePdf = directPdfW; neeLi = V(sc.materials[ml_material(sc, ltri)].Ke); neeCos = cosTh; neePick = 1.0f / (float)den;
+                        haveL = true; Lnee = L;
+                    } else {
+                        neeBlocked = true;
+                    }
+                }
+                if (haveL) {                                         // the light sample (:262-268 / :289-295)
                     eiw = __uint_as_float(pixIdx);
                     member |= 2u;
                     if (!FULL) {
@@ -745,7 +810,7 @@ uint32_t fused_queue_mask(int fuse)
 // fuse: 0 = the plain logic kernel | USE_DIFFUSE | USE_ALL  (diffuse + glossy was measured too: never the best of the three)
 void launch_logic(hipStream_t s, const State &st, const Queues &qs, const Scene &sc, const Frame &fr, const flx_render_params &p,
                   uint8_t *member, uint32_t *blockCounts, uint32_t *blockOffsets, int firstIteration, int fuse, int raygenFirst, int extByPathId, int raw,
-                  unsigned long long *lookback, uint32_t epoch, int regen, int regenAppendExt, uint32_t *error, int regroup)
+                  unsigned long long *lookback, uint32_t epoch, int regen, int regenAppendExt, uint32_t *error, int regroup, const MeshLights *meshLights)
 {
     // the reference launches ceil32(NUM_TASKS) work-items (src/clcontext.cpp:792); here ceil256
     uint32_t blocks = (st.numTasks + LOGIC_BLOCK - 1) / LOGIC_BLOCK;
@@ -755,15 +820,20 @@ void launch_logic(hipStream_t s, const State &st, const Queues &qs, const Scene 
     const dim3 g(blocks), b(LOGIC_BLOCK);
     switch (fuse) {
     case USE_DIFFUSE:
-        if (raw) hipLaunchKernelGGL((k_logic<USE_DIFFUSE, true>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration);
-        else hipLaunchKernelGGL((k_logic<USE_DIFFUSE, false>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration);
+        if (raw) hipLaunchKernelGGL((k_logic<USE_DIFFUSE, true>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
+        else hipLaunchKernelGGL((k_logic<USE_DIFFUSE, false>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
         break;
     case USE_ALL:
-        if (rg) hipLaunchKernelGGL((k_logic<USE_ALL, true, true>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration);
-        else if (raw) hipLaunchKernelGGL((k_logic<USE_ALL, true>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration);
-        else hipLaunchKernelGGL((k_logic<USE_ALL, false>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration);
+        if (rg) hipLaunchKernelGGL((k_logic<USE_ALL, true, true>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
+        else if (raw) hipLaunchKernelGGL((k_logic<USE_ALL, true>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
+        else hipLaunchKernelGGL((k_logic<USE_ALL, false>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
         break;
-    default: fuse = 0; hipLaunchKernelGGL(k_logic<0>, g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration); break;
+    default:
+        fuse = 0;
+        // meshLights: the MESH instance exists for the plain pass alone; the caller (api_wavefront.hip) fuses nothing while the lamps light this integrator
+        if (meshLights) hipLaunchKernelGGL((k_logic<0, false, false, true>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<true>{*meshLights});
+        else hipLaunchKernelGGL(k_logic<0>, g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
+        break;
     }
     hipLaunchKernelGGL(k_queue_scan, dim3(NUM_LISTS), dim3(1024), 0, s, aux, qs.counters);
     hipLaunchKernelGGL(k_queue_scatter, g, b, 0, s, qs, aux, st.numTasks, fuse, (uint32_t)raygenFirst, (uint32_t)extByPathId);

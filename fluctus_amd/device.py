@@ -219,7 +219,9 @@ class HipContext:
         self._chk(self.L.flx_objects_read(self.h, _p(counts), C.byref(n), _p(members)))
         return counts, members
 
-    # emissive triangles as lights: set_option("mesh_lights", 1) (include/fluctus_hip.h)
+    # emissive triangles as lights: set_option("mesh_lights", 1) (include/fluctus_hip.h) for the microkernel integrator, and
+    # set_option("mesh_lights_wavefront", 1) on top of it (either order) for the wavefront one: wf_logic then runs the MESH
+    # instance of the plain logic pass and the chain is the unfused one whatever "fuse" says.  Inert without "mesh_lights" or without lamps.
     def mesh_lights_read(self):
         """flx_mesh_lights_read (blocking): (tris uint32 ascending, cdf float32, pick float32, total float64) -- the table of emissive triangles
         as it stands on the device; host.mesh_light_table gives the same bytes on the CPU.  All empty when the scene has no light."""

@@ -578,6 +578,8 @@ int fh_tracer_set_motion_reprojection(void *t, int on) { FH_TRY ((Tracer *)t)->s
 int fh_tracer_get_motion_reprojection(void *t) { return ((Tracer *)t)->getMotionReprojection() ? 1 : 0; }
 int fh_tracer_set_max_history(void *t, float n) { FH_TRY ((Tracer *)t)->setMaxHistory(n); FH_CATCH }
 int fh_tracer_set_mesh_lights(void *t, int on) { FH_TRY ((Tracer *)t)->setMeshLights(on != 0); FH_CATCH }
+int fh_tracer_set_mesh_lights_wavefront(void *t, int on) { FH_TRY ((Tracer *)t)->setMeshLightsWavefront(on != 0); FH_CATCH }
+int fh_tracer_get_mesh_lights_wavefront(void *t) { return ((Tracer *)t)->getMeshLightsWavefront() ? 1 : 0; }
 int fh_tracer_mesh_light_count(void *t, uint32_t *out) { FH_TRY *out = ((Tracer *)t)->meshLightCount(); FH_CATCH }
 int fh_tracer_toggle_renderer(void *t) { FH_TRY ((Tracer *)t)->toggleRenderer(); FH_CATCH }
 int fh_tracer_uses_wavefront(void *t) { return ((Tracer *)t)->usesWavefront() ? 1 : 0; }

@@ -373,7 +373,7 @@ bool Tracer::onlyCameraChanged(bool posed) const
 }
 void Tracer::toggleRenderer()
 {
-    if (!useWavefront && meshLightsOn)
+    if (!useWavefront && meshLightsOn && !meshLightsWavefrontOn)
         throw std::runtime_error("toggleRenderer: mesh lights are on and the wavefront integrator does not see emissive triangles -- the scene's lamps would go dark; setMeshLights(false) first");
     useWavefront = !useWavefront; iteration = 0; dropHistory();
 }
@@ -383,7 +383,20 @@ void Tracer::setMeshLights(bool on)
     if (on && useWavefront) toggleRenderer();                            // as renderSingle does
     clctx->setOption("mesh_lights", on ? 1 : 0);
     meshLightsOn = on;
+    if (!on && meshLightsWavefrontOn) { clctx->setOption("mesh_lights_wavefront", 0); meshLightsWavefrontOn = false; }
     iteration = 0; dropHistory();                                        // the accumulation was lit differently
+}
+// ... and the wavefront integrator: the logic pass's MESH instance samples and collects the lamps, so the wavefront loop is
+// allowed again.  The integrator in use stays the one it is: toggleRenderer() switches.
+void Tracer::setMeshLightsWavefront(bool on)
+{
+    if (on && !peers.empty()) throw std::runtime_error("setMeshLightsWavefront: emissive triangles as lights are single-GPU");
+    if (on && !meshLightsOn) throw std::runtime_error("setMeshLightsWavefront: needs setMeshLights(true) first");
+    if (on == meshLightsWavefrontOn) return;                             // nothing changes: the accumulation stays
+    if (!on && meshLightsOn && useWavefront) toggleRenderer();           // back to the integrator that sees the lamps, as setMeshLights(true) does
+    clctx->setOption("mesh_lights_wavefront", on ? 1 : 0);
+    meshLightsWavefrontOn = on;
+    iteration = 0; dropHistory();
 }
 void Tracer::setMaxHistory(float n)
 {

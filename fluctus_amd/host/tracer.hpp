@@ -130,6 +130,11 @@ public:
     void setMeshLights(bool on);
     bool getMeshLights() const { return meshLightsOn; }
     uint32_t meshLightCount() { return clctx->meshLightCount(); }
+    // ... and the wavefront integrator too, default off: throws unless setMeshLights(true) came first and on a multi-rank Tracer.
+    // While on, toggleRenderer() reaches the wavefront loop and update() renders the lamps there (the unfused chain: INTEGRATION.md).  Switching it
+    // off on the wavefront loop returns to the microkernel branch; setMeshLights(false) clears it.
+    void setMeshLightsWavefront(bool on);
+    bool getMeshLightsWavefront() const { return meshLightsWavefrontOn; }
     void toggleRenderer();                                                        // src/tracer.cpp:881-886 (no history across integrators)
     void setOption(const std::string &name, int value) { for (auto *c : ranks()) c->setOption(name, value); }   // every rank (HipContext::setOption)
     bool usesWavefront() const { return useWavefront; }
@@ -208,7 +213,7 @@ private:
     uint32_t gbWidth = 0, gbHeight = 0;                                           // ... traced at this size
     uint32_t framesSinceGbuffer = 0;                                              // > 0: there is an accumulation worth capturing
     uint32_t temporalFrames = 0;                                                  // frames since the last discarded history (the denoiser schedule while temporalOn)
-    bool meshLightsOn = false;
+    bool meshLightsOn = false, meshLightsWavefrontOn = false;
     bool useWavefront = true;                                                     // this library's default; the reference starts on MK (src/tracer.cpp:11)
     QueueCounters lastCnt {};
     std::string sceneName;

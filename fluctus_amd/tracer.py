@@ -237,6 +237,16 @@ class Tracer:
         update() renders with that integrator and toggle_renderer() to the wavefront loop raises.  Single-GPU."""
         host._chk(self.L.fh_tracer_set_mesh_lights(self.h, int(bool(on))))
 
+    def set_mesh_lights_wavefront(self, on):
+        """Tracer::setMeshLightsWavefront (default off; DESIGN.md 4.2.3): the wavefront integrator sees the lamps too, so toggle_renderer() to the
+        wavefront loop no longer raises and update() renders them there (the unfused chain: logic, then the separate material kernels).  Raises
+        unless set_mesh_lights(True) came first, and on a multi-rank Tracer; set_mesh_lights(False) clears it."""
+        host._chk(self.L.fh_tracer_set_mesh_lights_wavefront(self.h, int(bool(on))))
+
+    @property
+    def mesh_lights_wavefront(self):
+        return bool(self.L.fh_tracer_get_mesh_lights_wavefront(self.h))
+
     def mesh_light_count(self):
         """Tracer::meshLightCount: the emissive triangles listed as lights on the device (raises while mesh lights are off)"""
         n = C.c_uint32()

@@ -103,8 +103,16 @@ int flx_objects_read(flx_ctx *ctx, uint32_t *out_counts, uint32_t *out_nobjects,
  * list-driven (adaptive) instances do the same.  The table is built on the stream when the option is switched on and rebuilt at the end of every
  * call that moves triangles -- flx_upload_scene, flx_update_triangles, flx_update_triangles_subset, flx_objects_pose -- so the next sample sees the
  * lamps where and as large as they are.  The option survives flx_upload_scene.  With the option off, or on with no emissive triangle, every entry
- * point launches the kernels it launches without it and returns the same bits.  THE flx_wf_* CALLS IGNORE THE OPTION: the wavefront integrator
- * does not see emissive triangles.
+ * point launches the kernels it launches without it and returns the same bits.  THE flx_wf_* CALLS IGNORE THIS OPTION ALONE: the wavefront integrator
+ * sees emissive triangles only with the second option below.
+ * flx_set_option(ctx, "mesh_lights_wavefront", 1), default 0, readable through flx_get_option: the wavefront integrator sees the
+ * lamps too.  Inert unless "mesh_lights" is on and the scene has an emissive triangle; the two options may be set in either order, and both survive
+ * flx_upload_scene.  While it takes effect, flx_wf_logic runs the MESH instance of the plain logic pass: the lamps are a third kind of light in the
+ * one-draw light choice (probability 1 / (useEnvMap + useAreaLight + 1) each kind), sampled into the usual light-sample columns, and an implicit hit
+ * on a lamp adds its Ke with the MIS weight of that pdf and does not end the path; an implicit hit on the environment map is weighed the same way,
+ * lastPdfW / (lastPdfW + pdf * kind probability), not with the reference's weight, which loses environment light once a second kind exists.
+ * COST: the chain is the unfused one whatever "fuse" says ("fuse" still reads back what was set) -- flx_wf_logic does not defer, RAW hit records are committed first, flx_wf_materials launches the separate
+ * material kernels.  Off, or on without lamps, every flx_wf_* call launches what it launches without it and returns the same bits.
  * flx_mesh_lights_read, blocking: *out_count = the lights listed (0 when their total weight is 0: no lights), and where not NULL (room for the
  * count a first call reported) out_tris = their ascending triangle indices, out_cdf / out_pick = the table, *out_total = the fp64 total weight.
  * flx_mesh_lights_sample: test hook beside flx_math_probe, blocking.  r3 = n triples (pick, r1, r2) of host floats; out_light[i] = the light picked,
