@@ -219,44 +219,25 @@ int flx_gbuffer_objects_write(flx_ctx *c, int slot, const uint32_t *in)
 #define MK_READY(c) do { READY(c, CALL_OBSERVE); NEED(c, (c)->fr.nranks == 1, "the microkernel integrator is single-GPU: flx_set_partition(ctx, 0, 1) first"); } while (0)
 int flx_mk_reset(flx_ctx *c) { MK_READY(c); c->ad.state.dropped(); launch_mk_reset(c->stream, c->st, c->fr, c->params); LAUNCHED(c); return 0; }
 // with a list of active pixels installed (flx_mk_adaptive_update / flx_mk_active_write) the four kernels of a sample pass run their list-driven
-// instances over it; an empty list makes them no-ops
-int flx_mk_raygen(flx_ctx *c)
-{
-    MK_READY(c);
-    if (!c->ad.state.have) launch_mk_raygen(c->stream, c->st, c->params);
-    else if (c->ad.state.count) launch_mk_raygen_list(c->stream, c->st, c->params, c->ad.list, c->ad.state.count);
-    LAUNCHED(c); return 0;
-}
+// instances over it; an empty list makes them no-ops (microkernel.hip: mk_dispatch).  With option "mesh_lights" and emissive triangles the two
+// kernels that see lights run their MESH instances.
+static const uint32_t *mkList(const flx_ctx *c) { return c->ad.state.have ? c->ad.list : nullptr; }
+static const MeshLights *mkLamps(const flx_ctx *c) { return c->ml.state.lit() ? &c->ml.t : nullptr; }
+int flx_mk_raygen(flx_ctx *c) { MK_READY(c); launch_mk_raygen(c->stream, c->st, c->params, mkList(c), c->ad.state.count); LAUNCHED(c); return 0; }
 int flx_mk_next_vertex(flx_ctx *c)
 {
     MK_READY(c);
-    if (c->ml.state.lit()) {                                // option "mesh_lights" and emissive triangles: the MESH instances
-        if (!c->ad.state.have || c->ad.state.count)
-            launch_mk_next_vertex_mesh(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ml.t, c->ad.state.have ? c->ad.list : nullptr, c->ad.state.count);
-    }
-    else if (!c->ad.state.have) launch_mk_next_vertex(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
-    else if (c->ad.state.count) launch_mk_next_vertex_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ad.list, c->ad.state.count);
+    launch_mk_next_vertex(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, mkList(c), c->ad.state.count, mkLamps(c));
     LAUNCHED(c); return 0;
 }
 int flx_mk_sample_bsdf(flx_ctx *c)
 {
     MK_READY(c);
-    if (c->ml.state.lit()) {
-        if (!c->ad.state.have || c->ad.state.count)
-            launch_mk_sample_bsdf_mesh(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ml.t, c->ad.state.have ? c->ad.list : nullptr, c->ad.state.count);
-    }
-    else if (!c->ad.state.have) launch_mk_sample_bsdf(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats);
-    else if (c->ad.state.count) launch_mk_sample_bsdf_list(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, c->ad.list, c->ad.state.count);
+    launch_mk_sample_bsdf(c->stream, c->st, c->sc, c->fr, c->params, c->spill, c->mkStats, mkList(c), c->ad.state.count, mkLamps(c));
     LAUNCHED(c); return 0;
 }
-int flx_mk_splat(flx_ctx *c)
-{
-    MK_READY(c);
-    if (!c->ad.state.have) launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 0);
-    else if (c->ad.state.count) launch_mk_splat_list(c->stream, c->st, c->fr, c->params, c->mkStats, c->ad.list, c->ad.state.count);
-    LAUNCHED(c); return 0;
-}
-int flx_mk_splat_preview(flx_ctx *c) { MK_READY(c); launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 1); LAUNCHED(c); return 0; }
+int flx_mk_splat(flx_ctx *c) { MK_READY(c); launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 0, mkList(c), c->ad.state.count); LAUNCHED(c); return 0; }
+int flx_mk_splat_preview(flx_ctx *c) { MK_READY(c); launch_mk_splat(c->stream, c->st, c->fr, c->params, c->mkStats, 1, nullptr, 0u); LAUNCHED(c); return 0; }
 
 // ---- adaptive sampling (adaptive.hip, csrc/flx_adaptive.h)
 static int adaptiveReady(flx_ctx *c, const char *fn)

@@ -60,6 +60,9 @@ __device__ __forceinline__ void ml_vertices(const Scene &sc, uint32_t tri, f3 *p
     *p0 = ld3(t[0]); *p1 = ld3(t[3]); *p2 = ld3(t[6]);
 }
 __device__ __forceinline__ int ml_material(const Scene &sc, uint32_t tri) { return sc.tris[tri].matId; }
+// how the table reaches a kernel that exists with and without the lamps (template <bool MESH>): by value, and as an EMPTY struct in the instance without
+template <bool MESH> struct MeshArg { static constexpr bool on = false; __device__ MeshLights get() const { return MeshLights(); } };
+template <> struct MeshArg<true> { static constexpr bool on = true; MeshLights t; __device__ MeshLights get() const { return t; } };
 uint32_t mesh_light_runs(uint32_t n);
 void launch_mesh_light_build(hipStream_t, const Scene &, const MeshLights &);
 void launch_mesh_light_probe(hipStream_t, const Scene &, const MeshLights &, const float *, uint32_t, uint32_t *, float *);
@@ -94,17 +97,12 @@ void launch_state_export(hipStream_t, const State &, float *, float);
 void launch_state_import(hipStream_t, const State &, const float *);
 void launch_math_probe(hipStream_t, int, const float *, const float *, uint32_t, uint32_t *);
 void launch_mk_reset(hipStream_t, const State &, const Frame &, const flx_render_params &);
-void launch_mk_raygen(hipStream_t, const State &, const flx_render_params &);
-void launch_mk_next_vertex(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *);
-void launch_mk_sample_bsdf(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *);
-void launch_mk_splat(hipStream_t, const State &, const Frame &, const flx_render_params &, uint32_t *, int);
-void launch_mk_raygen_list(hipStream_t, const State &, const flx_render_params &, const uint32_t *, uint32_t);
-void launch_mk_next_vertex_list(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const uint32_t *, uint32_t);
-void launch_mk_sample_bsdf_list(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const uint32_t *, uint32_t);
-void launch_mk_splat_list(hipStream_t, const State &, const Frame &, const flx_render_params &, uint32_t *, const uint32_t *, uint32_t);
-// the MESH instances of the two kernels that see lights (option "mesh_lights"); a null list = every pixel
-void launch_mk_next_vertex_mesh(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const MeshLights &, const uint32_t *, uint32_t);
-void launch_mk_sample_bsdf_mesh(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const MeshLights &, const uint32_t *, uint32_t);
+// the four steps of a sample pass: (list of active pixels or null = every pixel, its count; an installed list that is EMPTY launches nothing), and for
+// the two that see lights the table of the lamps or null (option "mesh_lights")
+void launch_mk_raygen(hipStream_t, const State &, const flx_render_params &, const uint32_t *, uint32_t);
+void launch_mk_next_vertex(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const uint32_t *, uint32_t, const MeshLights *);
+void launch_mk_sample_bsdf(hipStream_t, const State &, const Scene &, const Frame &, const flx_render_params &, uint32_t *, uint32_t *, const uint32_t *, uint32_t, const MeshLights *);
+void launch_mk_splat(hipStream_t, const State &, const Frame &, const flx_render_params &, uint32_t *, int, const uint32_t *, uint32_t);
 uint32_t adaptive_blocks(uint32_t);
 void launch_adaptive_update(hipStream_t, const float4 *, int, int, const ad_params &, uint8_t *, uint32_t *, uint32_t *, uint32_t *);
 void launch_end_iteration(hipStream_t, uint32_t *, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t *);

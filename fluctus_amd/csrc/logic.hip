@@ -27,7 +27,7 @@
 #include "flx_denoise.h"        // flx_lum: the luminance moments (option "moments")
 #include "flx_launch.h"
 #include "flx_splat.h"         // wave_add4: a terminating path's pixel as one 16-byte piece of one atomic instruction
-#include "flx_mesh_light.h"    // option "mesh_lights_wavefront": the MESH instance of the plain pass
+#include "flx_light.h"         // the light sampling and MIS arithmetic, shared with microkernel.hip; option "mesh_lights_wavefront": the MESH instance of the plain pass
 
 namespace flxd {
 
@@ -173,13 +173,13 @@ __device__ __forceinline__ uint32_t material_list(int type, uint32_t separate)
 // MESH (option "mesh_lights_wavefront"): emissive triangles are a third KIND of light beside the environment map and the quad -- one
 // more outcome of the one kind draw, sampled through the table `mesh` (flx_mesh_light.h) into the same light-sample columns, and collected on an implicit
 // hit with the MIS weight of that very pdf.  One instance, of the plain pass (k_logic<0, false, false, true>); with MESH = false every `if (MESH ...)`
-// folds away, the last argument is an empty struct, and the kernels are the shipped ones.
-template <bool MESH> struct MeshArg { __device__ MeshLights get() const { return MeshLights(); } };
-template <> struct MeshArg<true> { MeshLights t; __device__ MeshLights get() const { return t; } };
+// folds away, the last argument is an empty struct (MeshArg, flx_launch.h), and the kernels are the shipped ones.
 template <int FUSE, bool RAW = false, bool REGROUP = false, bool MESH = false>
 __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : LOGIC_MIN_BLOCKS) > 0 ? (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : LOGIC_MIN_BLOCKS) : 1) void k_logic(State st, Scene sc, Frame fr, flx_render_params p, LogicAux aux, Queues qs, uint32_t firstIteration, MeshArg<MESH> meshArg)
 {
     const MeshLights mesh = meshArg.get();
+    // the kind probabilities of the one-draw light choice (flx_light.h), for the NEE branch and every implicit-hit branch alike; evaluated where a branch needs them
+    auto kinds = [&]() { return light_kind_probs(p.useEnvMap, p.useAreaLight, MESH && lamps_pickable(mesh)); };
     const uint32_t gid = blockIdx.x * LOGIC_BLOCK + threadIdx.x;
     uint32_t maxId = st.numTasks;
     if (firstIteration) { uint32_t npix = p.width * p.height; maxId = npix < maxId ? npix : maxId; }
@@ -249,14 +249,11 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
             if (p.sampleImpl && p.sampleExpl && p.useEnvMap && len > 1u && !lastSpecular) {
                 float lightPickProb = st.pickProb[gid];
                 float directPdfW = env_map_pdf(sc, rayDir);
-                weight = (lastPdfW * lightPickProb) / (lastPdfW * lightPickProb + directPdfW);
+                weight = mis_implicit_env_reference(lastPdfW, lightPickProb, directPdfW);
                 // MESH, the lamps a kind of their own: the reference's weight above is the complement of the NEE weight (directPdfW pick) / (directPdfW pick + bsdfPdfW)
                 // only for pick = 1 -- with a second kind the loop loses environment light under MIS, with the lamps as a third (pick 1/3) a third more.  The
                 // instance that brings the third kind weighs the implicit environment hit like the quad's and the lamps': against pdf x kind probability
-                if (MESH && mesh.n && mesh.hdr[1] != ML_NONE) {
-                    const float kindProb = (float)p.useEnvMap / (float)(p.useEnvMap + p.useAreaLight + 1u);
-                    weight = lastPdfW / (lastPdfW + directPdfW * kindProb);
-                }
+                if (MESH) { const KindProbs k = kinds(); if (k.lamps) weight = mis_implicit(lastPdfW, directPdfW, k.env); }
             }
             Ei = Ei + weight * T * bg;
             terminate = true;
@@ -265,35 +262,19 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
             const bool lastSpecular = fresh || __float_as_uint(rd4(st.at(S_LT, gid)).w) != 0u;
             const f3 hitP = (RAW && isRaw) ? rawP : ld3(rd4(st.at(S_HITP, gid)));
             if (p.sampleExpl && len > 1u && !lastSpecular) {
-                float directPdfA = 1.0f / (4.0f * p.areaLight.size.x * p.areaLight.size.y);
-                float directPdfW = pdf_a_to_w(directPdfA, length(hitP - rayOrig), dot(normalize(-rayDir), hitN));
-                float lightPickProb = st.pickProb[gid];
-                misWeight = lastPdfW / (lastPdfW + directPdfW * lightPickProb);
+                const float directPdfW = quad_pdf_w(p.areaLight, length(hitP - rayOrig), dot(normalize(-rayDir), hitN));
+                misWeight = mis_implicit(lastPdfW, directPdfW, st.pickProb[gid]);          // the STORED lastLightPickProb, as the reference
             }
             Ei = Ei + T * misWeight * V(p.areaLight.E);
             terminate = true;
         } else if (MESH && hitI >= 0 && !(hflags & 1u) && (!terminate || (meshCut && !is_zero(T) && lastPdfW != 0.0f))) {   // implicit hit on a lamp, seen from the side its geometric normal faces
-            const f3 Ke = V(sc.materials[hitMat].Ke);
-            if (flxml::ml_is_emissive(Ke.x, Ke.y, Ke.z) && (len == 1u || p.sampleImpl)) {       // (counted as the environment is, above)
-                f3 p0, p1, p2;
-                ml_vertices(sc, (uint32_t)hitI, &p0, &p1, &p2);
-                const f3 ng = flxml::ml_normal(p0, p1, p2);
-                if (dot(ng, rayDir) < 0.0f) {
-                    float misWeight = 1.0f;
-                    const bool lastSpecular = fresh || __float_as_uint(rd4(st.at(S_LT, gid)).w) != 0u;
-                    if (p.sampleExpl && len > 1u && !lastSpecular && mesh.n && mesh.hdr[1] != ML_NONE) {
-                        const uint32_t k = flxml::ml_find(mesh.tri, mesh.n, (uint32_t)hitI);
-                        if (k != ML_NONE) {                           // the pdf the light choice below would have sampled this point with: area pdf x kind probability
-                            const f3 hitP = (RAW && isRaw) ? rawP : ld3(rd4(st.at(S_HITP, gid)));
-                            const float directPdfA = flxml::ml_pdf_area(mesh.pick[k], flxml::ml_area(p0, p1, p2));
-                            const float directPdfW = pdf_a_to_w(directPdfA, length(hitP - rayOrig), dot(normalize(-rayDir), ng));
-                            const float kindProb = 1.0f / (float)(p.useEnvMap + p.useAreaLight + 1u);      // from the parameters, not from lastLightPickProb
-                            misWeight = lastPdfW / (lastPdfW + directPdfW * kindProb);
-                        }
-                    }
-                    Ei = Ei + T * misWeight * Ke;
-                }
-            }                                                         // the path goes on: the lamp's own BSDF decides, as in the microkernel
+            f3 Ke; float misWeight;
+            if (lamp_implicit(sc, p, mesh, hitI, hitMat, len, rayOrig, rayDir, lastPdfW,
+                              [&]() { return fresh || __float_as_uint(rd4(st.at(S_LT, gid)).w) != 0u; },
+                              [&]() { return (RAW && isRaw) ? rawP : ld3(rd4(st.at(S_HITP, gid))); },
+                              [&]() { return kinds().lamp; },                                   // from the parameters, not from lastLightPickProb
+                              &Ke, &misWeight))
+                Ei = Ei + T * misWeight * Ke;                          // the path goes on: the lamp's own BSDF decides, as in the microkernel
         }
 
         // consume the light sample generated at the previous vertex (:135-156)
@@ -313,10 +294,7 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
             if ((__float_as_uint(ei4.w) & FLX_FRESH) != 0u) { le = make_float4(0.0f, 0.0f, 0.0f, 0.0f); directPdfW = 0.0f; }
             const float lightPickProb = st.pickProb[gid];
             const float cosTh = le.w, bsdfPdfW = lb.w;
-            float weight = 1.0f;
-            if (p.sampleImpl) weight = (directPdfW * lightPickProb) / (directPdfW * lightPickProb + bsdfPdfW);
-            f3 contrib = ld3(lb) * ld3(lt) * ld3(le) * weight * cosTh / (lightPickProb * directPdfW);
-            Ei = Ei + contrib;
+            Ei = Ei + nee_contribution(ld3(lb), ld3(lt), ld3(le), cosTh, directPdfW, lightPickProb, bsdfPdfW, p.sampleImpl != 0u);
         }
 
         // ---- FULL: every record of the path state is stored by EVERY lane, in one store instruction per record (LOGIC_FULL_STORES, see the macro).
@@ -386,13 +364,12 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
 
             if (p.sampleExpl && !FLX_BXDF_IS_SINGULAR(mat.type)) {    // next event estimation, :217-302
                 // MESH: the lamps are a third kind while the table has a pickable light -- ONE kind draw all the same
-                const bool meshKind = MESH && mesh.n && mesh.hdr[1] != ML_NONE;
-                uint32_t den = p.useEnvMap + p.useAreaLight + (meshKind ? 1u : 0u); if (den < 1u) den = 1u;
-                const float envMapProb = (float)p.useEnvMap / (float)den;
+                const KindProbs kp = kinds();
+                const float envMapProb = kp.env;
                 const float kindDraw = rand01(&seed);
                 const bool useEnvMap = kindDraw < envMapProb;
-                const bool useAreaLight = !useEnvMap && p.useAreaLight && (!meshKind || kindDraw < (float)(p.useEnvMap + p.useAreaLight) / (float)den);
-                const bool useMesh = meshKind && !useEnvMap && !useAreaLight;
+                const bool useAreaLight = !useEnvMap && p.useAreaLight && (!kp.lamps || kindDraw < kp.envOrQuad);
+                const bool useMesh = kp.lamps && !useEnvMap && !useAreaLight;
                 if (useEnvMap && p.useEnvMap) {
                     f3 L; float directPdfW = 0.0f;
 #ifdef FLX_LAB_LOGIC_NONEE          // lab build only (RESULTS INVALID: radiance and the shadow rays' directions; the paths' flow is untouched): the pass without
@@ -415,43 +392,20 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
                     haveL = true; Lnee = L;
                 }
                 if (useAreaLight) {
-                    const float lightPickProb = meshKind ? (float)p.useAreaLight / (float)den : 1.0f - envMapProb;
-                    const float directPdfA = 1.0f / (4.0f * p.areaLight.size.x * p.areaLight.size.y);
-                    f3 posL = V(p.areaLight.pos);
-                    const float r1 = 2.0f * rand01(&seed) - 1.0f;
-                    const float r2 = 2.0f * rand01(&seed) - 1.0f;
-                    posL = posL + r1 * p.areaLight.size.x * V(p.areaLight.right);
-                    posL = posL + r2 * p.areaLight.size.y * V(p.areaLight.up);
-                    f3 L = posL - orig;
-                    const float lenL = length(L) * 0.995f;
-                    L = normalize(L);
-                    const float cosLight = fmaxf_(dot(V(p.areaLight.N), -L), 0.0f);
-                    if (cosLight > 0.0f) {
-                        const float directPdfW = pdf_a_to_w(directPdfA, lenL, cosLight);
-                        const float cosTh = fmaxf_(0.0f, dot(L, hitN));
-                        neeLen = lenL; neePdf = directPdfW; neeLi = V(p.areaLight.E); neeCos = cosTh; neePick = lightPickProb;
-                        haveL = true; Lnee = L;
+                    const LightSample ls = quad_sample(p.areaLight, orig, &seed, 0.995f);      // the reference's quirk: the shortened length in the pdf too
+                    if (ls.cosLight > 0.0f) {
+                        neeLen = ls.rayLen; neePdf = ls.pdfW(); neeLi = V(p.areaLight.E); neeCos = fmaxf_(0.0f, dot(ls.L, hitN)); neePick = kp.quad;
+                        haveL = true; Lnee = ls.L;
                     } else {
                         neeBlocked = true;
                     }
                 }
-                if (MESH && useMesh) {                                // the lamps: three more draws (pick, r1, r2); the quad's block with the table's triangle
-                    const float pk = rand01(&seed);
-                    const float r1 = rand01(&seed);
-                    const float r2 = rand01(&seed);
-                    const uint32_t k = flxml::ml_pick(mesh.cdf, mesh.n, mesh.hdr[1], pk);
-                    const uint32_t ltri = mesh.tri[k];
-                    f3 p0, p1, p2;
-                    ml_vertices(sc, ltri, &p0, &p1, &p2);
-                    f3 L = flxml::ml_sample_triangle(p0, p1, p2, r1, r2) - orig;
-                    const float lenL = length(L);                     // the TRUE distance: it enters the pdf; the shadow ray stops short of the lamp, which is in the tree
-                    L = normalize(L);
-                    const float cosLight = fmaxf_(dot(flxml::ml_normal(p0, p1, p2), -L), 0.0f);
-                    if (cosLight > 0.0f) {
-                        const float directPdfW = pdf_a_to_w(flxml::ml_pdf_area(mesh.pick[k], flxml::ml_area(p0, p1, p2)), lenL, cosLight);
-                        const float cosTh = fmaxf_(0.0f, dot(L, hitN));
-                        neeLen = 0.995f * lenL; neePdf = directPdfW; neeLi = V(sc.materials[ml_material(sc, ltri)].Ke); neeCos = cosTh; neePick = 1.0f / (float)den;
-                        haveL = true; Lnee = L;
+                if (MESH && useMesh) {                                // the lamps: three more draws (pick, r1, r2), the true distance in the pdf
+                    uint32_t ltri;
+                    const LightSample ls = lamp_sample(sc, mesh, orig, &seed, &ltri);
+                    if (ls.cosLight > 0.0f) {
+                        neeLen = ls.rayLen; neePdf = ls.pdfW(); neeLi = V(sc.materials[ml_material(sc, ltri)].Ke); neeCos = fmaxf_(0.0f, dot(ls.L, hitN)); neePick = kp.lamp;
+                        haveL = true; Lnee = ls.L;
                     } else {
                         neeBlocked = true;
                     }

@@ -10,14 +10,14 @@
 #include "flx_bsdf.h"
 #include "flx_denoise.h"        // flx_lum: the luminance moments (option "moments")
 #include "flx_launch.h"
-#include "flx_mesh_light.h"      // option "mesh_lights": the MESH instances of mk_next_vertex / mk_sample_bsdf
+#include "flx_light.h"           // the light sampling and MIS arithmetic, shared with logic.hip; option "mesh_lights": the MESH instances
 
 namespace flxd {
 
 #define MK_BLOCK TRACE_BLOCK      // the traversal stack's LDS layout is [level][TRACE_BLOCK lanes]
 enum { MK_RT_NEXT_VERTEX = 0, MK_SAMPLE_BSDF = 1, MK_SPLAT_SAMPLE = 4, MK_GENERATE_CAMERA_RAY = 5 };
 
-__device__ __forceinline__ uint32_t mk_limit(const State &st, const flx_render_params &p)
+__host__ __device__ __forceinline__ uint32_t mk_limit(const State &st, const flx_render_params &p)
 {
     uint32_t npix = p.width * p.height;
     return npix < st.numTasks ? npix : st.numTasks;
@@ -49,23 +49,25 @@ __global__ __launch_bounds__(256) void k_mk_reset(State st, Frame fr, flx_render
     st.firstDiffuse[gid] = 0u;
 }
 
-// The four kernels of a sample pass exist twice: over every pixel (LIST false: thread = pixel, the instances under the
-// reference's names) and over a compacted ascending list of ACTIVE pixels (LIST true, k_mk_*_list: thread tid < count serves pixel
-// list[tid]; flx_mk_adaptive_update, adaptive.hip).  `gid` below is the pixel = the state slot either way; only the traversal stack's LDS
-// column and spill column belong to the THREAD (tid).  One body per kernel, so the two cannot drift apart.
+// The four kernels of a sample pass exist twice: over every pixel (LIST false: thread = pixel, the reference's kernels)
+// and over a compacted ascending list of ACTIVE pixels (LIST true: thread tid < count serves pixel list[tid]; flx_mk_adaptive_update,
+// adaptive.hip).  `gid` below is the pixel = the state slot either way; only the traversal stack's LDS column and spill column belong to the
+// THREAD (tid).  One template per kernel, so the instances cannot drift apart; the list travels as the lamps' table does (MeshArg,
+// flx_launch.h): an instance without it carries an empty struct.
+template <bool LIST> struct ListArg { static constexpr bool on = false; };
+template <> struct ListArg<true> { static constexpr bool on = true; const uint32_t *list; uint32_t count; };
 template <bool LIST>
-__device__ __forceinline__ bool mk_map(const State &st, const flx_render_params &p, uint32_t tid, const uint32_t *list, uint32_t count, uint32_t *gid)
+__device__ __forceinline__ bool mk_map(const State &st, const flx_render_params &p, uint32_t tid, const ListArg<LIST> &la, uint32_t *gid)
 {
-    if (LIST) { const bool in = tid < count; *gid = in ? list[tid] : 0u; return in; }
-    *gid = tid;
-    return tid < mk_limit(st, p);
+    if constexpr (LIST) { const bool in = tid < la.count; *gid = in ? la.list[tid] : 0u; return in; }
+    else { *gid = tid; return tid < mk_limit(st, p); }
 }
 
 template <bool LIST>
-__device__ __forceinline__ void mk_raygen(State st, flx_render_params p, const uint32_t *list, uint32_t count)
+__global__ __launch_bounds__(256) void k_mk_raygen(State st, flx_render_params p, ListArg<LIST> la)
 {
     uint32_t gid;
-    if (!mk_map<LIST>(st, p, blockIdx.x * 256 + threadIdx.x, list, count, &gid) || st.phase[gid] != MK_GENERATE_CAMERA_RAY) return;
+    if (!mk_map(st, p, blockIdx.x * 256 + threadIdx.x, la, &gid) || st.phase[gid] != MK_GENERATE_CAMERA_RAY) return;
     const float4 thr = rd4(st.at(S_THR, gid));
     uint32_t seed = __float_as_uint(thr.w);
     float x = (float)(gid % p.width), y = (float)(gid / p.width);
@@ -92,18 +94,19 @@ __device__ __forceinline__ void mk_raygen(State st, flx_render_params p, const u
     wr4(st.at(S_THR, gid), mk4u(ld3(thr), seed));
     st.phase[gid] = MK_RT_NEXT_VERTEX;
 }
-__global__ __launch_bounds__(256) void k_mk_raygen(State st, flx_render_params p) { mk_raygen<false>(st, p, nullptr, 0u); }
-__global__ __launch_bounds__(256) void k_mk_raygen_list(State st, flx_render_params p, const uint32_t *list, uint32_t count) { mk_raygen<true>(st, p, list, count); }
 
 // MESH (option "mesh_lights"): emissive triangles are lights -- their emission is collected here on an implicit hit and sampled in
-// mk_sample_bsdf, MIS-weighted against each other through the table `ml`.  The MESH = false instances are the reference's kernels.
+// k_mk_sample_bsdf, MIS-weighted against each other through the table `ml`.  The MESH = false instances are the reference's kernels.  The light
+// arithmetic of both kernels is flx_light.h's, with the microkernel's arguments: every light is sampled at every vertex, so the pick probability is 1.
 template <bool LIST, bool MESH>
-__device__ __forceinline__ void mk_next_vertex(uint32_t *s_stack, State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill,
-                                               uint32_t totalThreads, uint32_t *stats, const uint32_t *list, uint32_t count, const MeshLights &ml)
+__global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
+                                                             ListArg<LIST> la, MeshArg<MESH> meshArg)
 {
+    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
+    const MeshLights ml = meshArg.get();
     const uint32_t tid = blockIdx.x * MK_BLOCK + threadIdx.x;
     uint32_t gid;
-    const bool active = mk_map<LIST>(st, p, tid, list, count, &gid) && st.phase[gid] == MK_RT_NEXT_VERTEX;
+    const bool active = mk_map(st, p, tid, la, &gid) && st.phase[gid] == MK_RT_NEXT_VERTEX;
     bool primary = false;
     if (active) {
         const float4 o4 = rd4(st.at(S_ORIG, gid)), d4 = rd4(st.at(S_DIR, gid));
@@ -141,10 +144,7 @@ __device__ __forceinline__ void mk_next_vertex(uint32_t *s_stack, State st, Scen
             float weight = 1.0f;
             const bool lastSpecular = __float_as_uint(rd4(st.at(S_LT, gid)).w) != 0u;
             if (p.sampleImpl && p.sampleExpl && p.useEnvMap && len > 1u && !lastSpecular) {
-                const float lightPickProb = 1.0f;
-                const float directPdfW = env_map_pdf(sc, dir);
-                const float actualPdfW = o4.w;
-                weight = (actualPdfW * lightPickProb) / (actualPdfW * lightPickProb + directPdfW);
+                weight = mis_implicit_env_reference(o4.w, 1.0f, env_map_pdf(sc, dir));
             }
             const f3 T = ld3(rd4(st.at(S_THR, gid)));
             const float4 ei = rd4(st.at(S_EI, gid));
@@ -153,72 +153,36 @@ __device__ __forceinline__ void mk_next_vertex(uint32_t *s_stack, State st, Scen
         } else if (flags & 1u) {                                     // implicit area-light hit (:94-113)
             float misWeight = 1.0f;
             const bool lastSpecular = __float_as_uint(rd4(st.at(S_LT, gid)).w) != 0u;
-            if (p.sampleExpl && len > 1u && !lastSpecular) {
-                const float directPdfA = 1.0f / (4.0f * p.areaLight.size.x * p.areaLight.size.y);
-                const float directPdfW = pdf_a_to_w(directPdfA, length(P - orig), dot(normalize(-dir), N));
-                const float lightPickProb = 1.0f;
-                const float lastPdfW = o4.w;
-                misWeight = lastPdfW / (lastPdfW + directPdfW * lightPickProb);
-            }
+            if (p.sampleExpl && len > 1u && !lastSpecular)
+                misWeight = mis_implicit(o4.w, quad_pdf_w(p.areaLight, length(P - orig), dot(normalize(-dir), N)), 1.0f);
             const f3 T = ld3(rd4(st.at(S_THR, gid)));
             const float4 ei = rd4(st.at(S_EI, gid));
             wr4(st.at(S_EI, gid), mk4(ld3(ei) + T * misWeight * V(p.areaLight.E), ei.w));
             phase = MK_SPLAT_SAMPLE;
         } else if (MESH) {                                           // a triangle whose material emits, seen from the side its geometric normal faces
-            const f3 Ke = V(sc.materials[matId].Ke);
-            if (flxml::ml_is_emissive(Ke.x, Ke.y, Ke.z) && (len == 1u || p.sampleImpl)) {       // (counted as the environment is, above)
-                f3 p0, p1, p2;
-                ml_vertices(sc, (uint32_t)tri, &p0, &p1, &p2);
-                const f3 ng = flxml::ml_normal(p0, p1, p2);
-                if (dot(ng, dir) < 0.0f) {
-                    float misWeight = 1.0f;
-                    const bool lastSpecular = __float_as_uint(rd4(st.at(S_LT, gid)).w) != 0u;
-                    if (p.sampleExpl && len > 1u && !lastSpecular && ml.n && ml.hdr[1] != ML_NONE) {
-                        const uint32_t k = flxml::ml_find(ml.tri, ml.n, (uint32_t)tri);
-                        if (k != ML_NONE) {                          // the pdf mk_sample_bsdf would have sampled this point with
-                            const float directPdfA = flxml::ml_pdf_area(ml.pick[k], flxml::ml_area(p0, p1, p2));
-                            const float directPdfW = pdf_a_to_w(directPdfA, length(P - orig), dot(normalize(-dir), ng));
-                            const float lastPdfW = o4.w;
-                            misWeight = lastPdfW / (lastPdfW + directPdfW);
-                        }
-                    }
-                    const f3 T = ld3(rd4(st.at(S_THR, gid)));
-                    const float4 ei = rd4(st.at(S_EI, gid));
-                    wr4(st.at(S_EI, gid), mk4(ld3(ei) + T * misWeight * Ke, ei.w));
-                }
-            }                                                        // the path goes on: a lamp with a black BSDF ends it in mk_sample_bsdf (is_zero(bsdf))
+            f3 Ke; float misWeight;                                  // weighed against the pdf k_mk_sample_bsdf would have sampled this point with
+            if (lamp_implicit(sc, p, ml, tri, matId, len, orig, dir, o4.w, [&]() { return __float_as_uint(rd4(st.at(S_LT, gid)).w) != 0u; },
+                              [&]() { return P; }, []() { return 1.0f; }, &Ke, &misWeight)) {
+                const f3 T = ld3(rd4(st.at(S_THR, gid)));
+                const float4 ei = rd4(st.at(S_EI, gid));
+                wr4(st.at(S_EI, gid), mk4(ld3(ei) + T * misWeight * Ke, ei.w));
+            }                                                        // the path goes on: a lamp with a black BSDF ends it in k_mk_sample_bsdf (is_zero(bsdf))
         }
         st.phase[gid] = phase;
     }
     wave_count(&stats[0], active && primary);
     wave_count(&stats[1], active && !primary);
 }
-__global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats)
-{
-    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    mk_next_vertex<false, false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, nullptr, 0u, MeshLights());
-}
-__global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex_list(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
-                                                                  const uint32_t *list, uint32_t count)
-{
-    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    mk_next_vertex<true, false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count, MeshLights());
-}
-template <bool LIST>
-__global__ __launch_bounds__(MK_BLOCK) void k_mk_next_vertex_mesh(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
-                                                                  const uint32_t *list, uint32_t count, MeshLights ml)
-{
-    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    mk_next_vertex<LIST, true>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count, ml);
-}
 
 template <bool LIST, bool MESH>
-__device__ __forceinline__ void mk_sample_bsdf(uint32_t *s_stack, State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill,
-                                               uint32_t totalThreads, uint32_t *stats, const uint32_t *list, uint32_t count, const MeshLights &ml)
+__global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
+                                                             ListArg<LIST> la, MeshArg<MESH> meshArg)
 {
+    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
+    const MeshLights ml = meshArg.get();
     const uint32_t tid = blockIdx.x * MK_BLOCK + threadIdx.x;
     uint32_t gid;
-    const bool active = mk_map<LIST>(st, p, tid, list, count, &gid) && st.phase[gid] == MK_SAMPLE_BSDF;
+    const bool active = mk_map(st, p, tid, la, &gid) && st.phase[gid] == MK_SAMPLE_BSDF;
     uint32_t nShadow = 0;
     if (active) {
         const float4 thr = rd4(st.at(S_THR, gid));
@@ -244,7 +208,8 @@ __device__ __forceinline__ void mk_sample_bsdf(uint32_t *s_stack, State st, Scen
         const f3 T = ld3(thr);
         Stack stk; stk.lds = s_stack + threadIdx.x; stk.stride = totalThreads; stk.spill = spill + tid;
         if (p.sampleExpl && !FLX_BXDF_IS_SINGULAR(m.type)) {         // next event estimation, both lights (src/mk_sample_bsdf.cl:62-141)
-            const float lightPickProb = 1.0f;
+            const float lightPickProb = 1.0f;                        // every light is sampled at every vertex
+            const bool mis = p.sampleImpl != 0u;
             if (p.useEnvMap) {
                 f3 L; float directPdfW = 0.0f;
                 sample_env_alias(sc, rand01(&seed), &L, &directPdfW);
@@ -254,65 +219,26 @@ __device__ __forceinline__ void mk_sample_bsdf(uint32_t *s_stack, State st, Scen
                 if (p.useAreaLight) { float tl = lenL; occluded = light_quad(p.areaLight, orig, L, &tl); }
                 if (!occluded) { float t = lenL, u, v; int tri; uint32_t a = 0, b = 0; occluded = traverse<true, false>(sc, stk, orig, L, t, u, v, tri, a, b); }
                 nShadow++;
-                if (!occluded && directPdfW != 0.0f) {
-                    const f3 brdf = bxdf_eval(sc, h, m, backface, rayDir, L);
-                    const float cosTh = fmaxf_(0.0f, dot(L, h.N));
-                    const float bsdfPdfW = fmaxf_(0.0f, bxdf_pdf(sc, h, m, backface, rayDir, L));
-                    float weight = 1.0f;
-                    if (p.sampleImpl) weight = (directPdfW * lightPickProb) / (directPdfW * lightPickProb + bsdfPdfW);
-                    const f3 envMapLi = eval_env_dir(sc, L) * p.envMapStrength;
-                    Ei = Ei + brdf * T * envMapLi * weight * cosTh / (lightPickProb * directPdfW);
-                }
+                if (!occluded && directPdfW != 0.0f)
+                    Ei = Ei + nee_eval(sc, h, m, backface, rayDir, L, T, eval_env_dir(sc, L) * p.envMapStrength, directPdfW, lightPickProb, mis);
             }
             if (p.useAreaLight) {
-                const float directPdfA = 1.0f / (4.0f * p.areaLight.size.x * p.areaLight.size.y);
-                f3 posL = V(p.areaLight.pos);
-                const float r1 = 2.0f * rand01(&seed) - 1.0f;
-                const float r2 = 2.0f * rand01(&seed) - 1.0f;
-                posL = posL + r1 * p.areaLight.size.x * V(p.areaLight.right);
-                posL = posL + r2 * p.areaLight.size.y * V(p.areaLight.up);
-                f3 L = posL - orig;
-                const float lenL = length(L);
-                L = normalize(L);
-                float t = lenL, u, v; int tri; uint32_t a = 0, b = 0;
-                const bool occluded = traverse<true, false>(sc, stk, orig, L, t, u, v, tri, a, b);
+                const LightSample ls = quad_sample(p.areaLight, orig, &seed, 1.0f);      // the true length, in the ray and in the pdf
+                float t = ls.rayLen, u, v; int tri; uint32_t a = 0, b = 0;
+                const bool occluded = traverse<true, false>(sc, stk, orig, ls.L, t, u, v, tri, a, b);
                 nShadow++;
-                const float cosLight = fmaxf_(dot(V(p.areaLight.N), -L), 0.0f);
-                if (!occluded && cosLight > 0.0f) {
-                    const f3 brdf = bxdf_eval(sc, h, m, backface, rayDir, L);
-                    const float cosTh = fmaxf_(0.0f, dot(L, h.N));
-                    const float directPdfW = pdf_a_to_w(directPdfA, lenL, cosLight);
-                    const float bsdfPdfW = fmaxf_(0.0f, bxdf_pdf(sc, h, m, backface, rayDir, L));
-                    float weight = 1.0f;
-                    if (p.sampleImpl) weight = (directPdfW * lightPickProb) / (directPdfW * lightPickProb + bsdfPdfW);
-                    Ei = Ei + brdf * T * V(p.areaLight.E) * weight * cosTh / (lightPickProb * directPdfW);
-                }
+                if (!occluded && ls.cosLight > 0.0f)
+                    Ei = Ei + nee_eval(sc, h, m, backface, rayDir, ls.L, T, V(p.areaLight.E), ls.pdfW(), lightPickProb, mis);
             }
-            // the emissive triangles: the quad's block line for line, three draws (pick, r1, r2) and none without a pickable light
-            if (MESH && ml.n && ml.hdr[1] != ML_NONE) {
-                const uint32_t k = flxml::ml_pick(ml.cdf, ml.n, ml.hdr[1], rand01(&seed));
-                const float r1 = rand01(&seed);
-                const float r2 = rand01(&seed);
-                const uint32_t ltri = ml.tri[k];
-                f3 p0, p1, p2;
-                ml_vertices(sc, ltri, &p0, &p1, &p2);
-                const float directPdfA = flxml::ml_pdf_area(ml.pick[k], flxml::ml_area(p0, p1, p2));
-                f3 L = flxml::ml_sample_triangle(p0, p1, p2, r1, r2) - orig;
-                const float lenL = length(L);
-                L = normalize(L);
-                float t = 0.995f * lenL, u, v; int tri; uint32_t a = 0, b = 0;        // the lamp is in the tree: stop short of it (the reference's factor for its own light, src/wf_logic.cl)
-                const bool occluded = traverse<true, false>(sc, stk, orig, L, t, u, v, tri, a, b);
+            // the emissive triangles: the quad's block with the table's triangle, three draws (pick, r1, r2) and none without a pickable light
+            if (MESH && lamps_pickable(ml)) {
+                uint32_t ltri;
+                const LightSample ls = lamp_sample(sc, ml, orig, &seed, &ltri);
+                float t = ls.rayLen, u, v; int tri; uint32_t a = 0, b = 0;
+                const bool occluded = traverse<true, false>(sc, stk, orig, ls.L, t, u, v, tri, a, b);
                 nShadow++;
-                const float cosLight = fmaxf_(dot(flxml::ml_normal(p0, p1, p2), -L), 0.0f);
-                if (!occluded && cosLight > 0.0f) {
-                    const f3 brdf = bxdf_eval(sc, h, m, backface, rayDir, L);
-                    const float cosTh = fmaxf_(0.0f, dot(L, h.N));
-                    const float directPdfW = pdf_a_to_w(directPdfA, lenL, cosLight);
-                    const float bsdfPdfW = fmaxf_(0.0f, bxdf_pdf(sc, h, m, backface, rayDir, L));
-                    float weight = 1.0f;
-                    if (p.sampleImpl) weight = (directPdfW * lightPickProb) / (directPdfW * lightPickProb + bsdfPdfW);
-                    Ei = Ei + brdf * T * V(sc.materials[ml_material(sc, ltri)].Ke) * weight * cosTh / (lightPickProb * directPdfW);
-                }
+                if (!occluded && ls.cosLight > 0.0f)
+                    Ei = Ei + nee_eval(sc, h, m, backface, rayDir, ls.L, T, V(sc.materials[ml_material(sc, ltri)].Ke), ls.pdfW(), lightPickProb, mis);
             }
         }
         float contProb = 1.0f;
@@ -339,31 +265,14 @@ __device__ __forceinline__ void mk_sample_bsdf(uint32_t *s_stack, State st, Scen
     for (int o = 32; o > 0; o >>= 1) nShadow += __shfl_xor(nShadow, o, 64);
     if (lane_id() == 0u && nShadow) atomicAdd(&stats[2], nShadow);
 }
-__global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats)
-{
-    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    mk_sample_bsdf<false, false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, nullptr, 0u, MeshLights());
-}
-__global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf_list(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
-                                                                  const uint32_t *list, uint32_t count)
-{
-    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    mk_sample_bsdf<true, false>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count, MeshLights());
-}
-template <bool LIST>
-__global__ __launch_bounds__(MK_BLOCK) void k_mk_sample_bsdf_mesh(State st, Scene sc, Frame fr, flx_render_params p, uint32_t *spill, uint32_t totalThreads, uint32_t *stats,
-                                                                  const uint32_t *list, uint32_t count, MeshLights ml)
-{
-    __shared__ uint32_t s_stack[LDS_LEVELS * MK_BLOCK];
-    mk_sample_bsdf<LIST, true>(s_stack, st, sc, fr, p, spill, totalThreads, stats, list, count, ml);
-}
 
 // (the list-driven instance is never a preview: flx_mk_splat_preview covers every pixel)
 template <bool LIST>
-__device__ __forceinline__ void mk_splat(State st, Frame fr, flx_render_params p, uint32_t *stats, int preview, const uint32_t *list, uint32_t count)
+__global__ __launch_bounds__(256) void k_mk_splat(State st, Frame fr, flx_render_params p, uint32_t *stats, int previewArg, ListArg<LIST> la)
 {
+    const int preview = LIST ? 0 : previewArg;
     uint32_t gid;
-    const bool inRange = mk_map<LIST>(st, p, blockIdx.x * 256 + threadIdx.x, list, count, &gid);
+    const bool inRange = mk_map(st, p, blockIdx.x * 256 + threadIdx.x, la, &gid);
     const bool active = inRange && (preview || st.phase[gid] == MK_SPLAT_SAMPLE);
     if (active) {
         const float4 ei = rd4(st.at(S_EI, gid));
@@ -390,57 +299,45 @@ __device__ __forceinline__ void mk_splat(State st, Frame fr, flx_render_params p
     }
     if (!preview) wave_count(&stats[3], active);
 }
-__global__ __launch_bounds__(256) void k_mk_splat(State st, Frame fr, flx_render_params p, uint32_t *stats, int preview) { mk_splat<false>(st, fr, p, stats, preview, nullptr, 0u); }
-__global__ __launch_bounds__(256) void k_mk_splat_list(State st, Frame fr, flx_render_params p, uint32_t *stats, const uint32_t *list, uint32_t count) { mk_splat<true>(st, fr, p, stats, 0, list, count); }
 
-static uint32_t mkThreads(const State &st, const flx_render_params &p) { uint32_t n = p.width * p.height; return n < st.numTasks ? n : st.numTasks; }
+// ONE place picks a step's instance and its thread count: f(threads, ListArg, MeshArg).  A null list = every pixel; an installed list that is EMPTY
+// launches nothing.  The caller guarantees ascending entries < min(width * height, numTasks) and count <= that bound, so the spill columns (one per
+// thread) stay inside the allocation the unlisted launches use.
+template <class F>
+static void mk_dispatch(const State &st, const flx_render_params &p, const uint32_t *list, uint32_t count, const MeshLights *ml, F f)
+{
+    if (list && !count) return;
+    const uint32_t threads = list ? count : mk_limit(st, p);
+    const ListArg<true> la{list, count};
+    if (list) { if (ml) f(threads, la, MeshArg<true>{*ml}); else f(threads, la, MeshArg<false>()); }
+    else { if (ml) f(threads, ListArg<false>(), MeshArg<true>{*ml}); else f(threads, ListArg<false>(), MeshArg<false>()); }
+}
 
 void launch_mk_reset(hipStream_t s, const State &st, const Frame &fr, const flx_render_params &p)
-{ hipLaunchKernelGGL(k_mk_reset, dim3((mkThreads(st, p) + 255) / 256), dim3(256), 0, s, st, fr, p); }
-void launch_mk_raygen(hipStream_t s, const State &st, const flx_render_params &p)
-{ hipLaunchKernelGGL(k_mk_raygen, dim3((mkThreads(st, p) + 255) / 256), dim3(256), 0, s, st, p); }
-void launch_mk_next_vertex(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats)
+{ hipLaunchKernelGGL(k_mk_reset, dim3((mk_limit(st, p) + 255) / 256), dim3(256), 0, s, st, fr, p); }
+void launch_mk_raygen(hipStream_t s, const State &st, const flx_render_params &p, const uint32_t *list, uint32_t count)
 {
-    uint32_t blocks = (mkThreads(st, p) + MK_BLOCK - 1) / MK_BLOCK;
-    hipLaunchKernelGGL(k_mk_next_vertex, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats);
+    mk_dispatch(st, p, list, count, nullptr, [&](uint32_t threads, auto la, auto) {
+        hipLaunchKernelGGL(k_mk_raygen<decltype(la)::on>, dim3((threads + 255) / 256), dim3(256), 0, s, st, p, la); });
 }
-void launch_mk_sample_bsdf(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats)
+void launch_mk_next_vertex(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats,
+                           const uint32_t *list, uint32_t count, const MeshLights *ml)
 {
-    uint32_t blocks = (mkThreads(st, p) + MK_BLOCK - 1) / MK_BLOCK;
-    hipLaunchKernelGGL(k_mk_sample_bsdf, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats);
+    mk_dispatch(st, p, list, count, ml, [&](uint32_t threads, auto la, auto ma) {
+        const uint32_t blocks = (threads + MK_BLOCK - 1) / MK_BLOCK;
+        hipLaunchKernelGGL((k_mk_next_vertex<decltype(la)::on, decltype(ma)::on>), dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, la, ma); });
 }
-void launch_mk_splat(hipStream_t s, const State &st, const Frame &fr, const flx_render_params &p, uint32_t *stats, int preview)
-{ hipLaunchKernelGGL(k_mk_splat, dim3((mkThreads(st, p) + 255) / 256), dim3(256), 0, s, st, fr, p, stats, preview); }
-
-// the list-driven pass: count > 0 threads, pixel list[tid]; the caller guarantees ascending entries < min(width * height, numTasks) and count <= that bound,
-// so the spill columns (one per thread) stay inside the allocation the unlisted launches use
-void launch_mk_raygen_list(hipStream_t s, const State &st, const flx_render_params &p, const uint32_t *list, uint32_t count)
-{ hipLaunchKernelGGL(k_mk_raygen_list, dim3((count + 255) / 256), dim3(256), 0, s, st, p, list, count); }
-void launch_mk_next_vertex_list(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats, const uint32_t *list, uint32_t count)
+void launch_mk_sample_bsdf(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats,
+                           const uint32_t *list, uint32_t count, const MeshLights *ml)
 {
-    uint32_t blocks = (count + MK_BLOCK - 1) / MK_BLOCK;
-    hipLaunchKernelGGL(k_mk_next_vertex_list, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, count);
+    mk_dispatch(st, p, list, count, ml, [&](uint32_t threads, auto la, auto ma) {
+        const uint32_t blocks = (threads + MK_BLOCK - 1) / MK_BLOCK;
+        hipLaunchKernelGGL((k_mk_sample_bsdf<decltype(la)::on, decltype(ma)::on>), dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, la, ma); });
 }
-void launch_mk_sample_bsdf_list(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats, const uint32_t *list, uint32_t count)
+void launch_mk_splat(hipStream_t s, const State &st, const Frame &fr, const flx_render_params &p, uint32_t *stats, int preview, const uint32_t *list, uint32_t count)
 {
-    uint32_t blocks = (count + MK_BLOCK - 1) / MK_BLOCK;
-    hipLaunchKernelGGL(k_mk_sample_bsdf_list, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, count);
+    mk_dispatch(st, p, list, count, nullptr, [&](uint32_t threads, auto la, auto) {
+        hipLaunchKernelGGL(k_mk_splat<decltype(la)::on>, dim3((threads + 255) / 256), dim3(256), 0, s, st, fr, p, stats, preview, la); });
 }
-void launch_mk_next_vertex_mesh(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats, const MeshLights &ml,
-                                const uint32_t *list, uint32_t count)
-{
-    const uint32_t blocks = ((list ? count : mkThreads(st, p)) + MK_BLOCK - 1) / MK_BLOCK;
-    if (list) hipLaunchKernelGGL(k_mk_next_vertex_mesh<true>, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, count, ml);
-    else hipLaunchKernelGGL(k_mk_next_vertex_mesh<false>, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, 0u, ml);
-}
-void launch_mk_sample_bsdf_mesh(hipStream_t s, const State &st, const Scene &sc, const Frame &fr, const flx_render_params &p, uint32_t *spill, uint32_t *stats, const MeshLights &ml,
-                                const uint32_t *list, uint32_t count)
-{
-    const uint32_t blocks = ((list ? count : mkThreads(st, p)) + MK_BLOCK - 1) / MK_BLOCK;
-    if (list) hipLaunchKernelGGL(k_mk_sample_bsdf_mesh<true>, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, count, ml);
-    else hipLaunchKernelGGL(k_mk_sample_bsdf_mesh<false>, dim3(blocks), dim3(MK_BLOCK), 0, s, st, sc, fr, p, spill, blocks * MK_BLOCK, stats, list, 0u, ml);
-}
-void launch_mk_splat_list(hipStream_t s, const State &st, const Frame &fr, const flx_render_params &p, uint32_t *stats, const uint32_t *list, uint32_t count)
-{ hipLaunchKernelGGL(k_mk_splat_list, dim3((count + 255) / 256), dim3(256), 0, s, st, fr, p, stats, list, count); }
 
 } // namespace flxd
