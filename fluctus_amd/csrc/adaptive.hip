@@ -1,7 +1,8 @@
 // adaptive.hip -- flx_mk_adaptive_update: classify every pixel with the stopping rule of csrc/flx_adaptive.h and compact the
 // active ones into an ASCENDING list for the list-driven microkernels (microkernel.hip: k_mk_*<true>).
 //
-// Three launches, the pattern of logic.hip's queues (k_logic's member bytes -> k_queue_scan -> k_queue_scatter), no atomics at all:
+// Three launches -- flag bytes and block counts, a one-block scan, a scatter; the pattern logic.hip's queues had before their scan and scatter became
+// one persistent launch (k_queue_build; not worth it here: this runs once per adaptive update, not in every step) -- and no atomics at all:
 //   k_ad_classify  one thread per pixel in 1-D blocks of 256 CONSECUTIVE pixels: the pixel's moments (16 B), the 3 x 3 neighbours' only where
 //                  the pixel itself has converged (the rows above and below come out of L2), one flag byte, and the block's count of active
 //                  pixels from four ballots.
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(AD_BLOCK) void k_ad_classify(const float4 *mom, int
 }
 
 // one block: every thread owns a contiguous run of `per` block counts; the 16 waves scan their threads' sums with shuffles, wave 0 the 16
-// wave totals (k_queue_scan's scheme).  In place: blockCounts holds the exclusive offsets afterwards (every thread reads its own run before it
+// wave totals. In place: blockCounts holds the exclusive offsets afterwards (every thread reads its own run before it
 // overwrites it).
 __global__ __launch_bounds__(1024) void k_ad_scan(uint32_t *blockCounts, uint32_t nb, uint32_t *count)
 {

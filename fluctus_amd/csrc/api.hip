@@ -153,15 +153,16 @@ int flx_create(int device, uint32_t num_tasks, flx_ctx **out)
     if (dalloc(c, c->fixedAllocs, &c->qs.counters, 8) || dalloc(c, c->fixedAllocs, &c->qs.cursors, FLX_NUM_BLOCK_CURSORS * FLX_CURSOR_STRIDE)) return fail("hipMalloc(counters)", hipErrorOutOfMemory);
     (void)hipMemsetAsync(c->qs.counters, 0, 32, c->stream);
     (void)hipMemsetAsync(c->qs.cursors, 0, 4 * FLX_NUM_BLOCK_CURSORS * FLX_CURSOR_STRIDE, c->stream);
-    const size_t auxStride = logic_aux_stride(num_tasks);          // per list, padded for the scan kernel's uint4 accesses
-    if (dalloc(c, c->fixedAllocs, &c->member, N) || dalloc(c, c->fixedAllocs, &c->blockCounts, (size_t)7 * auxStride) || dalloc(c, c->fixedAllocs, &c->blockOffsets, (size_t)7 * auxStride))
+    const size_t auxStride = logic_aux_stride(num_tasks);          // per list, padded to whole segments of the queue build
+    const size_t queueAuxWords = logic_queue_aux_words(num_tasks); // its segment totals (two buffers) and counter snapshot
+    if (dalloc(c, c->fixedAllocs, &c->member, N) || dalloc(c, c->fixedAllocs, &c->blockCounts, (size_t)7 * auxStride) || dalloc(c, c->fixedAllocs, &c->queueAux, queueAuxWords))
         return fail("hipMalloc(logic aux)", hipErrorOutOfMemory);
     // (the look-back words of option "regen" and the continuation records of option "shadow_split" -- both off by default, together ~45 B per path -- are
     //  allocated when the option is first switched on: optionBuffers)
     if (dalloc(c, c->fixedAllocs, &c->logicError, 1)) return fail("hipMalloc(logic error flag)", hipErrorOutOfMemory);
     (void)hipMemsetAsync(c->logicError, 0, 4, c->stream);
     (void)hipMemsetAsync(c->blockCounts, 0, (size_t)7 * auxStride * 4, c->stream);      // the pad behind each list's counts stays zero
-    (void)hipMemsetAsync(c->blockOffsets, 0, (size_t)7 * auxStride * 4, c->stream);
+    (void)hipMemsetAsync(c->queueAux, 0, queueAuxWords * 4, c->stream);                // both totals buffers start at zero; from then on the build kernels keep them so
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->numCUs = prop.multiProcessorCount; }
     if (dalloc(c, c->fixedAllocs, &c->stats, FLX_NUM_TRACE_STATS)) return fail("hipMalloc(stats)", hipErrorOutOfMemory);
     (void)hipMemsetAsync(c->stats, 0, FLX_NUM_TRACE_STATS * 8, c->stream);

@@ -55,7 +55,7 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
         // box's spread).  On whenever the all-types pass runs; option "regroup" overrides.
         c->regroupAuto = 1;
         c->regroup = c->regroupOpt >= 0 ? c->regroupOpt : c->regroupAuto;
-        // ... and the order in which the fused pass lists the continuing paths in the extension queue (logic.hip: k_queue_scatter): one
+        // ... and the order in which the fused pass lists the continuing paths in the extension queue (logic.hip: k_queue_build): one
         // segment per material queue, as the separate kernels append them, or all of them by path id.  Same-box A/B, Mrays/s segments ->
         // path id: conference 4318 -> 4446 (+3 %: three BSDF types of similar weight, the segments cut the id order into thirds),
         // kitchen 4278 -> 4230, courtyard 1678 -> 1652 (one dominant type: its segment IS the id order, and the small segments of the

@@ -85,8 +85,9 @@ static int runLogic(flx_ctx *c, int first, int fused, int raygenFirst)
     const int prep = (raw && !regen && c->prepOpt && c->raygenQueueEmpty && c->fr.localPixels > 0) ? 1 : 0;
     c->prepDone = prep != 0;
     if (++c->logicEpoch == 0u) c->logicEpoch = 1u;     // (epoch 0 = the zero-filled words of a fresh context)
-    { ScopedTimer t(c, fused ? FLX_K_LOGIC_FUSED : FLX_K_LOGIC); launch_logic(c->stream, c->st, c->qs, c->sc, c->fr, c->params, c->member, c->blockCounts, c->blockOffsets, first, fused, raygenFirst, order, raw,
+    { ScopedTimer t(c, fused ? FLX_K_LOGIC_FUSED : FLX_K_LOGIC); launch_logic(c->stream, c->st, c->qs, c->sc, c->fr, c->params, c->member, c->blockCounts, c->queueAux, first, fused, raygenFirst, order, raw,
                                                                                 c->lookback, c->logicEpoch, regen ? 1 : (prep ? 2 : 0), order == 2 ? 0 : 1, c->logicError, c->regroup,
+                                                                                c->queueParity ^= 1u, (uint32_t)c->numCUs,
                                                                                 (!fused && c->ml.state.litWavefront()) ? &c->ml.t : nullptr); }      // the lamps light this pass: its MESH instance
     LAUNCHED(c);
     c->matQueuesEmpty = false; c->raygenQueueEmpty = false;

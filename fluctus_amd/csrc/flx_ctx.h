@@ -90,7 +90,9 @@ struct flx_ctx {
     bool haveParams = false;
     uint32_t hostPixelIdx = 0;
     // logic aux
-    uint8_t *member = nullptr; uint32_t *blockCounts = nullptr, *blockOffsets = nullptr;
+    uint8_t *member = nullptr; uint32_t *blockCounts = nullptr;
+    // the queue build's segment totals (two buffers: every logic pass flips queueParity, its build kernel zeroes the other one) and counter snapshot (logic.hip)
+    uint32_t *queueAux = nullptr; uint32_t queueParity = 0;
     // in-kernel regeneration of the fused RAW pass (logic.hip: REGEN): look-back status words (one per wave, epoch-stamped: never reset), launch counter,
     // device error flag (a look-back that gave up), option "regen" (1: on where the pass allows it), and whether the LAST fused pass regenerated its
     // terminating paths itself -- then the genRays of the chain is not launched (flx_wf_materials)

@@ -81,7 +81,7 @@ uint32_t shadow_split_lists(); uint32_t shadow_split_count_words();
 void launch_extend4r(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, uint32_t *);
 void launch_shadow4r(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, uint32_t *);
 void launch_logic(hipStream_t, const State &, const Queues &, const Scene &, const Frame &, const flx_render_params &, uint8_t *, uint32_t *, uint32_t *, int, int, int, int, int,
-                  unsigned long long *, uint32_t, int, int, uint32_t *, int, const MeshLights *);     // (the last: non-null = the MESH instance of the plain pass)
+                  unsigned long long *, uint32_t, int, int, uint32_t *, int, uint32_t, uint32_t, const MeshLights *);     // (the last: non-null = the MESH instance of the plain pass)
 void launch_env_nee_table(hipStream_t, const Scene &, float4 *, uint32_t);
 int logic_can_regenerate();
 uint32_t logic_lookback_words(uint32_t numTasks);
@@ -90,6 +90,7 @@ void launch_materials(hipStream_t, const State &, const Queues &, const Scene &,
 void launch_materials_after_fused(hipStream_t, const State &, const Queues &, const Scene &, uint32_t, int);
 uint32_t fused_queue_mask(int);
 uint32_t logic_aux_stride(uint32_t);
+uint32_t logic_queue_aux_words(uint32_t);
 void launch_reset(hipStream_t, const State &, const Queues &, const Frame &, const flx_render_params &);
 void launch_raygen(hipStream_t, const State &, const Queues &, const Frame &, const flx_render_params &, int, int);
 void launch_postprocess(hipStream_t, const Frame &, const flx_render_params &);

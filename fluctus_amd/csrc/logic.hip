@@ -9,8 +9,10 @@
 //
 // Queue building is NOT a per-thread global atomic (reference, non-NVIDIA) and not an inline-PTX
 // warp aggregate (reference, NVIDIA): the kernel only records, per path, one byte of queue
-// membership and, per 256-path block, seven counts (wave64 ballot + popcount).  A one-block scan
-// turns the counts into offsets and a scatter kernel writes the queues with ballot/prefix ranks,
+// membership and, per 256-path block, seven counts (wave64 ballot + popcount), which it also adds
+// to seven totals per segment of 64 blocks.  ONE persistent kernel behind it (k_queue_build; the
+// index arithmetic is flx_queue_build.h's) turns totals and counts into offsets and streams the
+// membership bytes into the queues with ballot/prefix ranks, no block waiting for another,
 // i.e. a STABLE compaction: queue order = ascending path id = the order sequential execution of
 // the reference produces.  Only the raygen queue's order is observable (pixel
 // assignment), and it makes device runs bit-reproducible.
@@ -21,13 +23,14 @@
 // material kernels re-read and the 32 B both kernels write twice never travel.  Waves are no longer BSDF-uniform (the
 // reference's reason for the per-material queues), but the pass is bound by streaming the path state, not by the BSDF
 // arithmetic.  Queue contents, counters and the extension-queue order are the ones the separate kernels produce: the
-// scatter kernel appends the material lists to the extension queue at the slots the material kernels would compute.
+// queue build appends the material lists to the extension queue at the slots the material kernels would compute.
 #include "flx_bsdf.h"
 #include "flx_trace.h"          // hit_values_raw: the commit of traceExtension for RAW hit records
 #include "flx_denoise.h"        // flx_lum: the luminance moments (option "moments")
 #include "flx_launch.h"
 #include "flx_splat.h"         // wave_add4: a terminating path's pixel as one 16-byte piece of one atomic instruction
 #include "flx_light.h"         // the light sampling and MIS arithmetic, shared with microkernel.hip; option "mesh_lights_wavefront": the MESH instance of the plain pass
+#include "flx_queue_build.h"   // segments, owned ranges, ranks inside a tile: the index arithmetic of k_queue_build, shared with the CPU test
 
 namespace flxd {
 
@@ -88,10 +91,12 @@ __host__ __device__ constexpr bool fuse_inlines_list(int fuse, uint32_t ml)     
 
 struct LogicAux {
     uint8_t *member;          // numTasks
-    uint32_t *blockCounts;    // NUM_LISTS x numBlocks
-    uint32_t *blockOffsets;   // NUM_LISTS x numBlocks
+    uint32_t *blockCounts;    // NUM_LISTS x stride
+    uint32_t *segTotals;      // NUM_LISTS x numSegs: this pass's buffer of the two (flx_queue_build.h), zero when the pass starts
+    uint32_t *snapshot;       // NUM_LISTS: the lists' queue counters as they stand before this pass
     uint32_t numBlocks;
-    uint32_t stride;          // elements between two lists in blockCounts / blockOffsets: numBlocks rounded up for the scan's uint4 accesses
+    uint32_t numSegs;
+    uint32_t stride;          // elements between two lists in blockCounts: whole segments (qb_count_stride)
     // in-kernel regeneration (k_logic<FUSE, RAW>, LOGIC_REGEN): one status word per wave for the decoupled look-back over the terminating paths
     unsigned long long *lookback;
     uint32_t epoch;           // launch number: a status word counts only if it carries this launch's epoch (no reset between launches)
@@ -146,6 +151,11 @@ __device__ __forceinline__ uint32_t lookback_exclusive(const LogicAux &aux, uint
     if (lane == 0u) __hip_atomic_store(st + wave, LB_PACK(aux.epoch, 2u, sum + count), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return sum;
 }
+
+static_assert(LOGIC_BLOCK == flxqb::QB_BLOCK && NUM_LISTS == flxqb::QB_LISTS, "flx_queue_build.h counts in k_logic's blocks and lists");
+// list 0 raygen, 1 shadow, 2..6 the material lists -> its queue (the extension queue sits between raygen and shadow)
+__host__ __device__ constexpr uint32_t list_counter(uint32_t l) { return l == 0u ? (uint32_t)FLX_Q_RAYGEN : l + 1u; }
+static_assert(list_counter(1) == FLX_Q_SHADOW && list_counter(2) == FLX_Q_DIFFUSE && list_counter(6) == FLX_Q_DELTA, "queue numbering");
 
 __device__ __forceinline__ uint32_t material_list(int type, uint32_t separate)
 {
@@ -635,123 +645,148 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
         uint32_t s = 0;
         for (int w = 0; w < LOGIC_BLOCK / 64; w++) s += s_cnt[threadIdx.x][w];
         aux.blockCounts[threadIdx.x * aux.stride + blockIdx.x] = s;
+        // ... and into the list's total of this block's segment: fire and forget, nobody waits for it and integer adds commute (k_queue_build reads the sums)
+        if (s != 0u) atomicAdd(aux.segTotals + threadIdx.x * aux.numSegs + blockIdx.x / flxqb::QB_SEG_BLOCKS, s);
+        // the base the list appends behind, before k_queue_build moves the counter
+        if (blockIdx.x == 0u) aux.snapshot[threadIdx.x] = qs.counters[list_counter(threadIdx.x)];
     }
 }
 
-// one block per list: exclusive scan of the list's per-block counts; the total is added to its queue counter.
-// Every thread owns a contiguous run of counts (read as uint4s), the 16 waves scan their threads' sums with shuffles, wave 0 scans the
-// 16 wave totals: two barriers in all (the first version's Hillis-Steele over 1024 partial sums took 20 barriers and 21 us, during
-// which nothing else runs -- every later kernel of the iteration waits for the queues).
-__global__ __launch_bounds__(1024) void k_queue_scan(LogicAux aux, uint32_t *counters)
+// ---- the queue build: ONE persistent launch behind k_logic (flx_queue_build.h states the scheme and holds its index arithmetic).  It took the place
+// of a one-block-per-list scan of the block counts and a one-block-per-256-paths scatter, two latency-bound launches during which nothing else ran
+// (every later kernel of the iteration waits for the queues).
+#ifndef QUEUE_BUILD_BLOCKS_PER_CU      // the persistent grid: 4 blocks of 4 waves per compute unit -- one segment per block at 16 M paths on 256 CUs
+#define QUEUE_BUILD_BLOCKS_PER_CU 4
+#endif
+struct QueueBuild {
+    const uint8_t *member; const uint32_t *blockCounts; const uint32_t *totals; uint32_t *zero; const uint32_t *snapshot;
+    uint32_t stride, numTasks, numSegs, totalsWords;      // zero: the OTHER totals buffer, totalsWords long: the next pass adds into it
+    uint32_t parts;                                       // blocks that share a segment (flx_queue_build.h: qb_parts; 1 at the benchmark's size)
+    int fuse; uint32_t raygenFirst, byPathId;
+};
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64); return v; }
+// exclusive prefix over the lanes of a count 0..4: the lanes below, bit by bit
+__device__ __forceinline__ uint32_t prefix_of_count4(uint32_t n) { return mbcnt(__ballot(n & 1u)) + 2u * mbcnt(__ballot(n & 2u)) + 4u * mbcnt(__ballot(n & 4u)); }
+// the lane's paths gid .. gid + 3 that `bits` names, to consecutive slots; all four to an aligned slot: one 16-byte store.  (Compacting a tile's
+// members in a per-wave LDS stage first, so that every store instruction writes 64 consecutive slots, was built and measured: 80 against 70 us for
+// the kernel, 114 against 70 VGPRs -- profiles/queue_build_ab.txt.  The lanes' runs of up to four slots lie back to back, and L2 merges them.)
+__device__ __forceinline__ void emit4(uint32_t *q, uint32_t slot, uint32_t bits, uint32_t gid)
 {
-    __shared__ uint32_t s_wave[16];
-    const uint32_t listToCounter[NUM_LISTS] = {FLX_Q_RAYGEN, FLX_Q_SHADOW, FLX_Q_DIFFUSE, FLX_Q_GLOSSY, FLX_Q_GGX_REFL, FLX_Q_GGX_REFR, FLX_Q_DELTA};
-    const uint32_t nb = aux.numBlocks;
-    const uint32_t per = ((nb + 1023u) / 1024u + 3u) & ~3u;          // counts per thread, a multiple of 4 (the arrays are padded to it)
-    const int l = blockIdx.x;
-    const uint32_t *cnt = aux.blockCounts + (size_t)l * aux.stride;
-    uint32_t *off = aux.blockOffsets + (size_t)l * aux.stride;
-    const uint32_t base = counters[listToCounter[l]];
-    const uint32_t lo = threadIdx.x * per;
-    uint32_t s = 0;
-    for (uint32_t i = 0; i < per; i += 4) {
-        if (lo + i < nb) {                                            // (the pad beyond nb is zero-filled once at allocation and never written)
-            const uint4 v = *reinterpret_cast<const uint4 *>(cnt + lo + i);
-            s += v.x + v.y + v.z + v.w;
-        }
-    }
-    // inclusive scan of s over the wave
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = s;
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += v; }
-    if (lane == 63u) s_wave[wave] = inc;
-    __syncthreads();
-    if (wave == 0u) {
-        uint32_t w = lane < 16u ? s_wave[lane] : 0u, wi = w;
-        for (int d = 1; d < 16; d <<= 1) { const uint32_t v = __shfl_up(wi, d, 64); if (lane >= (uint32_t)d) wi += v; }
-        if (lane < 16u) s_wave[lane] = wi - w;                        // exclusive prefix of the wave totals
-        if (lane == 15u) counters[listToCounter[l]] = base + wi;
-    }
-    __syncthreads();
-    uint32_t run = base + s_wave[wave] + inc - s;
-    for (uint32_t i = 0; i < per; i += 4) {
-        if (lo + i < nb) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(cnt + lo + i);
-            uint4 o;
-            o.x = run; run += v.x; o.y = run; run += v.y; o.z = run; run += v.z; o.w = run; run += v.w;
-            *reinterpret_cast<uint4 *>(off + lo + i) = o;
-        }
-    }
+    if (bits == 0xFu && (slot & 3u) == 0u) { *reinterpret_cast<uint4 *>(q + slot) = make_uint4(gid, gid + 1u, gid + 2u, gid + 3u); return; }
+    if (bits & 1u) q[slot++] = gid;
+    if (bits & 2u) q[slot++] = gid + 1u;
+    if (bits & 4u) q[slot++] = gid + 2u;
+    if (bits & 8u) q[slot] = gid + 3u;
+}
+// the four membership bytes of paths p .. p + 3; those at or behind numTasks do not exist and read as 0 (no list)
+__device__ __forceinline__ uint32_t load_member4(const uint8_t *member, uint64_t p, uint32_t numTasks)
+{
+    const uint32_t valid = flxqb::qb_valid(p, numTasks);
+    if (valid == 4u) return *reinterpret_cast<const uint32_t *>(member + p);
+    uint32_t w = 0u;
+    for (uint32_t k = 0; k < valid; k++) w |= (uint32_t)member[p + k] << (8u * k);
+    return w;
 }
 
-// stable scatter: rank within block by wave ballots, block base from the scan.
-// fuse != 0: the scatter also writes the extension-queue entries of EVERY continuing path -- inlined BSDF type or not; the material
+// fuse != 0: the build also writes the extension-queue entries of EVERY continuing path -- inlined BSDF type or not; the material
 // kernel that serves the other types afterwards does not append -- as one list in path-id order behind (or in front of) the regenerated
 // paths, where the separate material kernels append one segment per material queue.  The extension queue is a set (the reference fills
 // it with atomic_inc in whatever order the work-items arrive, src/utils.cl:328-358); its order only decides which lane traces which ray,
 // and neighbouring path ids are neighbouring pixels' paths: on the same 4 M rays k_extend4 takes 0.730 ms in path-id order against
 // 0.800 ms in per-material segments on the conference scene (three BSDF types of similar weight), 0.912 against 0.933 ms on the kitchen,
 // 1.30 / 1.10 ms shuffled (scripts/exp_octant.py).  Needs material queues that were empty before this `logic` (the host checks).
-__global__ __launch_bounds__(LOGIC_BLOCK) void k_queue_scatter(Queues qs, LogicAux aux, uint32_t numTasks, int fuse, uint32_t raygenFirst, uint32_t byPathId)
+__global__ __launch_bounds__(flxqb::QB_THREADS) void k_queue_build(Queues qs, QueueBuild a)
 {
-    const uint32_t gid = blockIdx.x * LOGIC_BLOCK + threadIdx.x;
-    const uint32_t member = gid < numTasks ? aux.member[gid] : 0u;
-    const uint32_t ml = member >> 2;
-    const uint32_t wave = threadIdx.x >> 6;
-    __shared__ uint32_t s_cnt[NUM_LISTS][LOGIC_BLOCK / 64];
-    __shared__ uint32_t s_off[NUM_LISTS];
-    if (threadIdx.x < NUM_LISTS) s_off[threadIdx.x] = aux.blockOffsets[(size_t)threadIdx.x * aux.stride + blockIdx.x];   // in flight beside the member bytes
-    uint64_t bal[NUM_LISTS];
-    bal[0] = __ballot(member & 1u); bal[1] = __ballot(member & 2u);
-    bal[2] = __ballot(ml == 1u); bal[3] = __ballot(ml == 2u); bal[4] = __ballot(ml == 3u); bal[5] = __ballot(ml == 4u); bal[6] = __ballot(ml == 5u);
-    if ((threadIdx.x & 63u) == 0u)
-        for (int l = 0; l < NUM_LISTS; l++) s_cnt[l][wave] = (uint32_t)__popcll(bal[l]);
+    using namespace flxqb;
+    __shared__ uint32_t s_base[NUM_LISTS];                  // where the current segment's part of a list begins (snapshot + everything in front)
+    __shared__ uint32_t s_new[NUM_LISTS];                   // the new queue counters: snapshot + grand total
+    __shared__ uint32_t s_off[NUM_LISTS][QB_SEG_BLOCKS];    // ... and every tile's part, within the current segment
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t seg0, seg1;
+    qb_owned(blockIdx.x, gridDim.x, a.numSegs, a.parts, &seg0, &seg1);
+    uint32_t tile0, steps;
+    qb_tiles(blockIdx.x, a.parts, &tile0, &steps);
+    // the totals the NEXT pass adds into (the previous pass's: their last reader was the previous build)
+    for (uint32_t i = blockIdx.x * QB_THREADS + threadIdx.x; i < a.totalsWords; i += gridDim.x * QB_THREADS) a.zero[i] = 0u;
+    // 1. per list (one wave each, two rounds): the totals of all segments and of those in front of the own ones
+    for (uint32_t l = wave; l < NUM_LISTS; l += QB_WAVES) {
+        uint32_t before, all;
+        qb_partial(a.totals + (size_t)l * a.numSegs, a.numSegs, seg0, lane, 64u, &before, &all);
+        before = wave_sum(before); all = wave_sum(all);
+        if (lane == 0u) { const uint32_t snap = a.snapshot[l]; s_base[l] = snap + before; s_new[l] = snap + all; }
+    }
     __syncthreads();
+    if (blockIdx.x == 0u && threadIdx.x < NUM_LISTS) qs.counters[list_counter(threadIdx.x)] = s_new[threadIdx.x];
+    if (seg0 == seg1) return;                               // (the whole block: nothing owned)
+    // the extension queue's length before this pass (flx_device.h: ext_len, with the lists' NEW counters -- block 0 is storing them right now)
+    uint32_t extBase = qs.counters[FLX_Q_EXTENSION];
+    if (qs.extPend) for (uint32_t l = 0; l < NUM_LISTS; l++) if (qs.extPend & (1u << list_counter(l))) extBase += s_new[l];
+    if (a.byPathId != 2u && a.raygenFirst) extBase += s_new[0];           // behind the regenerated paths' block
     uint32_t *const outq[NUM_LISTS] = {qs.q[FLX_Q_RAYGEN], qs.q[FLX_Q_SHADOW], qs.q[FLX_Q_DIFFUSE], qs.q[FLX_Q_GLOSSY], qs.q[FLX_Q_GGX_REFL], qs.q[FLX_Q_GGX_REFR], qs.q[FLX_Q_DELTA]};
-    #pragma unroll
-    for (int l = 0; l < NUM_LISTS; l++) {
-        bool in = l == 0 ? (member & 1u) : l == 1 ? ((member & 2u) != 0u) : (ml == (uint32_t)(l - 1));
-        if (in) {
-            uint32_t r = s_off[l];
-            for (uint32_t w = 0; w < wave; w++) r += s_cnt[l][w];
-            r += mbcnt(bal[l]);
-            outq[l][r] = gid;
-            if (fuse != 0 && byPathId == 0u && l >= 2 && fuse_inlines_list(fuse, (uint32_t)(l - 1))) {
-                // option ext_order 0: the separate kernels' order -- one segment per material queue; the types that are not inlined
-                // are appended by their material kernel
-                uint32_t base = ext_len(qs) + (raygenFirst ? qs.counters[FLX_Q_RAYGEN] : 0u);
-                for (int q = FLX_Q_DIFFUSE; q < FLX_Q_DIFFUSE + (l - 2); q++) base += qs.counters[q];
-                qs.q[FLX_Q_EXTENSION][base + r] = gid;
+    uint32_t *const ext = qs.q[FLX_Q_EXTENSION];
+
+    for (uint32_t seg = seg0; seg < seg1; seg++) {
+        // the membership bytes of this wave's tiles (tile0 + wave, + 4, ...: the block streams 1024 consecutive paths per step), all in flight at once
+        uint32_t mw[QB_STEPS];
+        #pragma unroll
+        for (uint32_t i = 0; i < QB_STEPS; i++) mw[i] = i < steps ? load_member4(a.member, qb_first_path(seg, tile0 + wave + QB_WAVES * i, lane), a.numTasks) : 0u;
+        // 2. block counts -> offsets: lane j holds tile j's count (the counts behind the last block are zero: qb_count_stride)
+        if (seg != seg0) __syncthreads();                   // (the previous segment's tiles are done with s_off)
+        for (uint32_t l = wave; l < NUM_LISTS; l += QB_WAVES) {
+            const uint32_t c = a.blockCounts[(size_t)l * a.stride + (size_t)seg * QB_SEG_BLOCKS + lane];
+            uint32_t inc = c;
+            for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += v; }
+            const uint32_t base = s_base[l];
+            s_off[l][lane] = base + inc - c;
+            if (lane == 63u) s_base[l] = base + inc;        // the next segment's (this wave alone reads and writes the word)
+        }
+        __syncthreads();
+        // 3. the tiles
+        #pragma unroll
+        for (uint32_t i = 0; i < QB_STEPS; i++) {
+            if (i >= steps) break;                           // (wave-uniform: a block that shares its segment has fewer tiles)
+            const uint32_t tile = tile0 + wave + QB_WAVES * i;
+            const uint32_t w = mw[i];
+            const uint32_t gid = (uint32_t)qb_first_path(seg, tile, lane);
+            if (__ballot(w != 0u) == 0ull) continue;         // (wave-uniform: nobody here is in any list)
+            uint32_t matOff = 0u;
+            #pragma unroll
+            for (int l = 0; l < NUM_LISTS; l++) {
+                const uint32_t off = s_off[l][tile];
+                if (l >= 2) matOff += off;
+                const uint32_t bits = qb_bits(w, (uint32_t)l);
+                if (__ballot(bits != 0u) == 0ull) continue;
+                const uint32_t r = off + prefix_of_count4(qb_count4(bits));
+                emit4(outq[l], r, bits, gid);
+                if (a.fuse != 0 && a.byPathId == 0u && l >= 2 && fuse_inlines_list(a.fuse, (uint32_t)(l - 1))) {
+                    // option ext_order 0: the separate kernels' order -- one segment per material queue; the types that are not inlined
+                    // are appended by their material kernel
+                    uint32_t segBase = extBase;
+                    for (int m = 2; m < l; m++) segBase += s_new[m];
+                    emit4(ext, segBase + r, bits, gid);
+                }
+            }
+            if (a.fuse != 0 && a.byPathId == 1u) {
+                // the continuing paths of ALL material lists, in path-id order (see the comment above the kernel)
+                const uint32_t bits = qb_bits_material(w);
+                emit4(ext, extBase + matOff + prefix_of_count4(qb_count4(bits)), bits, gid);
+            }
+            if (a.fuse != 0 && a.byPathId == 2u) {
+                // ext_order 2: EVERY path that will be traced -- the regenerated ones (genRays follows in this chain and does not append: k_raygen,
+                // appendExt 0) merged with the continuing ones -- as ONE list in path-id order.  In the steady state every path traces an extension
+                // ray, so the queue is the identity permutation: the traversal kernel's path-state accesses are fully coalesced (round 3 measured
+                // -2 % / -2 % / -6 % of the closest-hit kernel for that order on host-reordered queues, scripts/exp_ray_order.py).  The same SET as the
+                // separate kernels' [regenerated | material segments] (the reference's order is whatever its atomic_inc produces).
+                const uint32_t bits = qb_bits_traced(w);
+                emit4(ext, extBase + s_off[0][tile] + matOff + prefix_of_count4(qb_count4(bits)), bits, gid);
             }
         }
     }
-    if (fuse != 0 && byPathId == 1u && ml != 0u) {
-        // the continuing paths of ALL material lists, in path-id order (see the comment above the kernel)
-        uint32_t r = s_off[2] + s_off[3] + s_off[4] + s_off[5] + s_off[6];
-        for (uint32_t w = 0; w < wave; w++) r += s_cnt[2][w] + s_cnt[3][w] + s_cnt[4][w] + s_cnt[5][w] + s_cnt[6][w];
-        r += mbcnt(bal[2] | bal[3] | bal[4] | bal[5] | bal[6]);
-        qs.q[FLX_Q_EXTENSION][ext_len(qs) + (raygenFirst ? qs.counters[FLX_Q_RAYGEN] : 0u) + r] = gid;
-    }
-    if (fuse != 0 && byPathId == 2u && ((member & 1u) != 0u || ml != 0u)) {
-        // ext_order 2: EVERY path that will be traced -- the regenerated ones (genRays follows in this chain and does not append: k_raygen,
-        // appendExt 0) merged with the continuing ones -- as ONE list in path-id order.  In the steady state every path traces an extension
-        // ray, so the queue is the identity permutation: the traversal kernel's path-state accesses are fully coalesced (round 3 measured
-        // -2 % / -2 % / -6 % of the closest-hit kernel for that order on host-reordered queues, scripts/exp_ray_order.py).  The same SET as the
-        // separate kernels' [regenerated | material segments] (the reference's order is whatever its atomic_inc produces).
-        uint32_t r = s_off[0] + s_off[2] + s_off[3] + s_off[4] + s_off[5] + s_off[6];
-        for (uint32_t w = 0; w < wave; w++) r += s_cnt[0][w] + s_cnt[2][w] + s_cnt[3][w] + s_cnt[4][w] + s_cnt[5][w] + s_cnt[6][w];
-        r += mbcnt(bal[0] | bal[2] | bal[3] | bal[4] | bal[5] | bal[6]);
-        qs.q[FLX_Q_EXTENSION][ext_len(qs) + r] = gid;
-    }
 }
 
-// elements per list in the block-count / block-offset arrays (api.hip allocates NUM_LISTS x this, zero-filled)
-uint32_t logic_aux_stride(uint32_t numTasks)
-{
-    const uint32_t blocks = (numTasks + LOGIC_BLOCK - 1) / LOGIC_BLOCK;
-    const uint32_t per = ((blocks + 1023u) / 1024u + 3u) & ~3u;
-    return per * 1024u;
-}
+// elements per list in the block-count array (api.hip allocates NUM_LISTS x this, zero-filled), and the words of the build's totals + snapshot
+uint32_t logic_aux_stride(uint32_t numTasks) { return flxqb::qb_count_stride(numTasks); }
+uint32_t logic_queue_aux_words(uint32_t numTasks) { return flxqb::qb_aux_words(numTasks); }
 
 // queues (bit q) whose paths the fused pass takes through their material step
 uint32_t fused_queue_mask(int fuse)
@@ -763,12 +798,18 @@ uint32_t fused_queue_mask(int fuse)
 
 // fuse: 0 = the plain logic kernel | USE_DIFFUSE | USE_ALL  (diffuse + glossy was measured too: never the best of the three)
 void launch_logic(hipStream_t s, const State &st, const Queues &qs, const Scene &sc, const Frame &fr, const flx_render_params &p,
-                  uint8_t *member, uint32_t *blockCounts, uint32_t *blockOffsets, int firstIteration, int fuse, int raygenFirst, int extByPathId, int raw,
-                  unsigned long long *lookback, uint32_t epoch, int regen, int regenAppendExt, uint32_t *error, int regroup, const MeshLights *meshLights)
+                  uint8_t *member, uint32_t *blockCounts, uint32_t *queueAux, int firstIteration, int fuse, int raygenFirst, int extByPathId, int raw,
+                  unsigned long long *lookback, uint32_t epoch, int regen, int regenAppendExt, uint32_t *error, int regroup, uint32_t parity, uint32_t numCUs,
+                  const MeshLights *meshLights)
 {
     // the reference launches ceil32(NUM_TASKS) work-items (src/clcontext.cpp:792); here ceil256
     uint32_t blocks = (st.numTasks + LOGIC_BLOCK - 1) / LOGIC_BLOCK;
-    LogicAux aux{member, blockCounts, blockOffsets, blocks, logic_aux_stride(st.numTasks), lookback, epoch, (uint32_t)(raw ? regen : 0), (uint32_t)regenAppendExt, error};
+    // queueAux (logic_queue_aux_words): two buffers of segment totals, this pass's by `parity` (the caller flips it with every pass), then the snapshot
+    const uint32_t tw = flxqb::qb_totals_words(st.numTasks);
+    parity &= 1u;
+    uint32_t *const totals = queueAux + (size_t)parity * tw;
+    LogicAux aux{member, blockCounts, totals, queueAux + flxqb::qb_snapshot_at(st.numTasks), blocks, flxqb::qb_segments(st.numTasks), logic_aux_stride(st.numTasks),
+                 lookback, epoch, (uint32_t)(raw ? regen : 0), (uint32_t)regenAppendExt, error};
     // the BSDF-uniform material step needs every thread of every block inside the pass (block barriers): whole blocks of paths, no `first` cut-off
     const bool rg = LOGIC_REGROUP && raw && regroup && fuse == USE_ALL && !firstIteration && st.numTasks % LOGIC_BLOCK == 0u;
     const dim3 g(blocks), b(LOGIC_BLOCK);
@@ -789,8 +830,9 @@ void launch_logic(hipStream_t s, const State &st, const Queues &qs, const Scene 
         else hipLaunchKernelGGL(k_logic<0>, g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
         break;
     }
-    hipLaunchKernelGGL(k_queue_scan, dim3(NUM_LISTS), dim3(1024), 0, s, aux, qs.counters);
-    hipLaunchKernelGGL(k_queue_scatter, g, b, 0, s, qs, aux, st.numTasks, fuse, (uint32_t)raygenFirst, (uint32_t)extByPathId);
+    // the queue build: a grid sized by the machine; a small wavefront, fewer segments than that, splits each segment over several blocks (qb_parts)
+    const QueueBuild qb{member, blockCounts, totals, queueAux + (size_t)(parity ^ 1u) * tw, aux.snapshot, aux.stride, st.numTasks, aux.numSegs, tw, flxqb::qb_parts(aux.numSegs, numCUs, QUEUE_BUILD_BLOCKS_PER_CU), fuse, (uint32_t)raygenFirst, (uint32_t)extByPathId};
+    hipLaunchKernelGGL(k_queue_build, dim3(flxqb::qb_grid(aux.numSegs, numCUs, QUEUE_BUILD_BLOCKS_PER_CU)), dim3(flxqb::QB_THREADS), 0, s, qs, qb);
 }
 // does this build regenerate terminating paths inside the fused RAW pass (LOGIC_FULL_STORES)?  (api.hip asks before it skips the genRays launch)
 int logic_can_regenerate() { return LOGIC_FULL_STORES != 0 ? 1 : 0; }

@@ -51,8 +51,8 @@ __global__ __launch_bounds__(MISC_BLOCK) void k_reset(State st, Queues qs, Frame
     if (gid == 0) qs.counters[FLX_Q_RAYGEN] = st.numTasks;
 }
 
-// appendExt 0: the extension-queue entries of the regenerated paths were written already -- by the fused scatter, merged with the continuing
-// paths into ONE list in path-id order (logic.hip: k_queue_scatter, ext_order 2) -- and only the paths are regenerated here
+// appendExt 0: the extension-queue entries of the regenerated paths were written already -- by the fused pass's queue build, merged with the continuing
+// paths into ONE list in path-id order (logic.hip: k_queue_build, ext_order 2) -- and only the paths are regenerated here
 // prepared 1 (PREPARED REGENERATION, logic.hip): the fused RAW pass of this chain has stored everything of the regenerated paths that does not depend on the
 // pixel -- origin, throughput + the seed genRays leaves, shadowRayBlocked, lastLightPickProb -- and left {jitter x, jitter y, seed after the jitter} in the
 // direction record: only the direction and the pixel word are stored here (two scattered 16-byte stores per path instead of four + three scalars; this kernel

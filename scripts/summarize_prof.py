@@ -10,7 +10,7 @@ def find(sub, pat):
 
 def short(name):
     n = name.split("(")[0]
-    for k in ("k_extend4", "k_shadow4", "k_extend", "k_shadow", "k_logic", "k_material", "k_raygen", "k_reset", "k_queue_scan", "k_queue_scatter",
+    for k in ("k_extend4", "k_shadow4", "k_extend", "k_shadow", "k_logic", "k_material", "k_raygen", "k_reset", "k_queue_build", "k_queue_scan", "k_queue_scatter",
               "k_end_iteration", "k_postprocess", "k_state"):
         if k in n:
             if k == "k_material":

@@ -15,7 +15,7 @@ prof = os.path.join(root, "profiles")
 for f in glob.glob(os.path.join(out, "trace", "**", "*kernel_stats.csv"), recursive=True):
     shutil.copy(f, os.path.join(prof, f"{tag}_{wl}_kernel_stats_whole_process.csv"))      # rocprofv3's own summary: every dispatch of the process (settling, extra untimed passes)
 KEYS = ("k_trace4r<false", "k_trace4r<true", "k_extend4<false>", "k_shadow4<false", "k_shadow4s<", "k_commit4", "k_lightfix4", "k_extend<false>", "k_shadow<false>", "k_logic", "k_material", "k_raygen",
-        "k_queue_scatter", "k_queue_scan")
+        "k_queue_build", "k_queue_scatter", "k_queue_scan")      # (the last two: captures from before the one-launch queue build)
 bench = {}
 try:
     bench = json.loads(open(os.path.join(prof, f"{tag}_{wl}_bench.json")).readline())
@@ -101,7 +101,7 @@ if ext:
 
     def per_launch(keys):
         """fabric bytes / VALU instructions / lanes per instruction of the dispatches of `keys` that make up ONE launch of the pass (e.g. the fused
-        logic pass = k_logic + k_queue_scan + k_queue_scatter: flx_wf_logic's timer covers all three)"""
+        logic pass = k_logic + k_queue_build -- k_queue_scan + k_queue_scatter in older captures: flx_wf_logic's timer covers them all)"""
         ks = [k for k in keys if k in acc]
         if not ks:
             return None
@@ -109,7 +109,7 @@ if ext:
         vi = sum(acc[k]["SQ_INSTS_VALU"][0] / max(1, acc[k]["SQ_INSTS_VALU"][1]) for k in ks if acc[k].get("SQ_INSTS_VALU", [0])[0])
         tc = sum(acc[k]["SQ_THREAD_CYCLES_VALU"][0] / max(1, acc[k]["SQ_THREAD_CYCLES_VALU"][1]) for k in ks if acc[k].get("SQ_THREAD_CYCLES_VALU", [0])[0])
         return {"kernels": ks, "hbm_bytes_per_launch": by, "valu_instructions_per_launch": vi or None, "lanes_per_valu_instruction": (tc / vi) if vi else None}
-    j["passes"] = {"extend": per_launch([ext]), "logic": per_launch(["k_logic", "k_queue_scan", "k_queue_scatter"]),
+    j["passes"] = {"extend": per_launch([ext]), "logic": per_launch(["k_logic", "k_queue_build", "k_queue_scan", "k_queue_scatter"]),
                    "shadow": per_launch(["k_shadow4<false", "k_shadow4s<", "k_trace4r<true", "k_shadow<false>", "k_lightfix4"])}
     json.dump(j, open(os.path.join(prof, f"traffic_{wl}.json"), "w"), indent=1)
     print("wrote traffic_%s.json: %.4g bytes per launch" % (wl, j["extend_hbm_bytes_per_launch"]))
