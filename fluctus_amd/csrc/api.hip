@@ -378,8 +378,16 @@ int flx_set_option(flx_ctx *c, const char *name, int value)
     }
     if (name && strcmp(name, "motion_history") == 0 && (value == 0 || value == 1)) {
         ENTER(c, CALL_OBSERVE);
+        NEED(c, !value || !c->deformHistory, "flx_set_option: \"motion_history\" cannot be switched on while \"deform_history\" is on (which keeps the history across flx_objects_pose too)");
         if (!value) c->temporal.state.motionHistoryOff();
         c->motionHistory = value;
+        return 0;
+    }
+    if (name && strcmp(name, "deform_history") == 0 && (value == 0 || value == 1)) {     // per-vertex reprojection
+        ENTER(c, CALL_OBSERVE);
+        NEED(c, !value || !c->motionHistory, "flx_set_option: \"deform_history\" cannot be switched on while \"motion_history\" is on (switch that off: this option follows a pose too)");
+        if (!value) c->temporal.state.deformHistoryOff();
+        c->deformHistory = value;
         return 0;
     }
     if (name && strcmp(name, "mesh_lights") == 0 && (value == 0 || value == 1)) {        // emissive triangles light the microkernel integrator
@@ -413,7 +421,7 @@ int flx_get_option(flx_ctx *c, const char *name, int *value)
     NEED(c, name && value, "flx_get_option: null");
     const struct { const char *n; int v; } tab[] = {
         {"xcd_remap", c->xcdRemap}, {"fuse", c->fuse}, {"overlap", c->overlap}, {"shadow_tree", c->shadowTree}, {"extend_tree", c->extendTree},
-        {"denoiser", c->denoiser}, {"moments", c->moments}, {"motion_history", c->motionHistory}, {"mesh_lights", c->ml.state.on ? 1 : 0}, {"mesh_lights_wavefront", c->ml.state.wavefront ? 1 : 0}, {"eager_bump", c->eagerBump}, {"node_layout", c->nodeLayout}, {"fuse_set", c->fuseSet}, {"ext_order", c->extOrder}, {"regen", c->regenOpt}, {"regroup", c->regroup}, {"regen_prep", c->prepOpt}, {"refill_extend", c->refillExt}, {"refill_shadow", c->refillShadow}, {"shadow_split", c->shadowSplit}, {"fused_queue_mask", (int)fused_queue_mask(fuseSetNow(c))}, {"fuse_set_now", fuseSetNow(c)}};
+        {"denoiser", c->denoiser}, {"moments", c->moments}, {"motion_history", c->motionHistory}, {"deform_history", c->deformHistory},{"mesh_lights", c->ml.state.on ? 1 : 0}, {"mesh_lights_wavefront", c->ml.state.wavefront ? 1 : 0}, {"eager_bump", c->eagerBump}, {"node_layout", c->nodeLayout}, {"fuse_set", c->fuseSet}, {"ext_order", c->extOrder}, {"regen", c->regenOpt}, {"regroup", c->regroup}, {"regen_prep", c->prepOpt}, {"refill_extend", c->refillExt}, {"refill_shadow", c->refillShadow}, {"shadow_split", c->shadowSplit}, {"fused_queue_mask", (int)fused_queue_mask(fuseSetNow(c))}, {"fuse_set_now", fuseSetNow(c)}};
     for (const auto &t : tab) if (strcmp(name, t.n) == 0) { *value = t.v; return 0; }
     if (strcmp(name, "phase") == 0) { *value = phaseCode(c); return 0; }
     if (strcmp(name, "wide_far") == 0) { *value = wideFar(c); return 0; }

@@ -4,6 +4,7 @@
 #include "flx_denoise.h"
 #include "flx_denoise_vg.h"
 #include "flx_reproject_motion.h"
+#include "flx_reproject_deform.h"
 #include "flx_adaptive.h"
 #include <cstring>
 
@@ -77,6 +78,9 @@ static int gbufferSlots(flx_ctx *c)
     // option "motion_history": one object id per pixel beside each slot; off: nothing is allocated
     if (c->motionHistory && !c->temporal.objPlane[0] &&
         (dalloc(c, c->temporal.allocs, &c->temporal.objPlane[0], n / 2) || dalloc(c, c->temporal.allocs, &c->temporal.objPlane[1], n / 2))) { c->temporal.release(); return 1; }
+    // option "deform_history": one float2 of barycentrics per pixel beside each slot; off: nothing is allocated
+    if (c->deformHistory && !c->temporal.baryPlane[0] &&
+        (dalloc(c, c->temporal.allocs, &c->temporal.baryPlane[0], n / 2) || dalloc(c, c->temporal.allocs, &c->temporal.baryPlane[1], n / 2))) { c->temporal.release(); return 1; }
     return 0;
 }
 int flx_gbuffer(flx_ctx *c)
@@ -86,9 +90,10 @@ int flx_gbuffer(flx_ctx *c)
     const bool obj = c->motionHistory && c->ob.have;      // the object plane is written only while the option is on and objects are defined
     { ScopedTimer t(c, FLX_K_GBUFFER);
       launch_gbuffer(c->stream, c->sc, c->params, c->spill, c->numTasks, (c->extendTree == 4 && c->wideOK) ? 4 : 2, c->temporal.gb[0], c->fr.localPixels,
-                     obj ? c->temporal.objPlane[0] : nullptr, obj ? c->ob.objectOfTri : nullptr); }
+                     obj ? c->temporal.objPlane[0] : nullptr, obj ? c->ob.objectOfTri : nullptr, c->deformHistory ? c->temporal.baryPlane[0] : nullptr); }
     LAUNCHED(c);
     c->temporal.state.traced(c->params.camera, c->params.width, c->params.height, obj);
+    c->temporal.state.baryWith(0, c->deformHistory != 0);
     return 0;
 }
 int flx_history_capture(flx_ctx *c)
@@ -108,6 +113,7 @@ int flx_history_capture(flx_ctx *c)
     if (withMom) HIPCHK(c, hipMemcpyAsync(c->temporal.histMomBuf, c->fr.moments, n * 16, hipMemcpyDeviceToDevice, c->stream));
     std::swap(c->temporal.gb[0], c->temporal.gb[1]);
     std::swap(c->temporal.objPlane[0], c->temporal.objPlane[1]);
+    std::swap(c->temporal.baryPlane[0], c->temporal.baryPlane[1]);
     c->temporal.state.captured(withMom);
     c->ob.pose.captured();
     return 0;
@@ -129,10 +135,16 @@ int flx_reproject(flx_ctx *c, const flx_reproject_params *pp)
     const bool mom = c->moments && c->fr.moments && ts.histMom;
     // objects posed since the capture (only flx_objects_pose under "motion_history" keeps a history across a move of triangles): the motion-aware
     // kernel with the table of flx_reproject_motion.h, nobjects x 64 bytes uploaded on the stream; no object moved: k_reproject as ever
+    // triangles moved since the capture under "deform_history" (api_refit.hip took the snapshot first): the flags, then the per-vertex kernel of
+    // flx_reproject_deform.h.  No read decides between kernels: with nothing moved its result is k_reproject's bit for bit.
+    const bool deform = ts.followsMoves();
+    if (deform)
+        NEED(c, c->deformHistory && c->rf.snapPos && c->rf.movedFlags && c->temporal.baryPlane[0] && ts.followsMovesReady(),
+             "flx_reproject: triangles moved since the capture: needs option \"deform_history\" on and both G-buffers traced with it (flx_gbuffer)");
     flx_ctx::Objects &ob = c->ob;
     bool moved = false;
     std::vector<rm_row> table;
-    if (ob.have && ob.t.nobjects) {
+    if (!deform && ob.have && ob.t.nobjects) {        // (under "deform_history" a pose is a move of triangles like any other: the snapshot follows it)
         table.resize((size_t)ob.t.nobjects * FLX_RM_ROWS);
         const PoseState::Poses p = ob.pose.sinceCapture();
         moved = rm_make_table(ob.t.nobjects, p.atCapture, p.atCaptureKnown, p.now, p.nowKnown, table.data());
@@ -145,7 +157,11 @@ int flx_reproject(flx_ctx *c, const flx_reproject_params *pp)
     }
     { ScopedTimer t(c, FLX_K_REPROJECT);
       float4 *px = reinterpret_cast<float4 *>(c->fr.pixels), *pm = mom ? reinterpret_cast<float4 *>(c->fr.moments) : nullptr;
-      if (moved) launch_reproject_motion(c->stream, vw, rp, c->temporal.gb[0], c->temporal.gb[1], c->temporal.hist, c->temporal.histMomBuf, px, pm,
+      if (deform) {
+          launch_moved_flags(c->stream, c->sc, c->rf.ntris, c->rf.snapPos, c->rf.movedFlags);
+          launch_reproject_deform(c->stream, vw, rp, c->temporal.gb[0], c->temporal.gb[1], c->temporal.hist, c->temporal.histMomBuf, px, pm,
+                                  c->temporal.baryPlane[0], c->temporal.baryPlane[1], c->sc, c->rf.ntris, c->rf.snapPos, c->rf.movedFlags);
+      } else if (moved) launch_reproject_motion(c->stream, vw, rp, c->temporal.gb[0], c->temporal.gb[1], c->temporal.hist, c->temporal.histMomBuf, px, pm,
                                          c->temporal.objPlane[0], c->temporal.objPlane[1], ob.motion, ob.t.nobjects);
       else launch_reproject(c->stream, vw, rp, c->temporal.gb[0], c->temporal.gb[1], c->temporal.hist, c->temporal.histMomBuf, px, pm); }
     LAUNCHED(c);
@@ -178,8 +194,14 @@ int flx_gbuffer_write(flx_ctx *c, int slot, const float *in8, const void *camera
         HIPCHK(c, hipMemsetAsync(c->temporal.objPlane[slot], 0xFF, (size_t)c->fr.localPixels * 4, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    if (c->deformHistory) {                               // ... and names no triangle until flx_gbuffer_bary_write says otherwise
+        const std::vector<float> none((size_t)c->fr.localPixels * 2, FLX_RD_NO_BARY);
+        HIPCHK(c, hipMemcpyAsync(c->temporal.baryPlane[slot], none.data(), none.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     flx_camera cam; memcpy(&cam, camera80, sizeof(flx_camera));
     c->temporal.state.written(slot, cam, c->params.width, c->params.height, c->motionHistory);
+    c->temporal.state.baryWith(slot, c->deformHistory != 0);
     return 0;
 }
 // ... and of the slots' object planes (option "motion_history"): one uint32 per pixel, FLX_NO_OBJECT or an object id (an id that is not below
@@ -211,6 +233,62 @@ int flx_gbuffer_objects_write(flx_ctx *c, int slot, const uint32_t *in)
     HIPCHK(c, hipMemcpyAsync(c->temporal.objPlane[slot], in, (size_t)c->fr.localPixels * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->temporal.state.objectsWritten(slot);
+    return 0;
+}
+
+// ... and of the slots' barycentric planes (option "deform_history"): two floats per pixel, (u, v) of the hit or (-1, -1) where the pixel names
+// no triangle (csrc/flx_reproject_deform.h).  Blocking.
+int flx_gbuffer_bary_read(flx_ctx *c, int slot, float *out2)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, slot == 0 || slot == 1, "flx_gbuffer_bary_read: slot must be 0 (current) or 1 (previous)");
+    NEED(c, out2, "flx_gbuffer_bary_read: null output");
+    NEED(c, c->temporal.baryPlane[slot] && c->temporal.state.holdsBary(slot),
+         "flx_gbuffer_bary_read: the slot holds no barycentric plane (option \"deform_history\" on, flx_gbuffer)");
+    const TemporalState::Slot &s = c->temporal.state.slot[slot];
+    HIPCHK(c, hipMemcpyAsync(out2, c->temporal.baryPlane[slot], (size_t)s.W * s.H * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+int flx_gbuffer_bary_write(flx_ctx *c, int slot, const float *in2)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, slot == 0 || slot == 1, "flx_gbuffer_bary_write: slot must be 0 (current) or 1 (previous)");
+    NEED(c, in2, "flx_gbuffer_bary_write: null barycentrics");
+    NEED(c, c->deformHistory, "flx_gbuffer_bary_write: needs flx_set_option(ctx, \"deform_history\", 1)");
+    if (temporalReady(c, "flx_gbuffer_bary_write")) return 1;
+    NEED(c, c->temporal.gb[slot] && c->temporal.state.holdsSized(slot, c->params.width, c->params.height),
+         "flx_gbuffer_bary_write: the slot holds no G-buffer of the current size (flx_gbuffer or flx_gbuffer_write first)");
+    if (gbufferSlots(c)) return 1;
+    HIPCHK(c, hipMemcpyAsync(c->temporal.baryPlane[slot], in2, (size_t)c->fr.localPixels * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->temporal.state.baryWritten(slot);
+    return 0;
+}
+// ... and of the snapshot: the nine position floats of every triangle at the capture and -- computed now, as flx_reproject would -- one moved byte
+// per triangle.  Either output may be null.  Blocking; fails when no move has snapshotted since the last capture.
+int flx_deform_read(flx_ctx *c, float *out9, uint8_t *out_moved)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    NEED(c, c->sc.bnodes, "flx_deform_read: upload a scene first (flx_upload_scene)");
+    NEED(c, c->temporal.state.followsMoves() && c->rf.snapPos && c->rf.movedFlags,
+         "flx_deform_read: no snapshot (option \"deform_history\" on, flx_gbuffer, flx_history_capture, then a move of triangles)");
+    const size_t n = c->rf.ntris;
+    if (out9) {
+        std::vector<float> v4(n * FLX_RD_SNAP_V4 * 4);
+        HIPCHK(c, hipMemcpyAsync(v4.data(), c->rf.snapPos, v4.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < n * 3; i++) memcpy(out9 + 3 * i, &v4[4 * i], 12);
+    }
+    if (out_moved) {
+        { ScopedTimer t(c, FLX_K_MOVED_FLAGS); launch_moved_flags(c->stream, c->sc, c->rf.ntris, c->rf.snapPos, c->rf.movedFlags); }
+        LAUNCHED(c);
+        HIPCHK(c, hipMemcpyAsync(out_moved, c->rf.movedFlags, n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     return 0;
 }
 

@@ -105,7 +105,14 @@ static int updateTriangles(flx_ctx *c, bool subset, const void *tris160, const u
     }
     // what flx_upload_scene clears: a list of active pixels and a G-buffer belong to the render of one geometry
     c->ad.state.dropped();
-    c->temporal.state.trianglesMoved(byPose, c->motionHistory);
+    // option "deform_history" (DESIGN.md 4.3.6): the first accepted move after a capture copies every triangle's positions aside, on the stream,
+    // before launch_refit overwrites any; later moves before the next capture keep that snapshot
+    if (c->temporal.state.needsSnapshot(c->deformHistory != 0)) {
+        if (!rf.snapPos && (dalloc(c, c->sceneAllocs, &rf.snapPos, (size_t)rf.ntris * 3) || dalloc(c, c->sceneAllocs, &rf.movedFlags, rf.ntris))) { rf.snapPos = nullptr; return 1; }
+        { ScopedTimer t(c, FLX_K_SNAPSHOT); launch_snapshot_positions(c->stream, c->sc, rf.ntris, rf.snapPos); }
+        LAUNCHED(c);
+    }
+    c->temporal.state.trianglesMoved(byPose, c->motionHistory != 0, c->deformHistory != 0);
     if (!byPose) c->ob.pose.trianglesSetDirectly();
     if (subset && !count) return 0;
     {

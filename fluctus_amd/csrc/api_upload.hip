@@ -256,6 +256,7 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
         c->ml.state.sceneUploaded((uint32_t)c->ml.list.size());
     }
     c->temporal.state.definitionChanged(c->motionHistory);
+    c->temporal.state.sceneUploaded(c->deformHistory != 0);
     if (newSpill) { freeAll(c->spillAllocs); c->spillAllocs.swap(freshSpill); c->spill = sp1; c->spill2 = sp2; c->spillLevels = spillLevels; }
     c->sc.bnodes = dB; c->sc.trirecs = dT; c->sc.shade = dS; c->sc.tris = dTri; c->sc.materials = dM; c->sc.texdesc = dD; c->sc.texdata = dX;
     c->sc.rootRef = 0;

@@ -144,14 +144,17 @@ struct flx_ctx {
     std::vector<void *> momAllocs;
     // temporal reprojection (TemporalState): the two G-buffer slots of 2 float4 per pixel, allocated by the first flx_gbuffer / flx_gbuffer_write; the
     // accumulation and the moments as flx_history_capture copied them (histMomBuf null: "moments" was never on at a capture); one object id per
-    // pixel beside each slot, swapped with the slots, allocated by the first of those calls that finds "motion_history" on.  Freed with the framebuffers.
+    // pixel beside each slot, swapped with the slots, allocated by the first of those calls that finds "motion_history" on; likewise one float2 of
+    // barycentrics per pixel beside each slot under "deform_history".  Freed with the framebuffers.
     struct Temporal {
         std::vector<void *> allocs;
         float4 *gb[2] = {nullptr, nullptr}, *hist = nullptr, *histMomBuf = nullptr; uint32_t *objPlane[2] = {nullptr, nullptr};
+        float2 *baryPlane[2] = {nullptr, nullptr};
         TemporalState state;
         void release() { freeAll(allocs); *this = Temporal(); }
     } temporal;
     int motionHistory = 0;      // option "motion_history": flx_objects_pose keeps a captured history, flx_reproject follows the posed objects
+    int deformHistory = 0;      // option "deform_history": every move of triangles keeps a captured history, flx_reproject follows the vertices
     // the adaptive microkernel render (ActiveListState): flag bytes, block counts and the list of active pixels, allocated by the first
     // flx_mk_adaptive_update / flx_mk_active_write for state.pix pixels and freed with the framebuffers
     struct Adaptive {

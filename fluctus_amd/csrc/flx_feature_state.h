@@ -15,35 +15,61 @@
 namespace flxd {
 // temporal reprojection (reproject.hip).  Two G-buffer slots, [0] current, [1] previous, each with the camera and the size it
 // was traced with.  traced: the slot holds a G-buffer.  objects (option "motion_history"): the object plane beside the slot
-// belongs to the slot's G-buffer and to the current definition -- never set without `traced`.  hist: flx_history_capture has copied the
-// accumulation; histMom: and the moments with it ("moments" was on then).  histMom is rewritten by the next capture and by nothing else.
+// belongs to the slot's G-buffer and to the current definition -- never set without `traced`.  bary (option "deform_history"):
+// the barycentric plane beside the slot belongs to the slot's G-buffer and to the uploaded triangle set -- never set without `traced`.
+// hist: flx_history_capture has copied the accumulation; histMom: and the moments with it ("moments" was on then).  histMom is rewritten by the
+// next capture and by nothing else.  snap ("deform_history"): triangles moved since the capture and their positions at the capture were
+// snapshotted first -- flx_reproject follows them (flx_reproject_deform.h); never set without a history.
 struct TemporalState {
-    struct Slot { flx_camera cam = {}; uint32_t W = 0, H = 0; bool traced = false, objects = false; };
+    struct Slot { flx_camera cam = {}; uint32_t W = 0, H = 0; bool traced = false, objects = false, bary = false; };
     Slot slot[2];
-    bool hist = false, histMom = false;
+    bool hist = false, histMom = false, snap = false;
 
     // flx_gbuffer traced slot 0 (withObjects: the option is on and objects are defined) | flx_gbuffer_write wrote a slot (its plane, kept only
     // while the option is on, shows no object) | flx_gbuffer_objects_write wrote the plane behind it
     void traced(const flx_camera &cam, uint32_t W, uint32_t H, bool withObjects) { slot[0] = Slot{cam, W, H, true, withObjects}; }
     void written(int s, const flx_camera &cam, uint32_t W, uint32_t H, bool motionHistory) { slot[s] = Slot{cam, W, H, true, motionHistory}; }
     void objectsWritten(int s) { slot[s].objects = true; }
-    // flx_history_capture: the current slot becomes the previous one (the caller swaps the buffers) and no longer is the current one
-    void captured(bool withMoments) { slot[1] = slot[0]; slot[1].traced = true; slot[0].traced = slot[0].objects = false; hist = true; histMom = withMoments; }
+    // ... and, right behind traced() / written(): the slot's barycentric plane was written with it (deformHistory: the option's value; a written
+    // G-buffer's plane holds the sentinel) | flx_gbuffer_bary_write wrote the plane
+    void baryWith(int s, bool deformHistory) { slot[s].bary = deformHistory; }
+    void baryWritten(int s) { slot[s].bary = true; }
+    // flx_history_capture: the current slot becomes the previous one (the caller swaps the buffers) and no longer is the current one; nothing
+    // has moved since THIS capture
+    void captured(bool withMoments) { slot[1] = slot[0]; slot[1].traced = true; slot[0].traced = slot[0].objects = slot[0].bary = false; hist = true; histMom = withMoments; snap = false; }
     // a G-buffer and a history belong to the render of one geometry
-    void dropHistory() { slot[0].traced = slot[1].traced = false; slot[0].objects = slot[1].objects = false; hist = false; }
+    void dropHistory() { slot[0].traced = slot[1].traced = false; slot[0].objects = slot[1].objects = false; slot[0].bary = slot[1].bary = false; hist = false; snap = false; }
     // triangles moved.  By flx_objects_pose with a history it can follow (flx_reproject_motion.h): the previous slot and the history stay, only
     // the current slot is gone.  Otherwise, and always for triangles set one by one -- nobody knows where those were -- everything goes.
     bool poseKeepsHistory(bool motionHistory) const { return motionHistory && hasHistory() && slot[1].objects; }
-    void trianglesMoved(bool byPose, bool motionHistory) { if (byPose && poseKeepsHistory(motionHistory)) slot[0].traced = slot[0].objects = false; else dropHistory(); }
+    void trianglesMoved(bool byPose, bool motionHistory) { snap = false; if (byPose && poseKeepsHistory(motionHistory)) slot[0].traced = slot[0].objects = slot[0].bary = false; else dropHistory(); }
+    // ... unless option "deform_history" knows where they were: with a history whose G-buffer has a barycentric plane, ANY move (one by one, a
+    // subset, a pose) keeps the previous slot and the history -- the caller has snapshotted the positions before it overwrites them when
+    // needsSnapshot() said so -- and only the current slot is gone.  Any other move does what it does without the option.
+    bool moveKeepsHistory(bool deformHistory) const { return deformHistory && hasHistory() && slot[1].bary; }
+    bool needsSnapshot(bool deformHistory) const { return moveKeepsHistory(deformHistory) && !snap; }
+    void trianglesMoved(bool byPose, bool motionHistory, bool deformHistory)
+    {
+        if (!moveKeepsHistory(deformHistory)) { trianglesMoved(byPose, motionHistory); return; }
+        snap = true; slot[0].traced = slot[0].objects = slot[0].bary = false;
+    }
     // flx_upload_scene, flx_objects_define: the planes name the objects of the earlier definition; with the option on the history goes with it
     void definitionChanged(bool motionHistory) { motionHistoryOff(); if (motionHistory) dropHistory(); }
     void motionHistoryOff() { slot[0].objects = slot[1].objects = false; }     // planes not kept up while the option is off are nobody's
+    // flx_upload_scene (behind definitionChanged): the hit indices no longer name the same triangles and the snapshot went with the scene
+    void sceneUploaded(bool deformHistory) { if (deformHistory) dropHistory(); snap = false; }
+    // "deform_history" switched off: the planes are nobody's; a move the history has not been told of otherwise takes the history with it --
+    // never a reprojection that ignores a move
+    void deformHistoryOff() { slot[0].bary = slot[1].bary = false; if (snap) dropHistory(); }
 
     bool holds(int s) const { return slot[s].traced; }
     bool holdsSized(int s, uint32_t W, uint32_t H) const { return slot[s].traced && slot[s].W == W && slot[s].H == H; }
     bool holdsObjects(int s) const { return slot[s].traced && slot[s].objects; }
+    bool holdsBary(int s) const { return slot[s].traced && slot[s].bary; }
     bool hasHistory() const { return hist && slot[1].traced; }
     bool historyFits(uint32_t W, uint32_t H) const { return slot[0].W == W && slot[0].H == H && slot[1].W == W && slot[1].H == H; }
+    bool followsMoves() const { return snap && hasHistory(); }                  // flx_reproject runs the per-vertex kernels
+    bool followsMovesReady() const { return holdsBary(0) && holdsBary(1); }     // ... and has both planes for them
 };
 
 // every object's pose now and at the last flx_history_capture (12 floats each, flx_objects_pose's matrices) with a `known` byte: unknown until

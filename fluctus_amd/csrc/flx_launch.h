@@ -27,6 +27,9 @@ struct RefitTables {
     size_t stampWords = 0;
     uint32_t epoch = 0;
     uint32_t *stageIdx = nullptr;                       // ntris indices for a host source (the triangles go to `stage`); allocated by the first such call
+    // option "deform_history" (DESIGN.md 4.3.6): the positions at the last capture, three float4 per triangle, and one moved byte per triangle;
+    // allocated by the first move that snapshots.  Whether the snapshot is of THIS capture is TemporalState::snap's to say.
+    float4 *snapPos = nullptr; uint8_t *movedFlags = nullptr;
 };
 // (source triangles, index list, listed count: a null list means every triangle of the scene, the full refit)
 void launch_refit_validate(hipStream_t, const void *, const uint32_t *, uint32_t, const Scene &, const RefitTables &, uint32_t *);
@@ -112,12 +115,18 @@ void launch_deinterleave(hipStream_t, const float *, float *, uint32_t, uint32_t
 struct DnGuided; struct DnVg;     // the two filters of denoise.hip
 template <class F> void launch_denoise(hipStream_t, const Frame &, float4 *, float4 *, float4 *, float2 *, float *, int, int, int, float, float, float,
                                        float, const flx_render_params &);
-// (the last two: the slot's object plane and the object of every triangle -- both null: no plane is written)
-void launch_gbuffer(hipStream_t, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, float4 *, uint32_t, uint32_t *, const uint32_t *);
+// (the last three: the slot's object plane and the object of every triangle -- both null: no plane is written; the slot's barycentric plane or null)
+void launch_gbuffer(hipStream_t, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, float4 *, uint32_t, uint32_t *, const uint32_t *, float2 *);
 void launch_reproject(hipStream_t, const rp_view &, const rp_params &, const float4 *, const float4 *, const float4 *, const float4 *, float4 *, float4 *);
 // (... then the current and the previous object plane, the motion table and the object count)
 void launch_reproject_motion(hipStream_t, const rp_view &, const rp_params &, const float4 *, const float4 *, const float4 *, const float4 *, float4 *, float4 *,
                              const uint32_t *, const uint32_t *, const float4 *, uint32_t);
+// option "deform_history" (flx_reproject_deform.h): (triangle count, the snapshot: three float4 per triangle) | (..., one moved byte per triangle) |
+// launch_reproject's arguments, then the current and the previous barycentric plane, the scene, the triangle count, the snapshot and the flags
+void launch_snapshot_positions(hipStream_t, const Scene &, uint32_t, float4 *);
+void launch_moved_flags(hipStream_t, const Scene &, uint32_t, const float4 *, uint8_t *);
+void launch_reproject_deform(hipStream_t, const rp_view &, const rp_params &, const float4 *, const float4 *, const float4 *, const float4 *, float4 *, float4 *,
+                             const float2 *, const float2 *, const Scene &, uint32_t, const float4 *, const uint8_t *);
 #ifdef FLX_LAB_RSTATS
 extern unsigned long long *g_lab_rstats;
 #endif

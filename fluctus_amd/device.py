@@ -26,6 +26,7 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_mk_adaptive_update", "flx_mk_adaptive_clear", "flx_mk_active_read", "flx_mk_active_write",
            "flx_update_triangles", "flx_update_triangles_subset", "flx_tree_read", "flx_tree_cost",
            "flx_objects_define", "flx_objects_pose", "flx_objects_read", "flx_gbuffer_objects_read", "flx_gbuffer_objects_write",
+           "flx_gbuffer_bary_read", "flx_gbuffer_bary_write", "flx_deform_read",
            "flx_mesh_lights_read", "flx_mesh_lights_sample"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
@@ -33,6 +34,7 @@ K_DENOISE = 9           # FLX_K_DENOISE: timed with profile level 1, read with H
 K_GBUFFER, K_REPROJECT = 10, 11      # FLX_K_GBUFFER / FLX_K_REPROJECT: profile level 1, read with HipContext.kernel_profile
 K_REFIT = 12                         # FLX_K_REFIT: the kernels of update_triangles, likewise
 K_TREE_COST = 13                     # FLX_K_TREE_COST: the kernels of tree_cost, likewise
+K_SNAPSHOT, K_MOVED_FLAGS = 14, 15   # FLX_K_SNAPSHOT / FLX_K_MOVED_FLAGS: option "deform_history"'s snapshot and flag passes, likewise
 NO_OBJECT = 0xFFFFFFFF               # FLX_NO_OBJECT: a triangle that belongs to no object (objects_define)
 
 
@@ -437,6 +439,26 @@ class HipContext:
         o = np.ascontiguousarray(objects, np.uint32).reshape(-1)
         assert o.size == self.local_pixels(), (o.size, self.local_pixels())
         self._chk(self.L.flx_gbuffer_objects_write(self.h, int(slot), _p(o)))
+
+    # ... across a per-triangle move: set_option("deform_history", 1) (include/fluctus_hip.h)
+    def gbuffer_bary_read(self, slot=0):
+        """test hook: (pixels, 2) float32, the barycentrics (u, v) of every pixel of the slot's G-buffer ((-1, -1): a miss, the area light)"""
+        out = np.empty((self.local_pixels(), 2), np.float32)
+        self._chk(self.L.flx_gbuffer_bary_read(self.h, int(slot), _p(out)))
+        return out
+
+    def gbuffer_bary_write(self, slot, bary):
+        """test hook: two float32 per pixel into the barycentric plane of slot 0 (current) or 1 (previous); after gbuffer_write, which fills it with (-1, -1)"""
+        b = np.ascontiguousarray(bary, np.float32).reshape(-1, 2)
+        assert b.shape[0] == self.local_pixels(), (b.shape, self.local_pixels())
+        self._chk(self.L.flx_gbuffer_bary_write(self.h, int(slot), _p(b)))
+
+    def deform_read(self, ntris):
+        """test hook (blocking) -> ((ntris, 3, 3) float32: every triangle's positions as the first move after the last capture found them,
+        (ntris,) bool: its positions now differ from them bitwise).  ntris: the uploaded scene's triangle count.  Fails without a snapshot."""
+        pos, moved = np.empty((int(ntris), 3, 3), np.float32), np.empty(int(ntris), np.uint8)
+        self._chk(self.L.flx_deform_read(self.h, _p(pos), _p(moved)))
+        return pos, moved.astype(bool)
 
     def kernel_profile(self, kernel):
         """(milliseconds, launches) of one FLX_K_* id accumulated while profiling (level 1) since the last profile_reset; after finish()"""

@@ -576,6 +576,8 @@ int fh_tracer_set_temporal_reprojection(void *t, int on) { FH_TRY ((Tracer *)t)-
 int fh_tracer_get_temporal_reprojection(void *t) { return ((Tracer *)t)->getTemporalReprojection() ? 1 : 0; }
 int fh_tracer_set_motion_reprojection(void *t, int on) { FH_TRY ((Tracer *)t)->setMotionReprojection(on != 0); FH_CATCH }
 int fh_tracer_get_motion_reprojection(void *t) { return ((Tracer *)t)->getMotionReprojection() ? 1 : 0; }
+int fh_tracer_set_deform_reprojection(void *t, int on) { FH_TRY ((Tracer *)t)->setDeformReprojection(on != 0); FH_CATCH }
+int fh_tracer_get_deform_reprojection(void *t) { return ((Tracer *)t)->getDeformReprojection() ? 1 : 0; }
 int fh_tracer_set_max_history(void *t, float n) { FH_TRY ((Tracer *)t)->setMaxHistory(n); FH_CATCH }
 int fh_tracer_set_mesh_lights(void *t, int on) { FH_TRY ((Tracer *)t)->setMeshLights(on != 0); FH_CATCH }
 int fh_tracer_set_mesh_lights_wavefront(void *t, int on) { FH_TRY ((Tracer *)t)->setMeshLightsWavefront(on != 0); FH_CATCH }

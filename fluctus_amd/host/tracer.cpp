@@ -133,8 +133,17 @@ void Tracer::updateGeometry(const std::vector<flx_triangle> &tris)
     if (!scene || !bvh) throw std::runtime_error("Tracer::updateGeometry: no scene (init first)");
     if (tris.size() != scene->getTriangles().size()) throw std::runtime_error("Tracer::updateGeometry: the triangle count differs from the scene's");
     if (rebuildMode != RebuildOff) adoptFinishedRebuild();
-    refitAll(tris);
+    bool captured = false;
+    const bool keep = keepHistoryAcrossMove(deformOn, captured);
+    try {
+        refitAll(tris);
+    } catch (...) {
+        if (captured) paramsUpdatePending = true;            // the capture has handed the current slot over: the next update() traces it again and reprojects (nothing moved)
+        throw;
+    }
+    const uint32_t topologies = rebuilds;
     afterMove();
+    movedKeepingHistory(keep, topologies);
 }
 // ... a subset of them (flx_update_triangles_subset, BVH::refitSubset): only the boxes above the listed triangles are refitted.
 // Takes part in the rebuild policy exactly as the full overload does.
@@ -143,12 +152,37 @@ void Tracer::updateGeometry(const std::vector<uint32_t> &indices, const std::vec
     if (!scene || !bvh) throw std::runtime_error("Tracer::updateGeometry: no scene (init first)");
     if (indices.size() != tris.size()) throw std::runtime_error("Tracer::updateGeometry: as many triangles as indices");
     if (rebuildMode != RebuildOff) adoptFinishedRebuild();
-    for (auto *c : ranks()) c->updateTriangles(indices, tris);   // refused (a bad index list or triangle): throws, and everything is still the old geometry's
+    bool captured = false;
+    const bool keep = keepHistoryAcrossMove(deformOn, captured);
+    try {
+        for (auto *c : ranks()) c->updateTriangles(indices, tris);   // refused (a bad index list or triangle): throws, and everything is still the old geometry's
+    } catch (...) {
+        if (captured) paramsUpdatePending = true;
+        throw;
+    }
     std::vector<flx_triangle> all = scene->getTriangles();
     for (size_t k = 0; k < indices.size(); k++) all[indices[k]] = tris[k];      // (the device has checked the list: ascending, in range)
     bvh->refitSubset(all, indices);
     scene->getTriangles().swap(all);
+    const uint32_t topologies = rebuilds;
     afterMove();
+    movedKeepingHistory(keep, topologies);
+}
+// Reprojection across a move of triangles, shared by poseObjects and both updateGeometry overloads.  `on`: the switch
+// under which this kind of move keeps the history.  With a history by update()'s own conditions, capture it before the ranks are moved -- at
+// most once per frame -- so that the device keeps it.  captured: this call made the capture (a refused move must then re-arm update()).
+bool Tracer::keepHistoryAcrossMove(bool on, bool &captured)
+{
+    const bool keep = on && historyExists(true);
+    captured = keep && !poseHistory;
+    if (captured) { clctx->historyCapture(); poseHistory = true; }
+    return keep;
+}
+// ... and after afterMove(), whose geometryChanged dropped the host's view of the history: the device still has it, unless a rebuild inside
+// afterMove re-uploaded the topology (the device dropped its history with the upload)
+void Tracer::movedKeepingHistory(bool keep, uint32_t topologiesBefore)
+{
+    if (keep && rebuilds == topologiesBefore) { haveGbuffer = true; poseHistory = true; }
 }
 // Objects moved by their transforms: updateGeometry(indices, tris) with the triangles made where they are needed -- on every rank
 // by flx_objects_pose, here by the same csrc/flx_pose.h function for the host tree and the scene's copy.
@@ -190,9 +224,8 @@ void Tracer::poseObjects(const std::vector<uint32_t> &ids, const std::vector<flo
     if (rebuildMode != RebuildOff) adoptFinishedRebuild();
     // motion-aware reprojection: with a history by update()'s own conditions, capture it before the ranks are posed -- at most once
     // per frame -- so that flx_objects_pose keeps it
-    const bool keep = motionOn && historyExists(true);
-    const bool capture = keep && !poseHistory;
-    if (capture) { clctx->historyCapture(); poseHistory = true; }
+    bool capture = false;
+    const bool keep = keepHistoryAcrossMove(motionOn || deformOn, capture);      // (under per-vertex reprojection a pose is a move of triangles like any other)
     try {
         for (auto *c : ranks()) c->poseObjects(ids, xforms12);    // refused (a bad list or matrix, a vertex out of range): throws, and everything is still the old geometry's
     } catch (...) {
@@ -213,7 +246,7 @@ void Tracer::poseObjects(const std::vector<uint32_t> &ids, const std::vector<flo
     scene->getTriangles().swap(all);
     const uint32_t topologies = rebuilds;
     afterMove();
-    if (keep && rebuilds == topologies) { haveGbuffer = true; poseHistory = true; }      // (a rebuild inside afterMove re-defined the objects: the device dropped the history)
+    movedKeepingHistory(keep, topologies);                   // (a rebuild inside afterMove re-defined the objects: the device dropped the history)
 }
 // what follows every move of the triangles: the resets of geometryChanged, then the rebuild policy on the trees as they stand now
 void Tracer::afterMove()
@@ -345,14 +378,25 @@ void Tracer::setTemporalReprojection(bool on)
     temporalOn = on;
     dropHistory(); temporalFrames = 0;
     if (!on && motionOn) setMotionReprojection(false);
+    if (!on && deformOn) setDeformReprojection(false);
 }
 void Tracer::setMotionReprojection(bool on)
 {
     if (on && !peers.empty()) throw std::runtime_error("setMotionReprojection: temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
     if (on && !temporalOn) throw std::runtime_error("setMotionReprojection: needs setTemporalReprojection(true)");
+    if (on && deformOn) throw std::runtime_error("setMotionReprojection: per-vertex reprojection is on, which follows poseObjects too; setDeformReprojection(false) first");
     for (auto *c : ranks()) c->setOption("motion_history", on ? 1 : 0);
     motionOn = on;
     dropHistory();                                           // a G-buffer traced under the other setting has no object plane (or one nobody keeps up)
+}
+void Tracer::setDeformReprojection(bool on)
+{
+    if (on && !peers.empty()) throw std::runtime_error("setDeformReprojection: temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
+    if (on && !temporalOn) throw std::runtime_error("setDeformReprojection: needs setTemporalReprojection(true)");
+    if (on && motionOn) throw std::runtime_error("setDeformReprojection: motion-aware reprojection is on; setMotionReprojection(false) first (this switch follows poseObjects too)");
+    for (auto *c : ranks()) c->setOption("deform_history", on ? 1 : 0);
+    deformOn = on;
+    dropHistory();                                           // a G-buffer traced under the other setting has no barycentric plane (or one nobody keeps up)
 }
 // everything of RenderParams that shapes the radiance of a point, i.e. all but the camera (bytes 96..175) and the post-process (exposure,
 // tmOperator: 176..183), equals what the G-buffer's frames were rendered with

@@ -123,6 +123,14 @@ public:
     // the geometry restarts as ever: updateGeometry in either form, a rebuild the policy runs or adopts, the microkernel branch, renderSingle.
     void setMotionReprojection(bool on);
     bool getMotionReprojection() const { return motionOn; }
+    // Per-vertex reprojection, default off; needs setTemporalReprojection(true) and throws without it, on a multi-rank Tracer
+    // and while motion-aware reprojection is on (the two options refuse each other on the device; this one follows poseObjects as well).  On:
+    // updateGeometry in both forms and poseObjects on the WAVEFRONT integrator keep the accumulation as poseObjects does under
+    // setMotionReprojection -- capture (at most once per frame), move, and the next update() traces the G-buffer, resets and reprojects, each
+    // moved triangle's pixels looking their history up where that point of the triangle was.  A rebuild the policy runs or adopts, the
+    // microkernel branch and renderSingle restart as ever.
+    void setDeformReprojection(bool on);
+    bool getDeformReprojection() const { return deformOn; }
     float getMaxHistory() const { return maxHistory; }
     // Emissive triangles as lights, default off: only the microkernel integrator sees them, so while this is on update() takes
     // its microkernel branch (as renderSingle forces it) and toggleRenderer() to the wavefront loop THROWS -- lamps never go silently dark.
@@ -208,7 +216,9 @@ private:
     void dropHistory() { haveGbuffer = false; poseHistory = false; }
     bool historyExists(bool posed) const;                                         // update()'s conditions for a history worth capturing, shared with poseObjects
     bool onlyCameraChanged(bool posed = false) const;                             // params against gbParams, the camera and the post-process aside (posed: and worldRadius, which a pose re-derives)
-    bool motionOn = false;
+    bool motionOn = false, deformOn = false;
+    bool keepHistoryAcrossMove(bool on, bool &captured);                          // capture before the ranks move (at most once per frame)
+    void movedKeepingHistory(bool keep, uint32_t topologiesBefore);               // ... and re-arm update() after afterMove()
     bool poseHistory = false;                                                     // poseObjects has captured the history of this frame: the next update() reprojects it
     uint32_t gbWidth = 0, gbHeight = 0;                                           // ... traced at this size
     uint32_t framesSinceGbuffer = 0;                                              // > 0: there is an accumulation worth capturing

@@ -224,6 +224,16 @@ class Tracer:
     def motion_reprojection(self):
         return bool(self.L.fh_tracer_get_motion_reprojection(self.h))
 
+    def set_deform_reprojection(self, on):
+        """Tracer::setDeformReprojection (default off; needs set_temporal_reprojection(True), refuses while motion reprojection is on):
+        update_geometry in both forms and pose_objects on the wavefront integrator keep the accumulated image -- a moved triangle's pixels look
+        their history up where that point of the triangle was.  Single-GPU."""
+        host._chk(self.L.fh_tracer_set_deform_reprojection(self.h, int(bool(on))))
+
+    @property
+    def deform_reprojection(self):
+        return bool(self.L.fh_tracer_get_deform_reprojection(self.h))
+
     def set_max_history(self, n):
         """Tracer::setMaxHistory: the sample count a reprojected pixel may keep (flx_reproject's max_history, >= 1; default 32)"""
         host._chk(self.L.fh_tracer_set_max_history(self.h, C.c_float(float(n))))

@@ -274,6 +274,39 @@ int flx_gbuffer_write(flx_ctx *ctx, int slot, const float *in_8_floats_per_pixel
  * FLX_NO_OBJECT, so a test writes G first and objects second.  An id that is not below the object count reads as FLX_NO_OBJECT. */
 int flx_gbuffer_objects_read(flx_ctx *ctx, int slot, uint32_t *out_1_uint32_per_pixel);
 int flx_gbuffer_objects_write(flx_ctx *ctx, int slot, const uint32_t *in_1_uint32_per_pixel);
+/* ---- ... across a per-triangle move (an animated mesh: skinning, cloth, morph targets): flx_set_option(ctx, "deform_history", 1)
+ * (csrc/flx_reproject_deform.h).  Off (the default) every call does what it does without the option.  On, the sequence is
+ *     ... render under shape A, camera A ...
+ *     flx_gbuffer; flx_history_capture
+ *     flx_update_triangles(B) | flx_update_triangles_subset(B) | flx_objects_pose(B), any number of them
+ *                                              (the FIRST one after a capture copies every triangle's positions aside before it overwrites any;
+ *                                               all keep the PREVIOUS slot and the captured history; only the current slot becomes "not traced")
+ *     [flx_set_params(camera B)]               (camera and triangles may move in the same frame)
+ *     flx_gbuffer; flx_wf_reset or flx_mk_reset (unchanged); flx_reproject; ... render on ...
+ * What the option changes:
+ * flx_gbuffer also writes one float2 per pixel beside the slot: the barycentrics (u, v) the traversal returned for a triangle hit (u weighs vertex
+ * 1, v vertex 2), (-1, -1) on a miss and on the implicit area-light quad; G0 / G1 are the same bytes.  flx_history_capture swaps these planes
+ * with the slots.
+ * A move of triangles -- by any of the three calls, from a host or a device source -- keeps a captured history whose G-buffer has such a plane;
+ * without one the history is dropped as without the option.  A refused call snapshots nothing and changes no state.  flx_upload_scene drops the
+ * history while the option is on (the hit indices no longer name the same triangles).  Switching the option off after a move drops it too.
+ * flx_reproject (same signature, same parameters): without a move since the capture it is the call above; after one, a pixel whose triangle's
+ * nine position words differ bitwise from the snapshot looks its history up where that surface point WAS: P' = (1 - u - v) q0 + u q1 + v q2 over
+ * the positions at the capture, N' = the old triangle's unit normal on the side N is on, and a tap is refused when exactly one of the tap's and
+ * the pixel's triangles moved.  With nothing moved every pixel equals the plain call bit for bit.  A triangle that was degenerate at the capture
+ * gets no history.  Two different moved surfaces sliding coplanar over each other still share taps.  Stale shadows and reflections on surfaces that
+ * did not move decay only through max_history, as under "motion_history".  After a move, a slot without its plane is refused with a message.
+ * "deform_history" and "motion_history" refuse each other: this option follows flx_objects_pose as well.
+ * The planes are allocated by the first flx_gbuffer / flx_gbuffer_write that finds the option on, the snapshot (48 B per triangle) and the flags
+ * (1 B per triangle) by the first move that needs them; they stay with the scene.
+ * flx_gbuffer_bary_read / flx_gbuffer_bary_write: test hooks beside flx_gbuffer_objects_read / _write, two floats per pixel, blocking.  The write
+ * needs the option on and the slot traced at the current size; while the option is on flx_gbuffer_write fills the slot's plane with (-1, -1), so
+ * a test writes G first and barycentrics second.
+ * flx_deform_read: test hook, blocking: the nine position floats of every triangle as snapshotted and one byte per triangle, 1 where the
+ * positions now differ from them (either may be NULL).  Fails when no move has snapshotted since the last capture. */
+int flx_gbuffer_bary_read(flx_ctx *ctx, int slot, float *out_2_floats_per_pixel);
+int flx_gbuffer_bary_write(flx_ctx *ctx, int slot, const float *in_2_floats_per_pixel);
+int flx_deform_read(flx_ctx *ctx, float *out_9_floats_per_triangle, uint8_t *out_1_byte_per_triangle);
 
 /* ---- microkernel integrator (the reference's second integrator).  One path per pixel (needs
  * num_tasks >= width*height to cover the image), `phase` state machine, exactly one sample per pixel per pass.
@@ -358,7 +391,9 @@ enum { FLX_K_RESET = 0, FLX_K_RAYGEN = 1, FLX_K_EXTEND = 2, FLX_K_SHADOW = 3, FL
        FLX_K_REPROJECT = 11,   /* flx_reproject */
        FLX_K_REFIT = 12,       /* the kernels of one flx_update_triangles / _subset; flx_objects_pose adds its pose kernels as a span of their own */
        FLX_K_TREE_COST = 13,   /* the kernels of one flx_tree_cost */
-       FLX_K_COUNT = 14 };
+       FLX_K_SNAPSHOT = 14,    /* option "deform_history": the copy of the positions a move of triangles makes after a capture */
+       FLX_K_MOVED_FLAGS = 15, /* ... and the moved-flag pass as flx_deform_read launches it (inside flx_reproject it is part of FLX_K_REPROJECT) */
+       FLX_K_COUNT = 16 };
 /* on: 0 off | 1 time every kernel | 2 time only the two trace kernels (+ their span), as the reference does | 3 only the
  * extension kernel | 4 the three kernels bench.py prices against a roof: extension, logic (the fused pass incl. its queue scan + scatter), shadow.
  * Each event pair costs a few microseconds of stream time, which shows at ~11 launches per 0.7 ms
