@@ -231,7 +231,7 @@ int flx_set_params(flx_ctx *c, const void *p240)
     const uint32_t oldW = c->params.width, oldH = c->params.height;
     memcpy(&c->params, p240, sizeof(flx_render_params));   // kernels receive the struct by value at launch = in-order semantics
     NEED(c, c->params.width > 0 && c->params.height > 0, "flx_set_params: zero-sized framebuffer");
-    if (c->params.width != oldW || c->params.height != oldH) c->ad.state.dropped();      // the list of active pixels indexes the old image
+    if (c->params.width != oldW || c->params.height != oldH) { c->ad.state.dropped(); c->temporal.state.imageResized(); }      // the list of active pixels and the mark index the old image
     c->haveParams = true;
     return allocFrame(c);
 }
@@ -242,6 +242,7 @@ int flx_set_partition(flx_ctx *c, uint32_t rank, uint32_t nranks)
     NEED(c, nranks >= 1 && rank < nranks, "flx_set_partition: bad rank");
     c->fr.rank = rank; c->fr.nranks = nranks;
     c->ad.state.dropped();                               // the list of active pixels indexes the pixels of the old partition
+    c->temporal.state.partitionSet();                    // ... and so does the mark of flx_history_mark
     return c->haveParams ? allocFrame(c) : 0;
 }
 uint32_t flx_local_pixels(flx_ctx *c) { return c->fr.localPixels; }

@@ -5,6 +5,7 @@
 #include "flx_denoise_vg.h"
 #include "flx_reproject_motion.h"
 #include "flx_reproject_deform.h"
+#include "flx_rectify.h"
 #include "flx_adaptive.h"
 #include <cstring>
 
@@ -167,6 +168,69 @@ int flx_reproject(flx_ctx *c, const flx_reproject_params *pp)
     LAUNCHED(c);
     return 0;
 }
+// ---- history rectification (csrc/flx_rectify.h, rectify.hip): the mark and the test of the new samples against it.  Like the
+// calls above: an unpartitioned context, CALL_OBSERVE, no path state, queue or counter.
+int flx_history_mark(flx_ctx *c)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (temporalReady(c, "flx_history_mark")) return 1;
+    NEED(c, c->temporal.gb[0] && c->temporal.state.holdsSized(0, c->params.width, c->params.height),
+         "flx_history_mark: no G-buffer of the current size has been traced for the current slot (flx_gbuffer first)");
+    flx_ctx::Temporal &t = c->temporal;
+    const size_t n = c->fr.localPixels;
+    const bool withMom = c->moments && c->fr.moments;
+    // (a failed allocation releases slots, history and mark together, so a retry starts clean: as flx_history_capture)
+    if ((!t.mark && (dalloc(c, t.allocs, &t.mark, n) || dalloc(c, t.allocs, &t.rcRec, n) || dalloc(c, t.allocs, &t.lambda, n))) ||
+        (withMom && !t.markMomBuf && dalloc(c, t.allocs, &t.markMomBuf, n))) {
+        const std::string why = c->err; t.release(); c->err = "flx_history_mark: " + why; return 1;
+    }
+    HIPCHK(c, hipMemcpyAsync(t.mark, c->fr.pixels, n * 16, hipMemcpyDeviceToDevice, c->stream));
+    if (withMom) HIPCHK(c, hipMemcpyAsync(t.markMomBuf, c->fr.moments, n * 16, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(t.lambda, 0, n * 4, c->stream));      // no flx_history_rectify has looked at this mark
+    t.state.marked(withMom);
+    return 0;
+}
+int flx_history_rectify(flx_ctx *c, const flx_rectify_params *pp)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (temporalReady(c, "flx_history_rectify")) return 1;
+    rc_params rc = rc_defaults();
+    if (pp) { rc.radius = pp->radius; rc.gamma = pp->gamma; rc.sensitivity = pp->sensitivity; rc.lum_floor = pp->lum_floor; rc.min_pixels = pp->min_pixels;
+              rc.plane_tolerance_px = pp->plane_tolerance_px; rc.normal_cos = pp->normal_cos; }
+    NEED(c, rc_params_ok(rc), "flx_history_rectify: parameters must be finite with radius in 1..4, gamma >= 0, sensitivity > 0, lum_floor >= 0, "
+                              "min_pixels in 1..(2 radius + 1)^2, plane_tolerance_px > 0, normal_cos in [-1, 1]");
+    flx_ctx::Temporal &t = c->temporal;
+    const TemporalState &ts = t.state;
+    NEED(c, ts.hasMark() && t.mark && t.rcRec && t.lambda, "flx_history_rectify: no mark (flx_history_mark first)");
+    NEED(c, ts.markLive() && t.gb[0] && ts.holdsSized(0, c->params.width, c->params.height),
+         "flx_history_rectify: the current slot holds no G-buffer of the mark's size (flx_gbuffer)");
+    const bool mom = c->moments && c->fr.moments && ts.markHasMoments() && t.markMomBuf;
+    const int W = (int)c->params.width, H = (int)c->params.height;
+    { ScopedTimer tm(c, FLX_K_RECTIFY);
+      launch_rectify(c->stream, rc, rc_footprint(ts.slot[0].cam.fov, H), W, H, t.gb[0], t.rcRec, reinterpret_cast<float4 *>(c->fr.pixels), t.mark,
+                     mom ? reinterpret_cast<float4 *>(c->fr.moments) : nullptr, mom ? t.markMomBuf : nullptr, t.lambda); }
+    LAUNCHED(c);
+    return 0;
+}
+// test hook: the mark (4 floats per pixel), its moments (refused when the mark has none) and lambda as the last flx_history_rectify since the
+// mark left it (1 float per pixel; zeros before one).  Any output may be null.  Blocking.
+int flx_history_mark_read(flx_ctx *c, float *out_mark4, float *out_mark_mom4, float *out_lambda)
+{
+    ENTER(c, CALL_OBSERVE);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (temporalReady(c, "flx_history_mark_read")) return 1;
+    flx_ctx::Temporal &t = c->temporal;
+    NEED(c, t.state.hasMark() && t.mark && t.lambda, "flx_history_mark_read: no mark (flx_history_mark first)");
+    NEED(c, !out_mark_mom4 || (t.state.markHasMoments() && t.markMomBuf), "flx_history_mark_read: the mark holds no moments (option \"moments\" was off at flx_history_mark)");
+    const size_t n = (size_t)t.state.markW * t.state.markH;
+    if (out_mark4) HIPCHK(c, hipMemcpyAsync(out_mark4, t.mark, n * 16, hipMemcpyDeviceToHost, c->stream));
+    if (out_mark_mom4) HIPCHK(c, hipMemcpyAsync(out_mark_mom4, t.markMomBuf, n * 16, hipMemcpyDeviceToHost, c->stream));
+    if (out_lambda) HIPCHK(c, hipMemcpyAsync(out_lambda, t.lambda, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
 // test hooks in the spirit of flx_state_import: slot 0 = current, 1 = previous; 8 floats per pixel (G0, G1) and the slot's 80-byte camera.  Blocking.
 int flx_gbuffer_read(flx_ctx *c, int slot, float *out8, void *camera80)
 {
@@ -295,7 +359,7 @@ int flx_deform_read(flx_ctx *c, float *out9, uint8_t *out_moved)
 // ---- microkernel integrator.  One path per pixel, framebuffers indexed by the path id: single-GPU only, the pixel
 // partition belongs to the wavefront path (allocFrame sizes the buffers for the rank's LOCAL pixels).
 #define MK_READY(c) do { READY(c, CALL_OBSERVE); NEED(c, (c)->fr.nranks == 1, "the microkernel integrator is single-GPU: flx_set_partition(ctx, 0, 1) first"); } while (0)
-int flx_mk_reset(flx_ctx *c) { MK_READY(c); c->ad.state.dropped(); launch_mk_reset(c->stream, c->st, c->fr, c->params); LAUNCHED(c); return 0; }
+int flx_mk_reset(flx_ctx *c) { MK_READY(c); c->ad.state.dropped(); c->temporal.state.accumulationReset(); launch_mk_reset(c->stream, c->st, c->fr, c->params); LAUNCHED(c); return 0; }
 // with a list of active pixels installed (flx_mk_adaptive_update / flx_mk_active_write) the four kernels of a sample pass run their list-driven
 // instances over it; an empty list makes them no-ops (microkernel.hip: mk_dispatch).  With option "mesh_lights" and emissive triangles the two
 // kernels that see lights run their MESH instances.

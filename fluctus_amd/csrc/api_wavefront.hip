@@ -117,7 +117,7 @@ int flxd::enter(flx_ctx *c, Call call)
 
 extern "C" {
 
-int flx_wf_reset(flx_ctx *c) { READY(c, CALL_OBSERVE); flushExt(c); c->raygenQueueEmpty = false; /* k_reset fills the raygen queue */ { ScopedTimer t(c, FLX_K_RESET); launch_reset(c->stream, c->st, c->qs, c->fr, c->params); } LAUNCHED(c); return 0; }
+int flx_wf_reset(flx_ctx *c) { READY(c, CALL_OBSERVE); flushExt(c); c->temporal.state.accumulationReset(); c->raygenQueueEmpty = false; /* k_reset fills the raygen queue */ { ScopedTimer t(c, FLX_K_RESET); launch_reset(c->stream, c->st, c->qs, c->fr, c->params); } LAUNCHED(c); return 0; }
 int flx_wf_raygen(flx_ctx *c)
 {
     if (c->phase == PH_DEFER_LOGIC) { ENTER(c, CALL_RAYGEN); return 0; }      // deferred behind the deferred flx_wf_logic (its queue does not exist yet)

@@ -150,6 +150,9 @@ struct flx_ctx {
         std::vector<void *> allocs;
         float4 *gb[2] = {nullptr, nullptr}, *hist = nullptr, *histMomBuf = nullptr; uint32_t *objPlane[2] = {nullptr, nullptr};
         float2 *baryPlane[2] = {nullptr, nullptr};
+        // history rectification: the accumulation and the moments as flx_history_mark copied them (markMomBuf null: "moments" was
+        // never on at a mark), the prepare records and the lambda plane of flx_history_rectify; allocated by the first flx_history_mark
+        float4 *mark = nullptr, *markMomBuf = nullptr, *rcRec = nullptr; float *lambda = nullptr;
         TemporalState state;
         void release() { freeAll(allocs); *this = Temporal(); }
     } temporal;

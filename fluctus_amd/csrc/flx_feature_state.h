@@ -20,10 +20,14 @@ namespace flxd {
 // hist: flx_history_capture has copied the accumulation; histMom: and the moments with it ("moments" was on then).  histMom is rewritten by the
 // next capture and by nothing else.  snap ("deform_history"): triangles moved since the capture and their positions at the capture were
 // snapshotted first -- flx_reproject follows them (flx_reproject_deform.h); never set without a history.
+// mark (history rectification): flx_history_mark has copied the accumulation of a markW x markH image; markMom: and the moments
+// with it.  The mark belongs to the accumulation it was copied from and to the current slot's G-buffer: whatever restarts the accumulation,
+// re-partitions or re-shapes the image, hands the current slot over, un-traces it or uploads a scene drops it.
 struct TemporalState {
     struct Slot { flx_camera cam = {}; uint32_t W = 0, H = 0; bool traced = false, objects = false, bary = false; };
     Slot slot[2];
     bool hist = false, histMom = false, snap = false;
+    bool mark = false, markMom = false; uint32_t markW = 0, markH = 0;
 
     // flx_gbuffer traced slot 0 (withObjects: the option is on and objects are defined) | flx_gbuffer_write wrote a slot (its plane, kept only
     // while the option is on, shows no object) | flx_gbuffer_objects_write wrote the plane behind it
@@ -36,13 +40,13 @@ struct TemporalState {
     void baryWritten(int s) { slot[s].bary = true; }
     // flx_history_capture: the current slot becomes the previous one (the caller swaps the buffers) and no longer is the current one; nothing
     // has moved since THIS capture
-    void captured(bool withMoments) { slot[1] = slot[0]; slot[1].traced = true; slot[0].traced = slot[0].objects = slot[0].bary = false; hist = true; histMom = withMoments; snap = false; }
+    void captured(bool withMoments) { slot[1] = slot[0]; slot[1].traced = true; slot[0].traced = slot[0].objects = slot[0].bary = false; hist = true; histMom = withMoments; snap = false; markDropped(); }
     // a G-buffer and a history belong to the render of one geometry
-    void dropHistory() { slot[0].traced = slot[1].traced = false; slot[0].objects = slot[1].objects = false; slot[0].bary = slot[1].bary = false; hist = false; snap = false; }
+    void dropHistory() { slot[0].traced = slot[1].traced = false; slot[0].objects = slot[1].objects = false; slot[0].bary = slot[1].bary = false; hist = false; snap = false; markDropped(); }
     // triangles moved.  By flx_objects_pose with a history it can follow (flx_reproject_motion.h): the previous slot and the history stay, only
     // the current slot is gone.  Otherwise, and always for triangles set one by one -- nobody knows where those were -- everything goes.
     bool poseKeepsHistory(bool motionHistory) const { return motionHistory && hasHistory() && slot[1].objects; }
-    void trianglesMoved(bool byPose, bool motionHistory) { snap = false; if (byPose && poseKeepsHistory(motionHistory)) slot[0].traced = slot[0].objects = slot[0].bary = false; else dropHistory(); }
+    void trianglesMoved(bool byPose, bool motionHistory) { snap = false; markDropped(); if (byPose && poseKeepsHistory(motionHistory)) slot[0].traced = slot[0].objects = slot[0].bary = false; else dropHistory(); }
     // ... unless option "deform_history" knows where they were: with a history whose G-buffer has a barycentric plane, ANY move (one by one, a
     // subset, a pose) keeps the previous slot and the history -- the caller has snapshotted the positions before it overwrites them when
     // needsSnapshot() said so -- and only the current slot is gone.  Any other move does what it does without the option.
@@ -51,16 +55,24 @@ struct TemporalState {
     void trianglesMoved(bool byPose, bool motionHistory, bool deformHistory)
     {
         if (!moveKeepsHistory(deformHistory)) { trianglesMoved(byPose, motionHistory); return; }
-        snap = true; slot[0].traced = slot[0].objects = slot[0].bary = false;
+        snap = true; slot[0].traced = slot[0].objects = slot[0].bary = false; markDropped();
     }
     // flx_upload_scene, flx_objects_define: the planes name the objects of the earlier definition; with the option on the history goes with it
     void definitionChanged(bool motionHistory) { motionHistoryOff(); if (motionHistory) dropHistory(); }
     void motionHistoryOff() { slot[0].objects = slot[1].objects = false; }     // planes not kept up while the option is off are nobody's
     // flx_upload_scene (behind definitionChanged): the hit indices no longer name the same triangles and the snapshot went with the scene
-    void sceneUploaded(bool deformHistory) { if (deformHistory) dropHistory(); snap = false; }
+    void sceneUploaded(bool deformHistory) { if (deformHistory) dropHistory(); snap = false; markDropped(); }
     // "deform_history" switched off: the planes are nobody's; a move the history has not been told of otherwise takes the history with it --
     // never a reprojection that ignores a move
     void deformHistoryOff() { slot[0].bary = slot[1].bary = false; if (snap) dropHistory(); }
+
+    // flx_history_mark copied the accumulation (and the moments) under the current slot | flx_wf_reset, flx_mk_reset: the accumulation restarted |
+    // flx_set_params with another width or height | flx_set_partition -- and every transition above that takes the current slot away
+    void marked(bool withMoments) { mark = true; markMom = withMoments; markW = slot[0].W; markH = slot[0].H; }
+    void accumulationReset() { markDropped(); }
+    void imageResized() { markDropped(); }
+    void partitionSet() { markDropped(); }
+    void markDropped() { mark = false; markMom = false; }
 
     bool holds(int s) const { return slot[s].traced; }
     bool holdsSized(int s, uint32_t W, uint32_t H) const { return slot[s].traced && slot[s].W == W && slot[s].H == H; }
@@ -70,6 +82,9 @@ struct TemporalState {
     bool historyFits(uint32_t W, uint32_t H) const { return slot[0].W == W && slot[0].H == H && slot[1].W == W && slot[1].H == H; }
     bool followsMoves() const { return snap && hasHistory(); }                  // flx_reproject runs the per-vertex kernels
     bool followsMovesReady() const { return holdsBary(0) && holdsBary(1); }     // ... and has both planes for them
+    bool hasMark() const { return mark; }
+    bool markLive() const { return mark && holdsSized(0, markW, markH); }       // flx_history_rectify: the mark and the G-buffer it is compared under
+    bool markHasMoments() const { return mark && markMom; }
 };
 
 // every object's pose now and at the last flx_history_capture (12 floats each, flx_objects_pose's matrices) with a `known` byte: unknown until

@@ -5,7 +5,7 @@
 #include "flx_device.h"
 #include <vector>
 
-namespace flx { struct ad_params; struct rp_view; struct rp_params; }     // flx_adaptive.h, flx_reproject.h: passed by reference only
+namespace flx { struct ad_params; struct rp_view; struct rp_params; struct rc_params; }     // flx_adaptive.h, flx_reproject.h, flx_rectify.h: passed by reference only
 
 namespace flxd {
 // What flx_upload_scene keeps for flx_update_triangles (refit.hip): the records of each depth of both trees (deepest level launched first), where
@@ -127,6 +127,9 @@ void launch_snapshot_positions(hipStream_t, const Scene &, uint32_t, float4 *);
 void launch_moved_flags(hipStream_t, const Scene &, uint32_t, const float4 *, uint8_t *);
 void launch_reproject_deform(hipStream_t, const rp_view &, const rp_params &, const float4 *, const float4 *, const float4 *, const float4 *, float4 *, float4 *,
                              const float2 *, const float2 *, const Scene &, uint32_t, const float4 *, const uint8_t *);
+// flx_history_rectify (flx_rectify.h, rectify.hip): parameters, the current camera's footprint, W, H, the current G-buffer slot, the prepare records
+// (scratch, one float4 per pixel), which = 0 and its mark, which = 7 and its mark (both null: the moments are left alone), the lambda plane
+void launch_rectify(hipStream_t, const rc_params &, float, int, int, const float4 *, float4 *, float4 *, float4 *, float4 *, float4 *, float *);
 #ifdef FLX_LAB_RSTATS
 extern unsigned long long *g_lab_rstats;
 #endif

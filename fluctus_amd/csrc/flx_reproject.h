@@ -92,6 +92,9 @@ FLX_HD bool rp_project(const rp_view &vw, f3 P, float *xf, float *yf)
 }
 
 FLX_HD bool rp_is_hit(rp4 g0) { return (int32_t)f2u(g0.w) >= 0; }
+/* the two tests that tie a tap (Pq, Nq) to the surface of the pixel (P, N); tol = plane_tolerance_px * t * footprint.  A NaN rejects. */
+FLX_HD bool rp_same_plane(f3 Pq, f3 P, f3 N, float tol) { const float d = dot(Pq - P, N); return absf(d) <= tol; }
+FLX_HD bool rp_same_facing(f3 Nq, f3 N, float normal_cos) { return dot(Nq, N) >= normal_cos; }
 
 /* The new pixel from the current G-buffer record (g0, g1).  prevG0(j) / prevG1(j) / hist(j) / mom(j) -> rp4 of previous-view pixel j (flat index);
  * mom is only called when `moments`.  Returns the bit mask of the counted taps (tap order above; 0: zeros were written). */
@@ -123,10 +126,9 @@ FLX_HD uint32_t rp_pixel(const rp_view &vw, const rp_params &rp, rp4 g0, rp4 g1,
         if (!rp_is_hit(q0)) continue;
         const rp4 hj = hist(j);
         if (!(hj.w > 0.0f) || !rp_finite(hj.w) || !rp_finite(hj.x) || !rp_finite(hj.y) || !rp_finite(hj.z)) continue;
-        const float d = dot(mk3(q0.x, q0.y, q0.z) - P, N);
-        if (!(absf(d) <= tol)) continue;
+        if (!rp_same_plane(mk3(q0.x, q0.y, q0.z), P, N, tol)) continue;
         const rp4 q1 = prevG1(j);
-        if (!(dot(mk3(q1.x, q1.y, q1.z), N) >= rp.normal_cos)) continue;
+        if (!rp_same_facing(mk3(q1.x, q1.y, q1.z), N, rp.normal_cos)) continue;
         b[k] = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
         h[k] = hj; idx[k] = j;
         S = S + b[k];

@@ -27,6 +27,7 @@ SYMBOLS = ["flx_create", "flx_destroy", "flx_last_error", "flx_upload_scene", "f
            "flx_update_triangles", "flx_update_triangles_subset", "flx_tree_read", "flx_tree_cost",
            "flx_objects_define", "flx_objects_pose", "flx_objects_read", "flx_gbuffer_objects_read", "flx_gbuffer_objects_write",
            "flx_gbuffer_bary_read", "flx_gbuffer_bary_write", "flx_deform_read",
+           "flx_history_mark", "flx_history_rectify", "flx_history_mark_read",
            "flx_mesh_lights_read", "flx_mesh_lights_sample"]
 
 KERNELS = {"reset": 0, "raygen": 1, "extend": 2, "shadow": 3, "logic": 4, "materials": 5, "postprocess": 6, "trace_span": 7, "logic_fused": 8}
@@ -35,7 +36,8 @@ K_GBUFFER, K_REPROJECT = 10, 11      # FLX_K_GBUFFER / FLX_K_REPROJECT: profile 
 K_REFIT = 12                         # FLX_K_REFIT: the kernels of update_triangles, likewise
 K_TREE_COST = 13                     # FLX_K_TREE_COST: the kernels of tree_cost, likewise
 K_SNAPSHOT, K_MOVED_FLAGS = 14, 15   # FLX_K_SNAPSHOT / FLX_K_MOVED_FLAGS: option "deform_history"'s snapshot and flag passes, likewise
-NO_OBJECT = 0xFFFFFFFF               # FLX_NO_OBJECT: a triangle that belongs to no object (objects_define)
+K_RECTIFY = 16                       # FLX_K_RECTIFY: the two kernels of history_rectify, likewise
+NO_OBJECT = 0xFFFFFFFF            # FLX_NO_OBJECT: a triangle that belongs to no object (objects_define)
 
 
 def tree_cost_value(sums4):
@@ -72,6 +74,16 @@ class ReprojectParams(C.Structure):
 
 # the library's defaults (FLX_RP_DEFAULT_*, csrc/flx_reproject.h)
 REPROJECT_DEFAULTS = dict(max_history=32.0, plane_tolerance_px=2.0, normal_cos=0.9, min_weight=0.01)
+
+
+class RectifyParams(C.Structure):
+    """flx_rectify_params (include/fluctus_hip.h)"""
+    _fields_ = [("radius", C.c_int), ("gamma", C.c_float), ("sensitivity", C.c_float), ("lum_floor", C.c_float), ("min_pixels", C.c_int),
+                ("plane_tolerance_px", C.c_float), ("normal_cos", C.c_float)]
+
+
+# the library's defaults (FLX_RC_DEFAULT_*, csrc/flx_rectify.h; DESIGN.md 4.3.7)
+RECTIFY_DEFAULTS = dict(radius=3, gamma=3.0, sensitivity=2.0, lum_floor=0.01, min_pixels=8, plane_tolerance_px=2.0, normal_cos=0.9)
 
 
 class AdaptiveParams(C.Structure):
@@ -409,6 +421,35 @@ class HipContext:
         P = dict(REPROJECT_DEFAULTS, **params)
         rp = ReprojectParams(float(P["max_history"]), float(P["plane_tolerance_px"]), float(P["normal_cos"]), float(P["min_weight"]))
         self._chk(self.L.flx_reproject(self.h, C.byref(rp)))
+
+    # history rectification (include/fluctus_hip.h)
+    def history_mark(self):
+        """flx_history_mark (asynchronous): copies of which = 0 (and 7) as the mark the next history_rectify compares the new samples with"""
+        self._chk(self.L.flx_history_mark(self.h))
+
+    def history_rectify(self, **params):
+        """flx_history_rectify (asynchronous): radius, gamma, sensitivity, lum_floor, min_pixels, plane_tolerance_px, normal_cos; missing ones take
+        the defaults, no keyword at all passes NULL.  Takes the share of the marked history the samples since the mark contradict out of
+        which = 0 (and 7) and out of the mark."""
+        unknown = set(params) - set(RECTIFY_DEFAULTS)
+        if unknown:
+            raise TypeError(f"history_rectify: unknown parameters {sorted(unknown)}")
+        if not params:
+            self._chk(self.L.flx_history_rectify(self.h, None))
+            return
+        P = dict(RECTIFY_DEFAULTS, **params)
+        rp = RectifyParams(int(P["radius"]), float(P["gamma"]), float(P["sensitivity"]), float(P["lum_floor"]), int(P["min_pixels"]),
+                           float(P["plane_tolerance_px"]), float(P["normal_cos"]))
+        self._chk(self.L.flx_history_rectify(self.h, C.byref(rp)))
+
+    def history_mark_read(self, moments=False):
+        """test hook (blocking) -> (mark (pixels, 4), mark moments (pixels, 4) or None, lambda (pixels,)) of the last history_rectify since the
+        mark (zeros before one)"""
+        n = self.local_pixels()
+        mark, lam = np.zeros((n, 4), np.float32), np.zeros(n, np.float32)
+        mom = np.zeros((n, 4), np.float32) if moments else None
+        self._chk(self.L.flx_history_mark_read(self.h, _p(mark), _p(mom), _p(lam)))
+        return mark, mom, lam
 
     def gbuffer_read(self, slot=0):
         """test hook -> ((pixels, 8) float32: G0 = (P, hit index bits), G1 = (Ng, t); the slot's camera as a wire.CAMERA record)"""

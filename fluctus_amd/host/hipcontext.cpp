@@ -19,6 +19,7 @@ struct HipContext::Api {
     FN(flx_denoise) FN(flx_denoise_variance_guided) FN(flx_gbuffer) FN(flx_history_capture) FN(flx_reproject)
     FN(flx_mk_adaptive_update) FN(flx_mk_adaptive_clear) FN(flx_update_triangles) FN(flx_update_triangles_subset) FN(flx_tree_cost) FN(flx_tree_read)
     FN(flx_objects_define) FN(flx_objects_pose) FN(flx_mesh_lights_read)
+    FN(flx_history_mark) FN(flx_history_rectify) FN(flx_history_mark_read)
 #undef FN
 };
 
@@ -49,6 +50,7 @@ HipContext::HipContext(int device, uint32_t numTasks, const std::string &libPath
     BIND(flx_denoise) BIND(flx_denoise_variance_guided) BIND(flx_gbuffer) BIND(flx_history_capture) BIND(flx_reproject)
     BIND(flx_mk_adaptive_update) BIND(flx_mk_adaptive_clear) BIND(flx_update_triangles) BIND(flx_update_triangles_subset) BIND(flx_tree_cost) BIND(flx_tree_read)
     BIND(flx_objects_define) BIND(flx_objects_pose) BIND(flx_mesh_lights_read)
+    BIND(flx_history_mark) BIND(flx_history_rectify) BIND(flx_history_mark_read)
 #undef BIND
     if (api->flx_create(device, numTasks, &ctx) != 0)
         throw std::runtime_error(std::string("HipContext: ") + api->flx_last_error(nullptr));
@@ -188,6 +190,21 @@ void HipContext::reproject(const ReprojectParams &p)
 {
     const flx_reproject_params rp = {p.maxHistory, p.planeTolerancePx, p.normalCos, p.minWeight};
     check(api->flx_reproject(ctx, &rp), "reproject");
+}
+void HipContext::historyMark() { check(api->flx_history_mark(ctx), "historyMark"); }
+void HipContext::historyRectify() { check(api->flx_history_rectify(ctx, nullptr), "historyRectify"); }
+void HipContext::historyRectify(const RectifyParams &p)
+{
+    const flx_rectify_params rp = {p.radius, p.gamma, p.sensitivity, p.lumFloor, p.minPixels, p.planeTolerancePx, p.normalCos};
+    check(api->flx_history_rectify(ctx, &rp), "historyRectify");
+}
+double HipContext::markedSamples()
+{
+    std::vector<float> m((size_t)localPixels() * 4);
+    check(api->flx_history_mark_read(ctx, m.data(), nullptr, nullptr), "markedSamples");
+    double n = 0.0;
+    for (size_t i = 3; i < m.size(); i += 4) n += m[i];
+    return n;
 }
 void HipContext::finishQueue() { check(api->flx_finish(ctx), "finish"); foldMkStats(); }
 void HipContext::updatePixelIndex(uint32_t n, uint32_t nnew) { check(api->flx_pixel_index_update(ctx, n, nnew), "updatePixelIndex"); }

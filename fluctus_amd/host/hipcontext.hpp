@@ -91,6 +91,14 @@ public:
     void gbuffer();
     void historyCapture();
     void reproject(const ReprojectParams &params);
+    // history rectification (flx_history_mark / flx_history_rectify): the copy of the accumulation the next rectify compares the
+    // new samples with; the share of it that they contradict taken out (no argument: the library's defaults).  Single-GPU, asynchronous.
+    // markedSamples: the sum of the mark's sample counts (blocking; throws without a mark) -- what share of a history a rectify kept.
+    struct RectifyParams { int radius = 3; float gamma = 3.0f, sensitivity = 2.0f, lumFloor = 0.01f; int minPixels = 8; float planeTolerancePx = 2.0f, normalCos = 0.9f; };
+    void historyMark();
+    void historyRectify();
+    void historyRectify(const RectifyParams &params);
+    double markedSamples();
     void finishQueue();
     void updatePixelIndex(uint32_t numPixels, uint32_t numNewPaths);
     void resetPixelIndex();

@@ -579,6 +579,15 @@ int fh_tracer_get_motion_reprojection(void *t) { return ((Tracer *)t)->getMotion
 int fh_tracer_set_deform_reprojection(void *t, int on) { FH_TRY ((Tracer *)t)->setDeformReprojection(on != 0); FH_CATCH }
 int fh_tracer_get_deform_reprojection(void *t) { return ((Tracer *)t)->getDeformReprojection() ? 1 : 0; }
 int fh_tracer_set_max_history(void *t, float n) { FH_TRY ((Tracer *)t)->setMaxHistory(n); FH_CATCH }
+int fh_tracer_set_history_rectification(void *t, int on) { FH_TRY ((Tracer *)t)->setHistoryRectification(on != 0); FH_CATCH }
+int fh_tracer_get_history_rectification(void *t) { return ((Tracer *)t)->getHistoryRectification() ? 1 : 0; }
+int fh_tracer_set_rectify_delay(void *t, int frames) { FH_TRY ((Tracer *)t)->setRectifyDelay(frames); FH_CATCH }
+int fh_tracer_get_rectify_delay(void *t) { return (int)((Tracer *)t)->getRectifyDelay(); }
+// measure != 0: every rectify of update() also reads the mark before and after (blocking).  out_share: the last such share (NaN before one)
+int fh_tracer_rectify_info(void *t, int measure, double *out_share, uint32_t *out_count)
+{
+    FH_TRY Tracer *tr = (Tracer *)t; tr->measureRetained = measure != 0; if (out_share) *out_share = tr->lastRetainedShare(); if (out_count) *out_count = tr->rectifyCount(); FH_CATCH
+}
 int fh_tracer_set_mesh_lights(void *t, int on) { FH_TRY ((Tracer *)t)->setMeshLights(on != 0); FH_CATCH }
 int fh_tracer_set_mesh_lights_wavefront(void *t, int on) { FH_TRY ((Tracer *)t)->setMeshLightsWavefront(on != 0); FH_CATCH }
 int fh_tracer_get_mesh_lights_wavefront(void *t) { return ((Tracer *)t)->getMeshLightsWavefront() ? 1 : 0; }

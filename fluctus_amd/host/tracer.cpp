@@ -23,7 +23,7 @@ Tracer::Tracer(int width, int height, int device, uint32_t numTasks)
     initAreaLight();
     scene.reset(new Scene());
     clctx.reset(new HipContext(device, numTasks));
-    lastRatio = std::nan("");
+    lastRatio = std::nan(""); retainedShare = std::nan("");
 }
 
 Tracer::Tracer(int width, int height, const std::vector<int> &devices, uint32_t numTasks) : Tracer(width, height, devices.empty() ? 0 : devices[0], numTasks)
@@ -379,6 +379,19 @@ void Tracer::setTemporalReprojection(bool on)
     dropHistory(); temporalFrames = 0;
     if (!on && motionOn) setMotionReprojection(false);
     if (!on && deformOn) setDeformReprojection(false);
+    if (!on && rectifyOn) setHistoryRectification(false);
+}
+void Tracer::setHistoryRectification(bool on)
+{
+    if (on && !peers.empty()) throw std::runtime_error("setHistoryRectification: temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
+    if (on && !temporalOn) throw std::runtime_error("setHistoryRectification: needs setTemporalReprojection(true)");
+    rectifyOn = on;
+    markPending = false;
+}
+void Tracer::setRectifyDelay(int frames)
+{
+    if (frames < 0) throw std::runtime_error("setRectifyDelay: the delay is a number of frames >= 1 (0: the default, 2 maxBounces + 2)");
+    rectifyDelay = (uint32_t)frames;
 }
 void Tracer::setMotionReprojection(bool on)
 {
@@ -411,6 +424,7 @@ bool Tracer::onlyCameraChanged(bool posed) const
 {
     RenderParams now = params;
     if (posed) now.worldRadius = gbParams.worldRadius;
+    if (rectifyOn) now.areaLight = gbParams.areaLight;       // history rectification sheds what a changed area light contradicts
     const char *a = (const char *)&now, *b = (const char *)&gbParams;
     return std::memcmp(a, b, offsetof(RenderParams, camera)) == 0 &&
            std::memcmp(a + offsetof(RenderParams, width), b + offsetof(RenderParams, width), sizeof(RenderParams) - offsetof(RenderParams, width)) == 0;
@@ -598,6 +612,8 @@ void Tracer::update()
         } else dropHistory();                                            // the update was consumed without a G-buffer: the slot is another camera's
     }
     if (iteration == 0 && !reprojectNow) temporalFrames = 0;             // the accumulation restarts from nothing
+    if (iteration == 0) markPending = false;                             // the reset below drops the device's mark
+    const bool markNow = rectifyOn && reprojectNow && iteration == 0 && useWavefront;
     if (!useWavefront) {
         if (!peers.empty()) throw std::runtime_error("update: the microkernel integrator is single-GPU");
         updateMicrokernel(); return;
@@ -632,6 +648,14 @@ void Tracer::update()
         }
     }
     if (iteration == 0) { params.maxBounces = maxBounces; for (auto *c : R) c->updateParams(params); }
+    // history rectification: the frame that reprojected marks what it has (history + preview); the frame that completes the delay compares
+    if (markNow) { clctx->historyMark(); markPending = true; }
+    else if (rectifyOn && markPending && framesSinceGbuffer + 1 >= getRectifyDelay()) {
+        const double before = measureRetained ? clctx->markedSamples() : 0.0;
+        clctx->historyRectify();
+        if (measureRetained) retainedShare = before > 0.0 ? clctx->markedSamples() / before : std::nan("");
+        markPending = false; rectifies++;
+    }
     for (auto *c : R) c->enqueuePostprocessKernel(params);
     const uint32_t sched = temporalOn ? temporalFrames : iteration;      // temporal reprojection: frames since the last discarded history
     if (useDenoiser && denoiserStrength > 0.0f && sched >= 10 && sched % 10 == 0) denoiseStep();   // :310-328 (single-GPU: setDenoiserStrength)

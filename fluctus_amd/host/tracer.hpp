@@ -132,6 +132,23 @@ public:
     void setDeformReprojection(bool on);
     bool getDeformReprojection() const { return deformOn; }
     float getMaxHistory() const { return maxHistory; }
+    // History rectification, default off; needs setTemporalReprojection(true) and throws without it or on a multi-rank Tracer.
+    // On: a frame that reprojects runs exactly as without the switch, preview passes included, and ends on flx_history_mark (the preview's
+    // samples count as history, as they effectively do anyway); the frame at whose end `delay` frames have been rendered since that G-buffer
+    // runs flx_history_rectify once, unless a newer reprojection has replaced the mark by then -- under continuous motion it never fires, it
+    // fires once the view rests.  The delay defaults to 2 maxBounces + 2 frames: the wavefront integrator splats a path when it ENDS, so for the
+    // first ~maxBounces frames after a reset the samples over-represent short paths, which would read as a change everywhere.
+    // And a moved, resized or re-coloured AREA LIGHT no longer discards the accumulation: it takes the reprojection route like a camera move
+    // (capture, G-buffer, reset, reprojection, mark) and the rectification sheds what the new light contradicts.  Every other parameter change,
+    // setEnvMap included, discards the history as ever.  lastRetainedShare: the mark's sample count after the last rectify over the one before
+    // it (NaN before one; two blocking reads per rectify while measureRetained is set).
+    void setHistoryRectification(bool on);
+    bool getHistoryRectification() const { return rectifyOn; }
+    void setRectifyDelay(int frames);                                             // >= 1; 0 = the default, 2 maxBounces + 2
+    uint32_t getRectifyDelay() const { return rectifyDelay ? rectifyDelay : 2 * params.maxBounces + 2; }
+    bool measureRetained = false;
+    double lastRetainedShare() const { return retainedShare; }
+    uint32_t rectifyCount() const { return rectifies; }                           // how many times update() has run flx_history_rectify
     // Emissive triangles as lights, default off: only the microkernel integrator sees them, so while this is on update() takes
     // its microkernel branch (as renderSingle forces it) and toggleRenderer() to the wavefront loop THROWS -- lamps never go silently dark.
     // Single-GPU like that integrator: throws on a multi-rank Tracer.  meshLightCount: the lights listed on the device (throws while off).
@@ -213,12 +230,15 @@ private:
     // wherever parameters reach the device without flx_gbuffer (dropHistory)
     bool haveGbuffer = false;
     RenderParams gbParams {};
-    void dropHistory() { haveGbuffer = false; poseHistory = false; }
+    void dropHistory() { haveGbuffer = false; poseHistory = false; markPending = false; }
     bool historyExists(bool posed) const;                                         // update()'s conditions for a history worth capturing, shared with poseObjects
     bool onlyCameraChanged(bool posed = false) const;                             // params against gbParams, the camera and the post-process aside (posed: and worldRadius, which a pose re-derives)
     bool motionOn = false, deformOn = false;
     bool keepHistoryAcrossMove(bool on, bool &captured);                          // capture before the ranks move (at most once per frame)
     void movedKeepingHistory(bool keep, uint32_t topologiesBefore);               // ... and re-arm update() after afterMove()
+    bool rectifyOn = false, markPending = false;                                  // markPending: a frame has marked and its rectify has not run yet
+    uint32_t rectifyDelay = 0, rectifies = 0;
+    double retainedShare = 0.0;                                                   // (set to NaN by the constructor)
     bool poseHistory = false;                                                     // poseObjects has captured the history of this frame: the next update() reprojects it
     uint32_t gbWidth = 0, gbHeight = 0;                                           // ... traced at this size
     uint32_t framesSinceGbuffer = 0;                                              // > 0: there is an accumulation worth capturing

@@ -238,6 +238,31 @@ class Tracer:
         """Tracer::setMaxHistory: the sample count a reprojected pixel may keep (flx_reproject's max_history, >= 1; default 32)"""
         host._chk(self.L.fh_tracer_set_max_history(self.h, C.c_float(float(n))))
 
+    def set_history_rectification(self, on):
+        """Tracer::setHistoryRectification (default off; needs set_temporal_reprojection(True)): a frame that reprojects ends on a mark, and once
+        rectify_delay frames have been rendered since, the share of the marked history that the new samples contradict is taken out
+        (DESIGN.md 4.3.7).  While on, a moved, resized or re-coloured area light keeps the accumulation the same way.  Single-GPU."""
+        host._chk(self.L.fh_tracer_set_history_rectification(self.h, int(bool(on))))
+
+    @property
+    def history_rectification(self):
+        return bool(self.L.fh_tracer_get_history_rectification(self.h))
+
+    def set_rectify_delay(self, frames):
+        """Tracer::setRectifyDelay: frames between the G-buffer of a reprojecting frame and the rectify (>= 1; 0: the default, 2 maxBounces + 2)"""
+        host._chk(self.L.fh_tracer_set_rectify_delay(self.h, int(frames)))
+
+    @property
+    def rectify_delay(self):
+        return int(self.L.fh_tracer_get_rectify_delay(self.h))
+
+    def rectify_info(self, measure=True):
+        """-> (the share of the marked sample count the last rectify of update() kept, NaN before one measured; how many rectifies update() has
+        run).  measure: from now on every rectify reads the mark before and after (two blocking reads)."""
+        share, count = C.c_double(float("nan")), C.c_uint32(0)
+        host._chk(self.L.fh_tracer_rectify_info(self.h, int(bool(measure)), C.byref(share), C.byref(count)))
+        return share.value, count.value
+
     def set_option(self, name, value):
         """HipContext::setOption -> flx_set_option (e.g. "extend_tree", 2 for the reference's bit-exact visit order)."""
         host._chk(self.L.fh_tracer_set_option(self.h, name.encode(), int(value)))

@@ -266,7 +266,8 @@ int flx_gbuffer_write(flx_ctx *ctx, int slot, const float *in_8_floats_per_pixel
  * cofactors, D = X_capture X_now^-1 (one 3 x 4 matrix per object, inverse and product in float64, rounded once), and a tap showing another
  * object is refused when either of the two moved.  An object posed for the first time since its definition has no known pose at the capture
  * (the uploaded triangles need not be the rest pose): its pixels get no history.  Per-triangle motion is not followed.  A moved object changes
- * shadows and reflections on surfaces that did not move: their history is stale and decays only through max_history.
+ * shadows and reflections on surfaces that did not move: their history is stale and decays only through max_history -- unless
+ * flx_history_mark / flx_history_rectify (below) take it out.
  * The object of every triangle, the two planes and the per-object table are allocated by the first flx_gbuffer or flx_objects_pose that finds
  * the option on and objects defined; turning the option off invalidates the planes.
  * flx_gbuffer_objects_read / flx_gbuffer_objects_write: test hooks beside flx_gbuffer_read / _write, one uint32 per pixel, blocking.  The write
@@ -295,7 +296,8 @@ int flx_gbuffer_objects_write(flx_ctx *ctx, int slot, const uint32_t *in_1_uint3
  * the positions at the capture, N' = the old triangle's unit normal on the side N is on, and a tap is refused when exactly one of the tap's and
  * the pixel's triangles moved.  With nothing moved every pixel equals the plain call bit for bit.  A triangle that was degenerate at the capture
  * gets no history.  Two different moved surfaces sliding coplanar over each other still share taps.  Stale shadows and reflections on surfaces that
- * did not move decay only through max_history, as under "motion_history".  After a move, a slot without its plane is refused with a message.
+ * did not move decay only through max_history, as under "motion_history" (or are taken out by flx_history_rectify, below).  After a move, a slot
+ * without its plane is refused with a message.
  * "deform_history" and "motion_history" refuse each other: this option follows flx_objects_pose as well.
  * The planes are allocated by the first flx_gbuffer / flx_gbuffer_write that finds the option on, the snapshot (48 B per triangle) and the flags
  * (1 B per triangle) by the first move that needs them; they stay with the scene.
@@ -307,6 +309,34 @@ int flx_gbuffer_objects_write(flx_ctx *ctx, int slot, const uint32_t *in_1_uint3
 int flx_gbuffer_bary_read(flx_ctx *ctx, int slot, float *out_2_floats_per_pixel);
 int flx_gbuffer_bary_write(flx_ctx *ctx, int slot, const float *in_2_floats_per_pixel);
 int flx_deform_read(flx_ctx *ctx, float *out_9_floats_per_triangle, uint8_t *out_1_byte_per_triangle);
+/* ---- history rectification (csrc/flx_rectify.h): shed stale history where new samples disagree.  Reprojection knows where a
+ * surface point WAS, not that its radiance CHANGED (a moved object's shadow on a floor that did not move, a dimmed lamp).  Opt-in; the sequence is
+ *     ... flx_gbuffer; flx_history_capture; [move / flx_set_params]; flx_gbuffer; flx_wf_reset or flx_mk_reset; flx_reproject;
+ *     flx_history_mark; ... sample passes ...; flx_history_rectify [; ... more passes ...; flx_history_rectify ...]
+ * A mark works without any reprojection as well: flx_gbuffer; flx_history_mark; change a light WITHOUT resetting; render; flx_history_rectify.
+ * All three calls need an unpartitioned context, flush deferred and fused launches first, touch no path state, queue or counter, and a refused
+ * call changes nothing.
+ * flx_history_mark: on the stream, copies of the accumulation (which = 0) and, with option "moments" on, of the moments (which = 7) into the
+ * mark.  Needs a traced current G-buffer slot of the current size.  The buffers (48 B per pixel, 64 B with moments) are allocated by the first
+ * call and freed with the framebuffers.  Asynchronous.  The mark is dropped by flx_wf_reset, flx_mk_reset, a change of the image size,
+ * flx_set_partition, flx_history_capture, flx_upload_scene and every call that un-traces the current slot (any move of triangles);
+ * flx_write_pixels keeps it.
+ * flx_history_rectify: per pixel with a surface, compares the mean luminance of the samples added since the mark with the marked history's over
+ * the (2 radius + 1)^2 window of pixels on the same surface (flx_reproject's plane and normal tests under the current slot's camera), pooling
+ * the PER-PIXEL differences so that static texture cancels, and takes the share lambda = min(1, sensitivity max(0, |d| - gamma se) / (max of
+ * the two means + lum_floor)) of the marked history out of which = 0 (and of which = 7 when "moments" is on now and was on at the mark):
+ * A' = A - lambda S, and the mark becomes S (1 - lambda), so A' - S' stays the new samples and the call may be repeated as evidence grows.  Fewer
+ * than min_pixels usable pixels in the window, a pixel that misses the scene, a non-finite value anywhere: lambda = 0, and a pixel whose lambda
+ * is 0 is not written.  Luminance only: a pure change of hue is not seen; curved surfaces count fewer pixels and keep more history.  Needs a
+ * live mark and the current slot traced at the mark's size.  params NULL = the defaults {3, 3, 2, 0.01, 8, 2, 0.9}; fails unless radius is in
+ * 1..4, gamma finite and >= 0, sensitivity finite and > 0, lum_floor finite and >= 0, min_pixels in 1..(2 radius + 1)^2, plane_tolerance_px > 0
+ * and normal_cos in [-1, 1].  Asynchronous, timed under FLX_K_RECTIFY.
+ * flx_history_mark_read: test hook, blocking: the mark (4 floats per pixel), its moments (refused when the mark has none) and lambda (1 float
+ * per pixel) as the last flx_history_rectify since the mark left it, zeros before one.  Any output may be NULL. */
+typedef struct { int radius; float gamma, sensitivity, lum_floor; int min_pixels; float plane_tolerance_px, normal_cos; } flx_rectify_params;
+int flx_history_mark(flx_ctx *ctx);
+int flx_history_rectify(flx_ctx *ctx, const flx_rectify_params *params);
+int flx_history_mark_read(flx_ctx *ctx, float *out_mark_4_floats_per_pixel, float *out_mark_moments_4_floats_per_pixel, float *out_lambda_1_float_per_pixel);
 
 /* ---- microkernel integrator (the reference's second integrator).  One path per pixel (needs
  * num_tasks >= width*height to cover the image), `phase` state machine, exactly one sample per pixel per pass.
@@ -393,7 +423,8 @@ enum { FLX_K_RESET = 0, FLX_K_RAYGEN = 1, FLX_K_EXTEND = 2, FLX_K_SHADOW = 3, FL
        FLX_K_TREE_COST = 13,   /* the kernels of one flx_tree_cost */
        FLX_K_SNAPSHOT = 14,    /* option "deform_history": the copy of the positions a move of triangles makes after a capture */
        FLX_K_MOVED_FLAGS = 15, /* ... and the moved-flag pass as flx_deform_read launches it (inside flx_reproject it is part of FLX_K_REPROJECT) */
-       FLX_K_COUNT = 16 };
+       FLX_K_RECTIFY = 16,     /* the two kernels of one flx_history_rectify */
+       FLX_K_COUNT = 17 };
 /* on: 0 off | 1 time every kernel | 2 time only the two trace kernels (+ their span), as the reference does | 3 only the
  * extension kernel | 4 the three kernels bench.py prices against a roof: extension, logic (the fused pass incl. its queue scan + scatter), shadow.
  * Each event pair costs a few microseconds of stream time, which shows at ~11 launches per 0.7 ms
