@@ -109,7 +109,7 @@ void Tracer::init(int width, int height, const std::string &sceneFile)
     // (the reference deletes the hierarchy here, :72-73; it stays for updateGeometry's refit: 48 bytes per node and the index list)
     paramsUpdatePending = true;
     iteration = 0;
-    haveGbuffer = false;                                     // a new scene: no history
+    history.dropped();                                       // a new scene: no history
 }
 
 // The scene's triangles move (an animated mesh, a dragged object): same count, same materials.  The host tree and both device trees are refitted
@@ -125,25 +125,33 @@ void Tracer::geometryChanged()
 {
     params.worldRadius = bvh->worldRadius();
     paramsUpdatePending = true;
-    dropHistory();                                           // the G-buffer and the accumulation belong to the old geometry
+    history.dropped();                                       // the G-buffer and the accumulation belong to the old geometry
     iteration = 0;
+}
+// What every move of triangles runs, in this order (reprojection across it: DESIGN.md 4.3.4, 4.3.6; history_state.hpp).  keepSwitch: the switch
+// under which this kind of move keeps the history.  moveRanks: the device call on every rank; refused (bad input), it throws and everything is
+// still the old geometry's.  moveHost: the host tree and the scene's copy follow.
+template <class MoveRanks, class MoveHost> void Tracer::moveTriangles(bool keepSwitch, MoveRanks moveRanks, MoveHost moveHost)
+{
+    if (rebuildMode != RebuildOff) adoptFinishedRebuild();
+    const HistoryState::MovePlan plan = history.beforeMove(keepSwitch, params, useWavefront);
+    if (plan.captureNow) clctx->historyCapture();            // before the ranks move, so that the device keeps the history
+    try {
+        moveRanks();
+    } catch (...) {
+        if (plan.captureNow) paramsUpdatePending = true;     // the capture has handed the current slot over: the next update() traces it again and reprojects (nothing moved)
+        throw;
+    }
+    moveHost();
+    const uint32_t topologies = rebuilds;
+    afterMove();                                             // (its geometryChanged drops the host's view of the history ...)
+    history.afterMove(plan.keep, rebuilds != topologies);    // (... which the device still has, unless a rebuild in there uploaded a topology)
 }
 void Tracer::updateGeometry(const std::vector<flx_triangle> &tris)
 {
     if (!scene || !bvh) throw std::runtime_error("Tracer::updateGeometry: no scene (init first)");
     if (tris.size() != scene->getTriangles().size()) throw std::runtime_error("Tracer::updateGeometry: the triangle count differs from the scene's");
-    if (rebuildMode != RebuildOff) adoptFinishedRebuild();
-    bool captured = false;
-    const bool keep = keepHistoryAcrossMove(deformOn, captured);
-    try {
-        refitAll(tris);
-    } catch (...) {
-        if (captured) paramsUpdatePending = true;            // the capture has handed the current slot over: the next update() traces it again and reprojects (nothing moved)
-        throw;
-    }
-    const uint32_t topologies = rebuilds;
-    afterMove();
-    movedKeepingHistory(keep, topologies);
+    moveTriangles(history.deform(), [&] { refitAll(tris); }, [] {});          // (refitAll moves the host copy behind the ranks)
 }
 // ... a subset of them (flx_update_triangles_subset, BVH::refitSubset): only the boxes above the listed triangles are refitted.
 // Takes part in the rebuild policy exactly as the full overload does.
@@ -151,38 +159,14 @@ void Tracer::updateGeometry(const std::vector<uint32_t> &indices, const std::vec
 {
     if (!scene || !bvh) throw std::runtime_error("Tracer::updateGeometry: no scene (init first)");
     if (indices.size() != tris.size()) throw std::runtime_error("Tracer::updateGeometry: as many triangles as indices");
-    if (rebuildMode != RebuildOff) adoptFinishedRebuild();
-    bool captured = false;
-    const bool keep = keepHistoryAcrossMove(deformOn, captured);
-    try {
-        for (auto *c : ranks()) c->updateTriangles(indices, tris);   // refused (a bad index list or triangle): throws, and everything is still the old geometry's
-    } catch (...) {
-        if (captured) paramsUpdatePending = true;
-        throw;
-    }
-    std::vector<flx_triangle> all = scene->getTriangles();
-    for (size_t k = 0; k < indices.size(); k++) all[indices[k]] = tris[k];      // (the device has checked the list: ascending, in range)
-    bvh->refitSubset(all, indices);
-    scene->getTriangles().swap(all);
-    const uint32_t topologies = rebuilds;
-    afterMove();
-    movedKeepingHistory(keep, topologies);
-}
-// Reprojection across a move of triangles, shared by poseObjects and both updateGeometry overloads.  `on`: the switch
-// under which this kind of move keeps the history.  With a history by update()'s own conditions, capture it before the ranks are moved -- at
-// most once per frame -- so that the device keeps it.  captured: this call made the capture (a refused move must then re-arm update()).
-bool Tracer::keepHistoryAcrossMove(bool on, bool &captured)
-{
-    const bool keep = on && historyExists(true);
-    captured = keep && !poseHistory;
-    if (captured) { clctx->historyCapture(); poseHistory = true; }
-    return keep;
-}
-// ... and after afterMove(), whose geometryChanged dropped the host's view of the history: the device still has it, unless a rebuild inside
-// afterMove re-uploaded the topology (the device dropped its history with the upload)
-void Tracer::movedKeepingHistory(bool keep, uint32_t topologiesBefore)
-{
-    if (keep && rebuilds == topologiesBefore) { haveGbuffer = true; poseHistory = true; }
+    moveTriangles(history.deform(),
+                  [&] { for (auto *c : ranks()) c->updateTriangles(indices, tris); },
+                  [&] {
+                      std::vector<flx_triangle> all = scene->getTriangles();
+                      for (size_t k = 0; k < indices.size(); k++) all[indices[k]] = tris[k];      // (the device has checked the list: ascending, in range)
+                      bvh->refitSubset(all, indices);
+                      scene->getTriangles().swap(all);
+                  });
 }
 // Objects moved by their transforms: updateGeometry(indices, tris) with the triangles made where they are needed -- on every rank
 // by flx_objects_pose, here by the same csrc/flx_pose.h function for the host tree and the scene's copy.
@@ -202,7 +186,7 @@ void Tracer::defineObjects(const std::vector<uint32_t> &objectOfTriangle, uint32
     }
     for (auto *c : ranks()) c->defineObjects(nobjects ? tris : std::vector<flx_triangle>(), nobjects ? objectOfTriangle : std::vector<uint32_t>(), nobjects);
     nObjects = nobjects; objMemberTri.swap(tri); objMemberObj.swap(obj); objRest.swap(rest);
-    if (motionOn) dropHistory();                             // the G-buffer's object plane names the earlier definition's objects (the device has dropped its history too)
+    history.objectsDefined();
 }
 void Tracer::defineObjects()
 {
@@ -221,32 +205,22 @@ void Tracer::poseObjects(const std::vector<uint32_t> &ids, const std::vector<flo
 {
     if (!scene || !bvh) throw std::runtime_error("Tracer::poseObjects: no scene (init first)");
     if (!nObjects) throw std::runtime_error("Tracer::poseObjects: no objects are defined (defineObjects)");
-    if (rebuildMode != RebuildOff) adoptFinishedRebuild();
-    // motion-aware reprojection: with a history by update()'s own conditions, capture it before the ranks are posed -- at most once
-    // per frame -- so that flx_objects_pose keeps it
-    bool capture = false;
-    const bool keep = keepHistoryAcrossMove(motionOn || deformOn, capture);      // (under per-vertex reprojection a pose is a move of triangles like any other)
-    try {
-        for (auto *c : ranks()) c->poseObjects(ids, xforms12);    // refused (a bad list or matrix, a vertex out of range): throws, and everything is still the old geometry's
-    } catch (...) {
-        if (capture) paramsUpdatePending = true;             // the capture has handed the current slot over: the next update() traces it again and reprojects (nothing moved)
-        throw;
-    }
-    std::vector<uint32_t> slot(nObjects, FLX_NO_OBJECT);     // (the device has checked the list: ascending, in range)
-    for (size_t k = 0; k < ids.size(); k++) slot[ids[k]] = (uint32_t)k;
-    std::vector<flx_triangle> all = scene->getTriangles();
-    std::vector<uint32_t> indices;
-    for (size_t k = 0; k < objMemberTri.size(); k++) {
-        const uint32_t s = slot[objMemberObj[k]];
-        if (s == FLX_NO_OBJECT) continue;
-        flx::ps_pose_triangles(xforms12.data() + 12 * (size_t)s, &objRest[k], &all[objMemberTri[k]], 1);
-        indices.push_back(objMemberTri[k]);
-    }
-    bvh->refitSubset(all, indices);
-    scene->getTriangles().swap(all);
-    const uint32_t topologies = rebuilds;
-    afterMove();
-    movedKeepingHistory(keep, topologies);                   // (a rebuild inside afterMove re-defined the objects: the device dropped the history)
+    moveTriangles(history.motion() || history.deform(),      // (under per-vertex reprojection a pose is a move of triangles like any other)
+                  [&] { for (auto *c : ranks()) c->poseObjects(ids, xforms12); },       // refused: a bad list or matrix, a vertex out of range
+                  [&] {
+                      std::vector<uint32_t> slot(nObjects, FLX_NO_OBJECT);               // (the device has checked the list: ascending, in range)
+                      for (size_t k = 0; k < ids.size(); k++) slot[ids[k]] = (uint32_t)k;
+                      std::vector<flx_triangle> all = scene->getTriangles();
+                      std::vector<uint32_t> indices;
+                      for (size_t k = 0; k < objMemberTri.size(); k++) {
+                          const uint32_t s = slot[objMemberObj[k]];
+                          if (s == FLX_NO_OBJECT) continue;
+                          flx::ps_pose_triangles(xforms12.data() + 12 * (size_t)s, &objRest[k], &all[objMemberTri[k]], 1);
+                          indices.push_back(objMemberTri[k]);
+                      }
+                      bvh->refitSubset(all, indices);
+                      scene->getTriangles().swap(all);
+                  });
 }
 // what follows every move of the triangles: the resets of geometryChanged, then the rebuild policy on the trees as they stand now
 void Tracer::afterMove()
@@ -326,7 +300,7 @@ void Tracer::setEnvMap(const std::string &hdrFile)
     for (auto *c : ranks()) c->createEnvMap(envMap.get());
     params.useEnvMap = 1;
     paramsUpdatePending = true;
-    dropHistory();                                           // another light: the accumulated radiance is stale
+    history.dropped();                                       // another light: the accumulated radiance is stale
 }
 
 // reference: src/tracer.cpp:625-684 (iterateStateItems): one item after the other in native byte order
@@ -372,68 +346,50 @@ void Tracer::setDenoiserStrength(float s)
     if (s > 0.0f && !peers.empty()) throw std::runtime_error("setDenoiserStrength: the denoiser is single-GPU (a pixel's neighbours are on other ranks)");
     denoiserStrength = s;
 }
+// what the four reprojection switches refuse alike, under the setter's own name
+void Tracer::refuseSwitch(const char *setter, bool on, bool needsTemporal) const
+{
+    const std::string name(setter);
+    if (on && !peers.empty()) throw std::runtime_error(name + ": temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
+    if (on && needsTemporal && !history.temporal()) throw std::runtime_error(name + ": needs setTemporalReprojection(true)");
+}
 void Tracer::setTemporalReprojection(bool on)
 {
-    if (on && !peers.empty()) throw std::runtime_error("setTemporalReprojection: temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
-    temporalOn = on;
-    dropHistory(); temporalFrames = 0;
-    if (!on && motionOn) setMotionReprojection(false);
-    if (!on && deformOn) setDeformReprojection(false);
-    if (!on && rectifyOn) setHistoryRectification(false);
+    refuseSwitch("setTemporalReprojection", on, false);
+    history.temporalSet(on);
+    if (!on && history.motion()) setMotionReprojection(false);
+    if (!on && history.deform()) setDeformReprojection(false);
+    if (!on && history.rectify()) setHistoryRectification(false);
 }
 void Tracer::setHistoryRectification(bool on)
 {
-    if (on && !peers.empty()) throw std::runtime_error("setHistoryRectification: temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
-    if (on && !temporalOn) throw std::runtime_error("setHistoryRectification: needs setTemporalReprojection(true)");
-    rectifyOn = on;
-    markPending = false;
+    refuseSwitch("setHistoryRectification", on);
+    history.rectifySet(on);
 }
 void Tracer::setRectifyDelay(int frames)
 {
     if (frames < 0) throw std::runtime_error("setRectifyDelay: the delay is a number of frames >= 1 (0: the default, 2 maxBounces + 2)");
-    rectifyDelay = (uint32_t)frames;
+    history.rectifyDelaySet((uint32_t)frames);
 }
 void Tracer::setMotionReprojection(bool on)
 {
-    if (on && !peers.empty()) throw std::runtime_error("setMotionReprojection: temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
-    if (on && !temporalOn) throw std::runtime_error("setMotionReprojection: needs setTemporalReprojection(true)");
-    if (on && deformOn) throw std::runtime_error("setMotionReprojection: per-vertex reprojection is on, which follows poseObjects too; setDeformReprojection(false) first");
+    refuseSwitch("setMotionReprojection", on);
+    if (on && history.deform()) throw std::runtime_error("setMotionReprojection: per-vertex reprojection is on, which follows poseObjects too; setDeformReprojection(false) first");
     for (auto *c : ranks()) c->setOption("motion_history", on ? 1 : 0);
-    motionOn = on;
-    dropHistory();                                           // a G-buffer traced under the other setting has no object plane (or one nobody keeps up)
+    history.motionSet(on);
 }
 void Tracer::setDeformReprojection(bool on)
 {
-    if (on && !peers.empty()) throw std::runtime_error("setDeformReprojection: temporal reprojection is single-GPU (a pixel's neighbours are on other ranks)");
-    if (on && !temporalOn) throw std::runtime_error("setDeformReprojection: needs setTemporalReprojection(true)");
-    if (on && motionOn) throw std::runtime_error("setDeformReprojection: motion-aware reprojection is on; setMotionReprojection(false) first (this switch follows poseObjects too)");
+    refuseSwitch("setDeformReprojection", on);
+    if (on && history.motion()) throw std::runtime_error("setDeformReprojection: motion-aware reprojection is on; setMotionReprojection(false) first (this switch follows poseObjects too)");
     for (auto *c : ranks()) c->setOption("deform_history", on ? 1 : 0);
-    deformOn = on;
-    dropHistory();                                           // a G-buffer traced under the other setting has no barycentric plane (or one nobody keeps up)
-}
-// everything of RenderParams that shapes the radiance of a point, i.e. all but the camera (bytes 96..175) and the post-process (exposure,
-// tmOperator: 176..183), equals what the G-buffer's frames were rendered with
-// a history exists: at least one frame rendered since the last G-buffer (or poseObjects has captured it already), at the same size (a resize frees
-// the device's slots) and with nothing but the camera changed since (lights, bounces, sampling switches: the kept radiance would be stale)
-bool Tracer::historyExists(bool posed) const
-{
-    return temporalOn && useWavefront && haveGbuffer && (poseHistory || framesSinceGbuffer > 0) && gbWidth == params.width && gbHeight == params.height &&
-           onlyCameraChanged(posed);
-}
-bool Tracer::onlyCameraChanged(bool posed) const
-{
-    RenderParams now = params;
-    if (posed) now.worldRadius = gbParams.worldRadius;
-    if (rectifyOn) now.areaLight = gbParams.areaLight;       // history rectification sheds what a changed area light contradicts
-    const char *a = (const char *)&now, *b = (const char *)&gbParams;
-    return std::memcmp(a, b, offsetof(RenderParams, camera)) == 0 &&
-           std::memcmp(a + offsetof(RenderParams, width), b + offsetof(RenderParams, width), sizeof(RenderParams) - offsetof(RenderParams, width)) == 0;
+    history.deformSet(on);
 }
 void Tracer::toggleRenderer()
 {
     if (!useWavefront && meshLightsOn && !meshLightsWavefrontOn)
         throw std::runtime_error("toggleRenderer: mesh lights are on and the wavefront integrator does not see emissive triangles -- the scene's lamps would go dark; setMeshLights(false) first");
-    useWavefront = !useWavefront; iteration = 0; dropHistory();
+    useWavefront = !useWavefront; iteration = 0; history.dropped();
 }
 void Tracer::setMeshLights(bool on)
 {
@@ -442,7 +398,7 @@ void Tracer::setMeshLights(bool on)
     clctx->setOption("mesh_lights", on ? 1 : 0);
     meshLightsOn = on;
     if (!on && meshLightsWavefrontOn) { clctx->setOption("mesh_lights_wavefront", 0); meshLightsWavefrontOn = false; }
-    iteration = 0; dropHistory();                                        // the accumulation was lit differently
+    iteration = 0; history.dropped();                                    // the accumulation was lit differently
 }
 // ... and the wavefront integrator: the logic pass's MESH instance samples and collects the lamps, so the wavefront loop is
 // allowed again.  The integrator in use stays the one it is: toggleRenderer() switches.
@@ -454,7 +410,7 @@ void Tracer::setMeshLightsWavefront(bool on)
     if (!on && meshLightsOn && useWavefront) toggleRenderer();           // back to the integrator that sees the lamps, as setMeshLights(true) does
     clctx->setOption("mesh_lights_wavefront", on ? 1 : 0);
     meshLightsWavefrontOn = on;
-    iteration = 0; dropHistory();
+    iteration = 0; history.dropped();
 }
 void Tracer::setMaxHistory(float n)
 {
@@ -501,7 +457,7 @@ void Tracer::renderSingle(int spp, bool denoise)
     params.useRoulette = 0;                                              // :104-108
     if (denoise) setDenoiser(true);                                      // :110-114
     clctx->updateParams(params); paramsUpdatePending = false;
-    dropHistory();                                                       // parameters reach the device without a G-buffer
+    history.dropped();                                                   // parameters reach the device without a G-buffer
     clctx->enqueueResetKernel(params);
     for (int sample = 0; sample < spp; sample++) {
         clctx->enqueueRayGenKernel(params);
@@ -537,7 +493,7 @@ uint64_t Tracer::renderAdaptive(int minSpp, int maxSpp, float threshold, bool de
     try {
     if (!hadMoments) clctx->setOption("moments", 1);                     // for this render only
     clctx->updateParams(params); paramsUpdatePending = false;
-    dropHistory();
+    history.dropped();
     clctx->enqueueResetKernel(params);                                   // (also clears a list of active pixels)
     HipContext::AdaptiveParams ap;
     ap.threshold = threshold; ap.minSamples = (uint32_t)minSpp; ap.maxSamples = (uint32_t)maxSpp;
@@ -598,22 +554,14 @@ void Tracer::update()
     auto R = ranks();
     bool reprojectNow = false;
     if (paramsUpdatePending) {
-        const bool temporal = temporalOn && useWavefront;
-        // (poseObjects under motion-aware reprojection has captured it already: a camera change pending in the same frame shares that capture)
-        const bool history = historyExists(poseHistory);
-        if (history && !poseHistory) clctx->historyCapture();            // under the old camera's slot
-        poseHistory = false;
+        const HistoryState::ParamsPlan plan = history.paramsReachDevice(params, useWavefront);
+        if (plan.captureNow) clctx->historyCapture();                    // under the old camera's slot: before the parameters reach the device
         for (auto *c : R) c->updateParams(params);
         paramsUpdatePending = false; iteration = 0;
-        if (temporal) {
-            clctx->gbuffer();
-            haveGbuffer = true; gbParams = params; gbWidth = params.width; gbHeight = params.height; framesSinceGbuffer = 0;
-            reprojectNow = history;
-        } else dropHistory();                                            // the update was consumed without a G-buffer: the slot is another camera's
+        if (plan.traceGbuffer) clctx->gbuffer();
+        reprojectNow = plan.reprojectNow;
     }
-    if (iteration == 0 && !reprojectNow) temporalFrames = 0;             // the accumulation restarts from nothing
-    if (iteration == 0) markPending = false;                             // the reset below drops the device's mark
-    const bool markNow = rectifyOn && reprojectNow && iteration == 0 && useWavefront;
+    const bool markNow = history.frameStarts(iteration, reprojectNow, useWavefront);
     if (!useWavefront) {
         if (!peers.empty()) throw std::runtime_error("update: the microkernel integrator is single-GPU");
         updateMicrokernel(); return;
@@ -649,15 +597,15 @@ void Tracer::update()
     }
     if (iteration == 0) { params.maxBounces = maxBounces; for (auto *c : R) c->updateParams(params); }
     // history rectification: the frame that reprojected marks what it has (history + preview); the frame that completes the delay compares
-    if (markNow) { clctx->historyMark(); markPending = true; }
-    else if (rectifyOn && markPending && framesSinceGbuffer + 1 >= getRectifyDelay()) {
+    if (markNow) { clctx->historyMark(); history.marked(); }
+    else if (history.rectifyDue(params.maxBounces)) {
         const double before = measureRetained ? clctx->markedSamples() : 0.0;
         clctx->historyRectify();
         if (measureRetained) retainedShare = before > 0.0 ? clctx->markedSamples() / before : std::nan("");
-        markPending = false; rectifies++;
+        history.rectified(); rectifies++;
     }
     for (auto *c : R) c->enqueuePostprocessKernel(params);
-    const uint32_t sched = temporalOn ? temporalFrames : iteration;      // temporal reprojection: frames since the last discarded history
+    const uint32_t sched = history.denoiserSchedule(iteration);          // temporal reprojection: frames since the last discarded history
     if (useDenoiser && denoiserStrength > 0.0f && sched >= 10 && sched % 10 == 0) denoiseStep();   // :310-328 (single-GPU: setDenoiserStrength)
     for (auto *c : R) c->finishQueue();
     QueueCounters sum; std::memset(&sum, 0, sizeof(sum));
@@ -672,7 +620,7 @@ void Tracer::update()
     clctx->statsAsync.primaryRays += sum.raygenQueue;
     clctx->statsAsync.samples += (iteration > 0) ? sum.raygenQueue : 0;
     lastCnt = sum;
-    iteration++; framesSinceGbuffer++; temporalFrames++;
+    iteration++; history.frameRendered();
 }
 
 // reference: src/tracer.cpp:362-528, wavefront body
@@ -687,7 +635,7 @@ std::string Tracer::runBenchmark(double seconds, int iterations)
     // resetRenderer (:372-382)
     iteration = 0;
     paramsUpdatePending = false;
-    dropHistory();
+    history.dropped();
     for (auto *c : R) {
         c->updateParams(params);
         c->resetPixelIndex();

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "hipcontext.hpp"
+#include "history_state.hpp"
 #include "rebuild_job.hpp"
 
 namespace fluctus {
@@ -114,7 +115,7 @@ public:
     // until the camera rests.  The interactive microkernel branch overwrites the pixel with its preview splat and keeps today's reset;
     // renderSingle is unaffected.  Single-GPU: throws on a multi-rank Tracer.
     void setTemporalReprojection(bool on);
-    bool getTemporalReprojection() const { return temporalOn; }
+    bool getTemporalReprojection() const { return history.temporal(); }
     void setMaxHistory(float n);                                                  // flx_reproject's max_history (>= 1; default 32)
     // Motion-aware reprojection, default off; needs setTemporalReprojection(true) and throws without it or on a multi-rank
     // Tracer.  On: poseObjects on the WAVEFRONT integrator no longer throws the accumulation away -- it captures the history (at most once per
@@ -122,7 +123,7 @@ public:
     // sequence unchanged and reproject, each posed object's pixels looking their history up where the object was.  Everything else that changes
     // the geometry restarts as ever: updateGeometry in either form, a rebuild the policy runs or adopts, the microkernel branch, renderSingle.
     void setMotionReprojection(bool on);
-    bool getMotionReprojection() const { return motionOn; }
+    bool getMotionReprojection() const { return history.motion(); }
     // Per-vertex reprojection, default off; needs setTemporalReprojection(true) and throws without it, on a multi-rank Tracer
     // and while motion-aware reprojection is on (the two options refuse each other on the device; this one follows poseObjects as well).  On:
     // updateGeometry in both forms and poseObjects on the WAVEFRONT integrator keep the accumulation as poseObjects does under
@@ -130,7 +131,7 @@ public:
     // moved triangle's pixels looking their history up where that point of the triangle was.  A rebuild the policy runs or adopts, the
     // microkernel branch and renderSingle restart as ever.
     void setDeformReprojection(bool on);
-    bool getDeformReprojection() const { return deformOn; }
+    bool getDeformReprojection() const { return history.deform(); }
     float getMaxHistory() const { return maxHistory; }
     // History rectification, default off; needs setTemporalReprojection(true) and throws without it or on a multi-rank Tracer.
     // On: a frame that reprojects runs exactly as without the switch, preview passes included, and ends on flx_history_mark (the preview's
@@ -143,9 +144,9 @@ public:
     // setEnvMap included, discards the history as ever.  lastRetainedShare: the mark's sample count after the last rectify over the one before
     // it (NaN before one; two blocking reads per rectify while measureRetained is set).
     void setHistoryRectification(bool on);
-    bool getHistoryRectification() const { return rectifyOn; }
+    bool getHistoryRectification() const { return history.rectify(); }
     void setRectifyDelay(int frames);                                             // >= 1; 0 = the default, 2 maxBounces + 2
-    uint32_t getRectifyDelay() const { return rectifyDelay ? rectifyDelay : 2 * params.maxBounces + 2; }
+    uint32_t getRectifyDelay() const { return history.rectifyDelayFrames(params.maxBounces); }
     bool measureRetained = false;
     double lastRetainedShare() const { return retainedShare; }
     uint32_t rectifyCount() const { return rectifies; }                           // how many times update() has run flx_history_rectify
@@ -214,7 +215,7 @@ private:
     void uploadTopology(BVH *tree, const std::vector<flx_triangle> &tris);        // every rank; keeps the first upload's option choices; re-reads the baseline
     void refitAll(const std::vector<flx_triangle> &tris);                         // every rank + the host tree + the scene's triangles
     bool adoptFinishedRebuild();                                                  // a finished job -> uploaded and refitted to the current triangles
-    void afterMove();                                                             // geometryChanged + the rebuild policy: what both updateGeometry overloads end on
+    void afterMove();                                                             // geometryChanged + the rebuild policy: what every move ends on
     void geometryChanged();                                                       // worldRadius, history, accumulation: what a change of the trees resets
     uint32_t iteration = 0;
     bool paramsUpdatePending = true;
@@ -224,25 +225,14 @@ private:
     bool momentsOn = false;                                                       // the ranks' option "moments" as applyMoments left it
     void applyMoments();                                                          // "moments" on iff the denoiser is on in VarianceGuided mode
     void denoiseStep();                                                           // the mode's filter with blend = 1 - strength (rank 0; single-GPU)
-    bool temporalOn = false;
+    // whether the device holds a history worth keeping: history_state.hpp decides and keeps the books, this class calls the device
+    HistoryState history;
     float maxHistory = 32.0f;
-    // the context's current slot holds the G-buffer of the camera the accumulation is being rendered under, traced under gbParams; cleared
-    // wherever parameters reach the device without flx_gbuffer (dropHistory)
-    bool haveGbuffer = false;
-    RenderParams gbParams {};
-    void dropHistory() { haveGbuffer = false; poseHistory = false; markPending = false; }
-    bool historyExists(bool posed) const;                                         // update()'s conditions for a history worth capturing, shared with poseObjects
-    bool onlyCameraChanged(bool posed = false) const;                             // params against gbParams, the camera and the post-process aside (posed: and worldRadius, which a pose re-derives)
-    bool motionOn = false, deformOn = false;
-    bool keepHistoryAcrossMove(bool on, bool &captured);                          // capture before the ranks move (at most once per frame)
-    void movedKeepingHistory(bool keep, uint32_t topologiesBefore);               // ... and re-arm update() after afterMove()
-    bool rectifyOn = false, markPending = false;                                  // markPending: a frame has marked and its rectify has not run yet
-    uint32_t rectifyDelay = 0, rectifies = 0;
+    uint32_t rectifies = 0;
     double retainedShare = 0.0;                                                   // (set to NaN by the constructor)
-    bool poseHistory = false;                                                     // poseObjects has captured the history of this frame: the next update() reprojects it
-    uint32_t gbWidth = 0, gbHeight = 0;                                           // ... traced at this size
-    uint32_t framesSinceGbuffer = 0;                                              // > 0: there is an accumulation worth capturing
-    uint32_t temporalFrames = 0;                                                  // frames since the last discarded history (the denoiser schedule while temporalOn)
+    void refuseSwitch(const char *setter, bool on, bool needsTemporal = true) const;   // what the reprojection switches refuse alike: several ranks; on without temporal reprojection
+    // the body of both updateGeometry overloads and poseObjects; keepSwitch: the switch under which this kind of move keeps the history
+    template <class MoveRanks, class MoveHost> void moveTriangles(bool keepSwitch, MoveRanks moveRanks, MoveHost moveHost);
     bool meshLightsOn = false, meshLightsWavefrontOn = false;
     bool useWavefront = true;                                                     // this library's default; the reference starts on MK (src/tracer.cpp:11)
     QueueCounters lastCnt {};

