@@ -141,6 +141,10 @@ int flx_create(int device, uint32_t num_tasks, flx_ctx **out)
         if (dalloc(c, c->fixedAllocs, &c->st.rec[r], N)) return fail("hipMalloc(state)", hipErrorOutOfMemory);
         (void)hipMemsetAsync(c->st.rec[r], 0, N * sizeof(float4), c->stream);
     }
+    for (int r = 0; r < 2; r++) {                        // the second {ORIG, DIR} pair (flx_device.h: State::other); freed with fixedAllocs whichever pair is current
+        if (dalloc(c, c->fixedAllocs, &c->st.other[r], N)) return fail("hipMalloc(state)", hipErrorOutOfMemory);
+        (void)hipMemsetAsync(c->st.other[r], 0, N * sizeof(float4), c->stream);
+    }
     if (dalloc(c, c->fixedAllocs, &c->st.phase, N) || dalloc(c, c->fixedAllocs, &c->mkStats, 4)) return fail("hipMalloc(state)", hipErrorOutOfMemory);
     (void)hipMemsetAsync(c->st.phase, 0, N * 4, c->stream); (void)hipMemsetAsync(c->mkStats, 0, 16, c->stream);
     if (dalloc(c, c->fixedAllocs, &c->st.blocked, N) || dalloc(c, c->fixedAllocs, &c->st.pickProb, N) || dalloc(c, c->fixedAllocs, &c->st.firstDiffuse, N))
@@ -361,6 +365,8 @@ int flx_set_option(flx_ctx *c, const char *name, int value)
     if (name && strcmp(name, "ext_order") == 0 && value >= 0 && value <= 2) { c->extOrder = value; return 0; }
     if (name && strcmp(name, "regen") == 0 && (value == 0 || value == 1)) { if (value && optionBuffers(c, false, true)) return 1; c->regenOpt = value; return 0; }
     if (name && strcmp(name, "regen_prep") == 0 && (value == 0 || value == 1)) { c->prepOpt = value; return 0; }
+    // 1: the fused RAW pass leaves the committed hit point / uv record to k_settle_hits | 0: it stores them itself.  (CALL_PEEK above has settled what was pending.)
+    if (name && strcmp(name, "lazy_hit_commit") == 0 && (value == 0 || value == 1)) { c->lazyCommitOpt = value; return 0; }
     if (name && strcmp(name, "regroup") == 0 && value >= -1 && value <= 1) { c->regroupOpt = value; c->regroup = value >= 0 ? value : c->regroupAuto; return 0; }
     if (name && strcmp(name, "fuse_set") == 0 && (value == 1 || value == 31)) { c->fuseSet = value; return 0; }
     if (name && strcmp(name, "overlap") == 0 && value >= -1 && value <= 2) { ENTER(c, CALL_OBSERVE); c->overlapOpt = value; pickSchedule(c); return 0; }
@@ -412,17 +418,17 @@ int flx_set_option(flx_ctx *c, const char *name, int value)
     return 1;
 }
 // the state machine's state as one number (read-only option "phase"; tests/test_gpu_fuzz.py reports which (phase, call) pairs it exercised):
-// bits 0-2 enum Phase, bit 3 RAW hit records pending, bit 4 material queues known empty
+// bits 0-2 enum Phase, bit 3 RAW hit records pending, bit 4 material queues known empty, bit 5 previous hits pending (flx_ctx::prevHitsPending)
 static int phaseCode(const flx_ctx *c)
 {
-    return c->phase | (c->rawHits ? 8 : 0) | (c->matQueuesEmpty ? 16 : 0);
+    return c->phase | (c->rawHits ? 8 : 0) | (c->matQueuesEmpty ? 16 : 0) | (c->prevHitsPending ? 32 : 0);
 }
 int flx_get_option(flx_ctx *c, const char *name, int *value)
 {
     NEED(c, name && value, "flx_get_option: null");
     const struct { const char *n; int v; } tab[] = {
         {"xcd_remap", c->xcdRemap}, {"fuse", c->fuse}, {"overlap", c->overlap}, {"shadow_tree", c->shadowTree}, {"extend_tree", c->extendTree},
-        {"denoiser", c->denoiser}, {"moments", c->moments}, {"motion_history", c->motionHistory}, {"deform_history", c->deformHistory},{"mesh_lights", c->ml.state.on ? 1 : 0}, {"mesh_lights_wavefront", c->ml.state.wavefront ? 1 : 0}, {"eager_bump", c->eagerBump}, {"node_layout", c->nodeLayout}, {"fuse_set", c->fuseSet}, {"ext_order", c->extOrder}, {"regen", c->regenOpt}, {"regroup", c->regroup}, {"regen_prep", c->prepOpt}, {"refill_extend", c->refillExt}, {"refill_shadow", c->refillShadow}, {"shadow_split", c->shadowSplit}, {"fused_queue_mask", (int)fused_queue_mask(fuseSetNow(c))}, {"fuse_set_now", fuseSetNow(c)}};
+        {"denoiser", c->denoiser}, {"moments", c->moments}, {"motion_history", c->motionHistory}, {"deform_history", c->deformHistory},{"mesh_lights", c->ml.state.on ? 1 : 0}, {"mesh_lights_wavefront", c->ml.state.wavefront ? 1 : 0}, {"eager_bump", c->eagerBump}, {"node_layout", c->nodeLayout}, {"fuse_set", c->fuseSet}, {"ext_order", c->extOrder}, {"regen", c->regenOpt}, {"regroup", c->regroup}, {"regen_prep", c->prepOpt}, {"lazy_hit_commit", c->lazyCommitOpt}, {"refill_extend", c->refillExt}, {"refill_shadow", c->refillShadow}, {"shadow_split", c->shadowSplit}, {"fused_queue_mask", (int)fused_queue_mask(fuseSetNow(c))}, {"fuse_set_now", fuseSetNow(c)}};
     for (const auto &t : tab) if (strcmp(name, t.n) == 0) { *value = t.v; return 0; }
     if (strcmp(name, "phase") == 0) { *value = phaseCode(c); return 0; }
     if (strcmp(name, "wide_far") == 0) { *value = wideFar(c); return 0; }

@@ -2,25 +2,30 @@
 // serves -- flx_wf_*, flx_clear_queues, flx_end_iteration_async.  The only writer of the scheduling fields of flx_ctx apart from the options.
 #include "flx_ctx.h"
 
-struct Step { bool launchDeferred, commitRaw; int next; };
+// settlePrev: a pass with "lazy_hit_commit" may have left the hit point / uv records of its paths to whoever looks first (flx_ctx::prevHitsPending):
+// k_settle_hits writes them before this call goes on.  Asked for wherever commitRaw is -- the same observers -- and by every call after which the NEXT
+// extension launch could miss one of those paths or find the chain since the pass broken: a second `logic` (it reads hit records, and a path the pass
+// terminated must not look traced to it), an extension launch from any phase but PH_CHAIN, and every call that leaves the chain (they enter PH_IDLE, from
+// where the extension launch settles).  The one call that needs nothing is the extension launch of the intact chain: it overwrites every pending record.
+struct Step { bool launchDeferred, commitRaw, settlePrev; int next; };
 static Step transition(int ph, Call call)
 {
     const bool deferred = ph == PH_DEFER_LOGIC || ph == PH_DEFER_LOGIC_RAYGEN;
     const bool chain = deferred || ph == PH_CHAIN || ph == PH_CHAIN_EXT;       // only genRays / materials / extension since `logic`
     switch (call) {
-    case CALL_LOGIC:     return {deferred, false, PH_IDLE};                     // (flx_wf_logic then enters PH_DEFER_LOGIC or PH_CHAIN; it hands RAW records to the fused pass or commits them itself)
-    case CALL_RAYGEN:    if (ph == PH_DEFER_LOGIC) return {false, false, PH_DEFER_LOGIC_RAYGEN};
-                         return {deferred, false, chain ? PH_CHAIN : PH_IDLE};  // genRays reads no hit record (and its paths' records are dead: flx_device.h)
-    case CALL_MATERIALS: if (deferred) return {false, false, PH_CHAIN};         // the fused pass runs now (flx_wf_materials)
-                         return {false, true, chain ? PH_CHAIN : PH_IDLE};      // the separate material kernels read the hit records
-    case CALL_EXTEND:    return {deferred, true, chain ? PH_CHAIN_EXT : PH_EXT};   // (a second extension launch needs the first one's records committed: pathLen)
-    case CALL_SHADOW:    return {deferred, false, PH_IDLE};                     // {shadowOrig, shadowDir} -> shadowRayBlocked: no hit record
-    case CALL_QUIET:     return {deferred, false, deferred ? PH_CHAIN : ph};
-    case CALL_NEUTRAL:   return {deferred, false, PH_IDLE};
-    case CALL_PEEK:      return {deferred, true, deferred ? PH_CHAIN : ph};
-    case CALL_OBSERVE:   return {deferred, true, PH_IDLE};
+    case CALL_LOGIC:     return {deferred, false, true, PH_IDLE};               // (flx_wf_logic then enters PH_DEFER_LOGIC or PH_CHAIN; it hands RAW records to the fused pass or commits them itself)
+    case CALL_RAYGEN:    if (ph == PH_DEFER_LOGIC) return {false, false, false, PH_DEFER_LOGIC_RAYGEN};
+                         return {deferred, false, false, chain ? PH_CHAIN : PH_IDLE};  // genRays reads no hit record (and its paths' records are dead: flx_device.h)
+    case CALL_MATERIALS: if (deferred) return {false, false, false, PH_CHAIN};  // the fused pass runs now (flx_wf_materials)
+                         return {false, true, true, chain ? PH_CHAIN : PH_IDLE};       // the separate material kernels read the hit records
+    case CALL_EXTEND:    return {deferred, true, ph != PH_CHAIN, chain ? PH_CHAIN_EXT : PH_EXT};   // (a second extension launch needs the first one's records committed: pathLen)
+    case CALL_SHADOW:    return {deferred, false, false, PH_IDLE};              // {shadowOrig, shadowDir} -> shadowRayBlocked: no hit record
+    case CALL_QUIET:     return {deferred, false, false, deferred ? PH_CHAIN : ph};
+    case CALL_NEUTRAL:   return {deferred, false, false, PH_IDLE};
+    case CALL_PEEK:      return {deferred, true, true, deferred ? PH_CHAIN : ph};
+    case CALL_OBSERVE:   return {deferred, true, true, PH_IDLE};
     }
-    return {deferred, true, PH_IDLE};
+    return {deferred, true, true, PH_IDLE};
 }
 // lazy extension counter (flx_device.h): make counters[EXTENSION] in memory current before anything outside the
 // raygen / material / extension / end-of-iteration kernels looks at it or overwrites the source counters
@@ -49,6 +54,16 @@ static int materialise(flx_ctx *c)
     LAUNCHED(c);
     return 0;
 }
+// write the hit point / uv records a pass with "lazy_hit_commit" left out (trace4r.hip: k_settle_hits, from the ray the pass consumed: st.other[])
+static int settlePrevHits(flx_ctx *c)
+{
+    if (!c->prevHitsPending) return 0;
+    c->prevHitsPending = false;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_settle_hits(c->stream, c->st, c->sc, c->params, (uint32_t)c->numCUs);
+    LAUNCHED(c);
+    return 0;
+}
 // how this fused pass lists the traced paths in the extension queue: ext_order 2 (regenerated + continuing paths merged by path id) needs
 // genRays to follow in the same chain -- the scatter writes the regenerated paths' entries, genRays then must not -- and falls back to 1
 // (continuing paths by id, genRays appends its own block whenever it is called) otherwise
@@ -67,6 +82,7 @@ static int runLogic(flx_ctx *c, int first, int fused, int raygenFirst)
     // ... and only when the pass covers EVERY path: with `first` set, logic stops at min(numTasks, pixels) (src/wf_logic.cl:45-48) and the paths
     // beyond would keep their RAW records (found by tests/test_gpu_fuzz.py, round 4)
     const int raw = (c->rawHits && fused != 0 && raygenFirst && !first) ? 1 : 0;
+    if (settlePrevHits(c)) return 1;                   // (CALL_LOGIC has asked for it already: no pass starts over records an earlier one left out)
     if (!raw && materialise(c)) return 1;
     c->rawHits = false;
     flushExt(c);                                       // logic's scan overwrites the source-queue counters
@@ -84,12 +100,16 @@ static int runLogic(flx_ctx *c, int first, int fused, int raygenFirst)
     // k_raygen that follows.  Same conditions as the in-kernel regeneration (every entry of the raygen queue is a path this pass terminated), minus the look-back.
     const int prep = (raw && !regen && c->prepOpt && c->raygenQueueEmpty && c->fr.localPixels > 0) ? 1 : 0;
     c->prepDone = prep != 0;
+    // LAZY HIT COMMIT (logic.hip; option "lazy_hit_commit", default on): the RAW pass stores neither the committed hit point nor the uv record and writes the
+    // new ray to the other {ORIG, DIR} pair; the pairs are swapped behind the launch, so the ray the RAW records belong to outlives the pass
+    const int lazy = (raw && c->lazyCommitOpt && logic_can_lazy_commit(fused)) ? 1 : 0;
     if (++c->logicEpoch == 0u) c->logicEpoch = 1u;     // (epoch 0 = the zero-filled words of a fresh context)
-    { ScopedTimer t(c, fused ? FLX_K_LOGIC_FUSED : FLX_K_LOGIC); launch_logic(c->stream, c->st, c->qs, c->sc, c->fr, c->params, c->member, c->blockCounts, c->queueAux, first, fused, raygenFirst, order, raw,
+    { ScopedTimer t(c, fused ? FLX_K_LOGIC_FUSED : FLX_K_LOGIC); launch_logic(c->stream, c->st, c->qs, c->sc, c->fr, c->params, c->member, c->blockCounts, c->queueAux, first, fused, raygenFirst, order, raw, lazy,
                                                                                 c->lookback, c->logicEpoch, regen ? 1 : (prep ? 2 : 0), order == 2 ? 0 : 1, c->logicError, c->regroup,
                                                                                 c->queueParity ^= 1u, (uint32_t)c->numCUs,
                                                                                 (!fused && c->ml.state.litWavefront()) ? &c->ml.t : nullptr); }      // the lamps light this pass: its MESH instance
     LAUNCHED(c);
+    if (lazy) { std::swap(c->st.rec[S_ORIG], c->st.other[0]); std::swap(c->st.rec[S_DIR], c->st.other[1]); c->prevHitsPending = true; }
     c->matQueuesEmpty = false; c->raygenQueueEmpty = false;
     if (c->overlap == 2) HIPCHK(c, hipEventRecord(c->evPostLogic, c->stream));
     return 0;
@@ -110,6 +130,7 @@ int flxd::enter(flx_ctx *c, Call call)
         if (runLogic(c, c->pendFirst, 0, 0)) return 1;     // (commits RAW hit records first)
         if (withRaygen && runRaygen(c)) return 1;
     }
+    if (st.settlePrev && settlePrevHits(c)) return 1;
     if (st.commitRaw && materialise(c)) return 1;
     c->phase = st.next;
     return 0;
@@ -128,6 +149,7 @@ int flx_wf_extend(flx_ctx *c)
 {
     READY(c, CALL_EXTEND);
     const bool chainIntact = c->phase == PH_CHAIN_EXT;
+    c->prevHitsPending = false;                        // settled on the way in, or this launch overwrites every pending record (transition: the intact chain)
     // "everything enqueued before the extension kernel": what a concurrent shadow kernel waits for -- unless it may start right after
     // `logic` (overlap 2 with the chain intact: it then waits for evPostLogic instead, and this marker would only put one more barrier
     // packet in front of the extension kernel)

@@ -123,6 +123,14 @@ struct flx_ctx {
     // fused logic pass of the next iteration (the steady state: nothing else touches hit records between the extension kernel and logic),
     // or by k_materialise as soon as an entry point that could observe a hit record runs (transition(): commitRaw).
     bool rawHits = false;
+    // PREVIOUS HITS PENDING.  The fused RAW pass with option "lazy_hit_commit" does the commit in registers and stores neither the hit point
+    // nor the uv record (logic.hip: LAZY): the paths it served keep their RAW {u, v, triangle, t}, and the ray those were traced with survives in
+    // st.other[] (flx_device.h).  True from that pass until the extension launch of an INTACT chain -- only genRays / the fused pass's material kernel /
+    // quiet calls since the pass: its queue holds every one of those paths and the kernel overwrites every such record -- or until k_settle_hits has
+    // written the two records the pass left out, which transition() asks for before any other call that could see them or break that chain.
+    // Never true together with rawHits: the pass that sets it consumes rawHits, and an extension launch clears or settles it before it sets rawHits.
+    bool prevHitsPending = false;
+    int lazyCommitOpt = 1;                      // option "lazy_hit_commit"
     bool cursorDirty[2] = {false, false};       // block cursors of the persistent kernels (closest hit, any hit) used since they were last zeroed
 
     uint32_t wideInfo[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // flx_scene_info

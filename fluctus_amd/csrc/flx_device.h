@@ -36,6 +36,11 @@ struct State {
     float4 *rec[S_NUM_REC];       // record r of path gid: rec[r] + gid  (pure SoA of float4; a layout of 64-byte lines with four records each
                                   // was measured in round 1 and lost: the coalesced kernels turn into 16-byte accesses at a 64-byte stride)
     __host__ __device__ __forceinline__ float4 *at(int r, uint32_t gid) const { return rec[r] + (size_t)gid; }
+    // ORIG and DIR are DOUBLE-BUFFERED: a second pair of arrays beside rec[S_ORIG] / rec[S_DIR].  The fused RAW pass that leaves the
+    // committed hit record to whoever looks first (logic.hip: LAZY) reads the ray from rec[] and writes the new one HERE; the host swaps the two pairs
+    // behind the launch (api_wavefront.hip: runLogic), so every later launch finds the current ray in rec[] as ever and the ray the pass consumed -- the
+    // one its RAW records were traced with -- in other[] (trace4r.hip: k_settle_hits is its only reader).  Every other kernel reads and writes rec[] alone.
+    float4 *other[2];             // {ORIG, DIR}
     uint32_t *blocked;            // shadowRayBlocked
     float *pickProb;              // lastLightPickProb
     uint32_t *firstDiffuse;       // carried for export parity only

@@ -83,12 +83,14 @@ void launch_shadow4_split(hipStream_t, const State &, const Queues &, const Scen
 uint32_t shadow_split_lists(); uint32_t shadow_split_count_words();
 void launch_extend4r(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, uint32_t *);
 void launch_shadow4r(hipStream_t, const State &, const Queues &, const Scene &, const flx_render_params &, uint32_t *, uint32_t, int, uint32_t *);
-void launch_logic(hipStream_t, const State &, const Queues &, const Scene &, const Frame &, const flx_render_params &, uint8_t *, uint32_t *, uint32_t *, int, int, int, int, int,
+void launch_logic(hipStream_t, const State &, const Queues &, const Scene &, const Frame &, const flx_render_params &, uint8_t *, uint32_t *, uint32_t *, int, int, int, int, int, int,
                   unsigned long long *, uint32_t, int, int, uint32_t *, int, uint32_t, uint32_t, const MeshLights *);     // (the last: non-null = the MESH instance of the plain pass)
 void launch_env_nee_table(hipStream_t, const Scene &, float4 *, uint32_t);
 int logic_can_regenerate();
+int logic_can_lazy_commit(int fuse);     // does the RAW pass of this BSDF set have an instance that leaves the hit point / uv records out (logic.hip: LAZY)?
 uint32_t logic_lookback_words(uint32_t numTasks);
 void launch_materialise(hipStream_t, const State &, const Scene &, const flx_render_params &, uint32_t);
+void launch_settle_hits(hipStream_t, const State &, const Scene &, const flx_render_params &, uint32_t);
 void launch_materials(hipStream_t, const State &, const Queues &, const Scene &, uint32_t);
 void launch_materials_after_fused(hipStream_t, const State &, const Queues &, const Scene &, uint32_t, int);
 uint32_t fused_queue_mask(int);

@@ -146,6 +146,12 @@ __device__ __forceinline__ HitVals hit_values_raw(const Scene &sc, const flx_ren
 {
     return hit_values<true>(sc, p, orig, dir, raw.w, raw.x, raw.y, (int)(__float_as_uint(raw.z) & FLX_RAW_TRI) - 1);
 }
+// ... of a path that is known to have CONTINUED behind that commit (material.hip: LAZY): the quad was not met, and then the commit is the triangle's alone
+__device__ __forceinline__ HitVals hit_surface_raw(const Scene &sc, f3 orig, f3 dir, float4 raw)
+{
+    const flx_render_params none{};                     // (never read: LIGHT_QUAD false)
+    return hit_values<false>(sc, none, orig, dir, raw.w, raw.x, raw.y, (int)(__float_as_uint(raw.z) & FLX_RAW_TRI) - 1);
+}
 
 struct Stack {
     uint32_t *lds;          // this thread's column: lds[level * TRACE_BLOCK]

@@ -184,7 +184,20 @@ __device__ __forceinline__ uint32_t material_list(int type, uint32_t separate)
 // more outcome of the one kind draw, sampled through the table `mesh` (flx_mesh_light.h) into the same light-sample columns, and collected on an implicit
 // hit with the MIS weight of that very pdf.  One instance, of the plain pass (k_logic<0, false, false, true>); with MESH = false every `if (MESH ...)`
 // folds away, the last argument is an empty struct (MeshArg, flx_launch.h), and the kernels are the shipped ones.
-template <int FUSE, bool RAW = false, bool REGROUP = false, bool MESH = false>
+// LAZY (option "lazy_hit_commit"): the FULL pass without the stores of the committed hit point and uv record -- 32 of the 211 bytes it writes per
+// path, which no kernel of the chain reads before the next extension launch overwrites the uv record (profiles/r06_logic_bytes.txt: they exist for whoever looks
+// in between).  They were stored because they could not be re-created: the material step replaces the ray the commit needs.  So the pass keeps the old ray, at no
+// traffic: it reads {ORIG, DIR} from st.rec[] and writes the new ray to the second pair st.other[], which the host makes the current one behind the launch
+// (api_wavefront.hip: runLogic).  A RAW record then simply stays RAW, and k_settle_hits (trace4r.hip) commits it from the old ray if anyone looks first.  Per lane class:
+//   T, C1   nothing stored for HITP / HITUV; a record that was not RAW holds what the eager pass would write back (T: dead, the path is regenerated)
+//   C2      as C1: the material kernel that serves the path commits its RAW record in registers as this pass does (material.hip), from the old origin in
+//           st.other[] and the old direction the DIR store has always carried for this class.  (Storing the two records for these 3 % of the lanes instead --
+//           partial lines -- was built and measured: slower in every round, profiles/lazy_commit_ab.txt)
+//   C0      in no extension queue, so nothing would ever overwrite its record: it stores the committed record as the eager pass does (a partial store, for a
+//           class real scenes do not have)
+// HITN is stored as ever: its flag word carries backfaceHit across the extension kernel (hit_keep_flags).  One instance, of the diffuse-inlining RAW pass; the
+// all-types instances re-read their own HITP / HITUV stores at the material step to stay at 5 waves per SIMD and keep them (launch_logic).
+template <int FUSE, bool RAW = false, bool REGROUP = false, bool MESH = false, bool LAZY = false>
 __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : LOGIC_MIN_BLOCKS) > 0 ? (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : LOGIC_MIN_BLOCKS) : 1) void k_logic(State st, Scene sc, Frame fr, flx_render_params p, LogicAux aux, Queues qs, uint32_t firstIteration, MeshArg<MESH> meshArg)
 {
     const MeshLights mesh = meshArg.get();
@@ -311,6 +324,7 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
         // Lane classes at the store phases:  T terminating (regenerated by the genRays that follows) | C1 continuing, BSDF inlined here |
         // C2 continuing, served by the material kernel that follows | C0 continuing, no queue (unknown BSDF type: the reference drops the path).
         constexpr bool FULL = LOGIC_FULL_STORES != 0 && RAW && FUSE != 0;
+        static_assert(!LAZY || (FULL && FUSE != USE_ALL && !REGROUP), "the lazy commit is a variant of the full-store pass that keeps its hit record in registers");
         // ---- REGEN (aux.regen): a terminating lane is regenerated HERE instead of by the genRays kernel of the chain -- its new origin, direction,
         // radiance + pixel and throughput + seed records ride on the full-line stores below, where genRays wrote four isolated 16-byte records per
         // path (partial sectors again: 0.15-0.19 ms per iteration for 1.8 M paths).  The one thing genRays has that a lane here has not is its index
@@ -476,7 +490,7 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
             }
             const float4 hp4 = mk4(hitP, hitT), huv4 = make_float4(hitUV.x, hitUV.y, __int_as_float(hitI), __int_as_float(hitMat));
             if (FUSE == USE_ALL) { wr4t(st.at(S_HITP, gid), hp4); wr4t(st.at(S_HITUV, gid), huv4); }      // (re-read at the material step below: keep the lines)
-            else { wr4(st.at(S_HITP, gid), hp4); wr4(st.at(S_HITUV, gid), huv4); }
+            else if (!LAZY || (!terminate && ml == 0u)) { wr4(st.at(S_HITP, gid), hp4); wr4(st.at(S_HITUV, gid), huv4); }      // (LAZY: the C0 lanes alone)
             wr4(st.at(S_HITN, gid), mk4u(hitN, (hflags & 1u) | (backface ? 2u : 0u)));
             wr4(st.at(S_SHO, gid), sho);
             wr4(st.at(S_SHD, gid), shd);
@@ -621,8 +635,8 @@ __global__ __launch_bounds__(LOGIC_BLOCK, (REGROUP ? LOGIC_REGROUP_MIN_BLOCKS : 
             wr4(st.at(S_LBSDF, gid), lbs);
             wr4(st.at(S_LT, gid), lt4);
             wr4(st.at(S_THR, gid), thr4);
-            wr4(st.at(S_ORIG, gid), or4);
-            wr4(st.at(S_DIR, gid), dr4);
+            wr4((LAZY ? st.other[0] : st.rec[S_ORIG]) + (size_t)gid, or4);      // (LAZY: the new ray goes to the second pair, the old one survives the pass)
+            wr4((LAZY ? st.other[1] : st.rec[S_DIR]) + (size_t)gid, dr4);
             splat();
         }
     }
@@ -798,7 +812,7 @@ uint32_t fused_queue_mask(int fuse)
 
 // fuse: 0 = the plain logic kernel | USE_DIFFUSE | USE_ALL  (diffuse + glossy was measured too: never the best of the three)
 void launch_logic(hipStream_t s, const State &st, const Queues &qs, const Scene &sc, const Frame &fr, const flx_render_params &p,
-                  uint8_t *member, uint32_t *blockCounts, uint32_t *queueAux, int firstIteration, int fuse, int raygenFirst, int extByPathId, int raw,
+                  uint8_t *member, uint32_t *blockCounts, uint32_t *queueAux, int firstIteration, int fuse, int raygenFirst, int extByPathId, int raw, int lazyCommit,
                   unsigned long long *lookback, uint32_t epoch, int regen, int regenAppendExt, uint32_t *error, int regroup, uint32_t parity, uint32_t numCUs,
                   const MeshLights *meshLights)
 {
@@ -815,7 +829,8 @@ void launch_logic(hipStream_t s, const State &st, const Queues &qs, const Scene 
     const dim3 g(blocks), b(LOGIC_BLOCK);
     switch (fuse) {
     case USE_DIFFUSE:
-        if (raw) hipLaunchKernelGGL((k_logic<USE_DIFFUSE, true>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
+        if (raw && lazyCommit && logic_can_lazy_commit(fuse)) hipLaunchKernelGGL((k_logic<USE_DIFFUSE, true, false, false, true>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
+        else if (raw) hipLaunchKernelGGL((k_logic<USE_DIFFUSE, true>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
         else hipLaunchKernelGGL((k_logic<USE_DIFFUSE, false>), g, b, 0, s, st, sc, fr, p, aux, qs, (uint32_t)firstIteration, MeshArg<false>());
         break;
     case USE_ALL:
@@ -836,6 +851,8 @@ void launch_logic(hipStream_t s, const State &st, const Queues &qs, const Scene 
 }
 // does this build regenerate terminating paths inside the fused RAW pass (LOGIC_FULL_STORES)?  (api.hip asks before it skips the genRays launch)
 int logic_can_regenerate() { return LOGIC_FULL_STORES != 0 ? 1 : 0; }
+// the RAW passes that have a LAZY instance: the diffuse-inlining one (the caller swaps the {ORIG, DIR} pairs behind exactly these launches)
+int logic_can_lazy_commit(int fuse) { return (LOGIC_FULL_STORES != 0 && fuse == USE_DIFFUSE) ? 1 : 0; }
 uint32_t logic_lookback_words(uint32_t numTasks) { return (numTasks + 63u) / 64u; }
 
 } // namespace flxd

@@ -12,6 +12,7 @@
 // the extension queue at a COMPUTED slot (extension base + lengths of the source queues appended earlier
 // + own index; no atomic -- see flx_device.h).
 #include "flx_bsdf.h"
+#include "flx_trace.h"          // hit_surface_raw: the commit of a RAW hit record the fused pass left to this kernel (LAZY)
 #include "flx_launch.h"
 
 namespace flxd {
@@ -23,7 +24,14 @@ namespace flxd {
 // earlierMask: the material queues appended to the extension queue before this one; FLX_NO_APPEND: the extension-queue entries of
 // this iteration's continuing paths exist already (written by the fused logic pass's scatter, logic.hip)
 #define FLX_NO_APPEND 0x80000000u
-template <int USE>
+// LAZY: the kernel behind a fused pass with "lazy_hit_commit" (logic.hip: LAZY), which does not store the committed hit point and uv record.  A path whose record
+// is still RAW is committed here in registers, as the pass does it -- the hit_values of flx_trace.h on the OLD ray, whose origin lies in st.other[] (flx_device.h: the
+// pair the pass read) and whose direction (with pathLen + 1) the pass has always left in DIR for these lanes -- and its normal, tangent-space mapped and flipped by the pass, comes from HITN as ever:
+// the same bits the committed records would hold.  Without the light quad (hit_surface_raw): a path in a material queue has continued, `logic` ends every path
+// whose commit met the quad, so this one's did not, and a quad that is not met changes nothing of the commit (with it the kernel needs 120 VGPRs instead of 88: a
+// wave per SIMD).  Nothing is stored for the record (k_settle_hits writes it if anyone looks first).  The kernels behind the separate `logic` only ever see
+// committed records (api_wavefront.hip: transition, commitRaw) and are the instances without.
+template <int USE, bool LAZY = false>
 __device__ __forceinline__ void material_body(const State &st, const Queues &qs, const Scene &sc, int queueId, uint32_t idx, uint32_t earlierMask)
 {
     const uint32_t qlen = qs.counters[queueId];
@@ -39,9 +47,16 @@ __device__ __forceinline__ void material_body(const State &st, const Queues &qs,
         const float4 sd = rd4t(st.at(S_SHD, gid));
         uint32_t seed = __float_as_uint(thr.w);
         SurfHit h; h.P = ld3(hp); h.N = ld3(hn); h.uv = mk2(huv.x, huv.y);
+        int matId = __float_as_int(huv.w);
+        if constexpr (LAZY) {
+            if (hit_is_raw(__float_as_uint(huv.z))) {
+                const HitVals hv = hit_surface_raw(sc, ld3(rd4(st.other[0] + (size_t)gid)), ld3(d4), huv);
+                h.P = hv.P; h.uv = mk2(hv.tu, hv.tv); matId = hv.matId;
+            }
+        }
         const bool backface = (__float_as_uint(hn.w) & 2u) != 0u;
         const f3 oldT = ld3(thr);
-        const MatStep o = material_step<USE>(sc, h, sc.materials[__float_as_int(huv.w)], backface, ld3(d4), ld3(sd), oldT, &seed);
+        const MatStep o = material_step<USE>(sc, h, sc.materials[matId], backface, ld3(d4), ld3(sd), oldT, &seed);
 
         wr4(st.at(S_LBSDF, gid), mk4(o.bsdfNEE, o.bsdfPdfW));
         wr4(st.at(S_LT, gid), mk4u(oldT, o.singular));
@@ -73,6 +88,7 @@ __global__ __launch_bounds__(MAT_BLOCK) void k_material(State st, Queues qs, Sce
 // (block ranges follow the queue lengths), so waves stay BSDF-uniform like in the per-queue kernels, but three
 // near-empty 4096-block launches per iteration disappear.
 // doneMask: queues the fused logic pass has already served (logic.hip); they only count as "appended earlier".
+template <bool LAZY>
 __global__ __launch_bounds__(MAT_BLOCK) void k_material_rest(State st, Queues qs, Scene sc, uint32_t doneMask)
 {
     const uint32_t noAppend = doneMask & FLX_NO_APPEND;
@@ -86,7 +102,7 @@ __global__ __launch_bounds__(MAT_BLOCK) void k_material_rest(State st, Queues qs
         uint32_t earlier = (1u << FLX_Q_DIFFUSE) | noAppend;
         for (int q = FLX_Q_GLOSSY; q <= FLX_Q_DELTA; q++) {
             const uint32_t nb = nbq[q - FLX_Q_GLOSSY];
-            if (b < nb) { material_body<USE_GLOSSY | USE_GGX_REFL | USE_GGX_REFR | USE_DELTA>(st, qs, sc, q, b * MAT_BLOCK + threadIdx.x, earlier); break; }
+            if (b < nb) { material_body<USE_GLOSSY | USE_GGX_REFL | USE_GGX_REFR | USE_DELTA, LAZY>(st, qs, sc, q, b * MAT_BLOCK + threadIdx.x, earlier); break; }
             b -= nb;
             earlier |= 1u << q;
         }
@@ -118,7 +134,7 @@ void launch_materials(hipStream_t s, const State &st, const Queues &qs, const Sc
         {   // glossy + ggxRefl + ggxRefr + delta (at most numTasks paths in total -> blocks + 4 partial blocks)
             uint32_t blocks = (st.numTasks + MAT_BLOCK - 1) / MAT_BLOCK + 4;
             if (blocks > MAT_GRID) blocks = MAT_GRID;
-            hipLaunchKernelGGL(k_material_rest, dim3(blocks), dim3(MAT_BLOCK), 0, s, st, qs, sc, 0u);
+            hipLaunchKernelGGL(k_material_rest<false>, dim3(blocks), dim3(MAT_BLOCK), 0, s, st, qs, sc, 0u);
         }
         (void)G; (void)RL; (void)RR; (void)DL; (void)D;            // the host records the appended queues (flx_wf_materials): lazy bump
     } else {
@@ -137,7 +153,8 @@ void launch_materials_after_fused(hipStream_t s, const State &st, const Queues &
     if ((doneMask & (all & ~(1u << FLX_Q_DIFFUSE))) != (all & ~(1u << FLX_Q_DIFFUSE))) {
         uint32_t blocks = (st.numTasks + MAT_BLOCK - 1) / MAT_BLOCK + 4;
         if (blocks > MAT_GRID) blocks = MAT_GRID;
-        hipLaunchKernelGGL(k_material_rest, dim3(blocks), dim3(MAT_BLOCK), 0, s, st, qs, sc, doneMask | FLX_NO_APPEND_);
+        // (the instance that can commit a RAW record: whether the pass in front left any is the records' own to say)
+        hipLaunchKernelGGL(k_material_rest<true>, dim3(blocks), dim3(MAT_BLOCK), 0, s, st, qs, sc, doneMask | FLX_NO_APPEND_);
     }
 }
 

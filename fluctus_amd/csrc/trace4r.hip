@@ -203,6 +203,26 @@ __global__ __launch_bounds__(256) void k_materialise(State st, Scene sc, flx_ren
     }
 }
 
+// The two records a fused RAW pass with "lazy_hit_commit" did not store (logic.hip: LAZY), for whoever wants to look before the next
+// extension launch of the intact chain overwrites them.  A path that pass served from a RAW record still has it; the ray the record was traced with
+// -- the one the pass committed it with, in registers -- lies untouched in st.other[] (flx_device.h), so the same function on the same inputs gives
+// the hit point and the uv record the eager pass would have stored.  Lane class by lane class (logic.hip, store phase A): a terminating lane and a
+// continuing one, BSDF inlined or not, all store {P, t} and {u, v, triangle, material} of that one commit -- the classes differ in the OTHER records --
+// and a lane without a queue has stored them itself; so the membership byte has nothing to add here.  pathLen is the pass's business and done; the
+// normal record, with the flag bits hit_keep_flags reads at the next commit, is stored by the pass as ever.
+__global__ __launch_bounds__(256) void k_settle_hits(State st, Scene sc, flx_render_params p)
+{
+    for (uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x; gid < st.numTasks; gid += gridDim.x * blockDim.x) {
+        const float4 raw = rd4t(st.at(S_HITUV, gid));
+        if (!hit_is_raw(__float_as_uint(raw.z))) continue;
+        const float4 o4 = rd4(st.other[0] + (size_t)gid);
+        const float4 d4 = rd4(st.other[1] + (size_t)gid);
+        const HitVals h = hit_values_raw(sc, p, ld3(o4), ld3(d4), raw);
+        wr4(st.at(S_HITP, gid), mk4(h.P, h.t));
+        wr4(st.at(S_HITUV, gid), make_float4(h.tu, h.tv, __int_as_float(h.tri), __int_as_float(h.matId)));
+    }
+}
+
 // The area-light quad of the ANY-HIT query, applied after the traversal for scenes that have one (two more triangle tests with their corner
 // set-up: inlined in k_trace4r they cost 30 VGPRs = three waves per SIMD; as a streaming pass ~40 B per ray).  The quad blocks like any
 // triangle (src/wf_shadowrays.cl:32-33); the reference tests it first, the result is the OR either way.  (The closest-hit query's implicit
@@ -262,7 +282,12 @@ void launch_materialise(hipStream_t s, const State &st, const Scene &sc, const f
     hipLaunchKernelGGL(k_materialise, dim3(numCUs * 8), dim3(256), 0, s, st, sc, p);
 }
 
-void launch_shadow4r(hipStream_t s, const State &st, const Queues &qs, const Scene &sc, const flx_render_params &p, uint32_t *spill, uint32_t numCUs, int refill, uint32_t *cursor)
+void launch_settle_hits(hipStream_t s, const State &st, const Scene &sc, const flx_render_params &p, uint32_t numCUs)
+{
+    hipLaunchKernelGGL(k_settle_hits, dim3(numCUs * 8), dim3(256), 0, s, st, sc, p);
+}
+
+void launch_shadow4r(hipStream_t s,const State &st, const Queues &qs, const Scene &sc, const flx_render_params &p, uint32_t *spill, uint32_t numCUs, int refill, uint32_t *cursor)
 {
     const int refillMin = (refill & 0xFF) ? (refill & 0xFF) : 1, waitMax = ((refill >> 8) & 0xFF) ? ((refill >> 8) & 0xFF) : 64;
     static int occ[2] = {0, 0};
