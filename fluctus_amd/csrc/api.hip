@@ -69,24 +69,74 @@ static bool refill_value_ok(int v) { return v == 0 || (v > 0 && (v & 0xFF) >= 1 
 //   kitchen 4951-5249 / 5208-5489 / 4800-4840     conference 4931-4996 / 5017-5019 / 4590-4720     courtyard 2165 / 2181 / 1998-2076
 // (an earlier build with a static share of blocks per wave preferred the serial schedule for the courtyard, whose tree comes from HBM; with
 // balanced waves it does not).  Options "overlap" and "refill_shadow" override; -1 = these defaults.
+// The thread-per-ray any-hit kernel of the second stream is itself a split launch where the light makes its rays long-tailed -- a budgeted pass, then ONE
+// persistent kernel over the suspended rays only, which retires progressively beside the closest-hit kernel like the thread-per-ray waves do: that
+// choice depends on the render parameters, not on the scene, and is made at the launch (effectiveSplit, below).
 void flxd::pickSchedule(flx_ctx *c)
 {
     c->overlap = c->overlapOpt >= 0 ? c->overlapOpt : 2;
     c->refillShadow = c->refillShadowOpt >= 0 ? c->refillShadowOpt : 0;
 }
 
-// Device buffers of the two features that are off by default, allocated when the option is first switched on (round 5's advisor: at 16 M paths the
-// continuation records alone were 670 MB that the default configuration never touched) and kept until the context goes away.
-static int optionBuffers(flx_ctx *c, bool split, bool regen)
+// The thread-per-ray any-hit kernel itself is one launch or a SPLIT one (trace4.hip: launch_shadow4_split): a pass over the queue under a
+// budget of node visits, then the suspended rays in persistent waves that refill from the continuation records.  Which, is not the scene's business but the
+// light's, and the render parameters can change from launch to launch, so the choice is made from them: where every shadow ray runs toward an environment
+// light -- the condition under which launch_shadow4 takes the far -> near visit order -- the rays are unbounded and their lengths long-tailed, and the split
+// pays; toward an area light they are short and it does not.  Option "shadow_split" overrides, 0 included; -1 = this choice.  How K was chosen and what
+// it is worth: DESIGN.md 4.8.1, profiles/shadow_resume_ab.txt.
+#define FLX_SPLIT_DEFAULT 8
+int flxd::effectiveSplit(const flx_ctx *c)
+{
+    if (c->shadowSplitOpt >= 0) return c->shadowSplitOpt;
+    return (c->haveParams && c->params.useEnvMap && !c->params.useAreaLight && !c->splitAllocFailed) ? FLX_SPLIT_DEFAULT : 0;
+}
+// ... and what the next flx_wf_shadow launches: the split exists for the thread-per-ray kernel on the 4-wide tree only -- not under "refill_shadow", the
+// binary tree, a scene without a usable wide tree, or the counting kernels.  This is what flx_get_option("shadow_split") reports.
+int flxd::splitNow(const flx_ctx *c)
+{
+    const bool wideKnown = c->sc.bnodes != nullptr;      // (before the first upload nothing says the wide tree is unusable)
+    return (c->shadowTree == 4 && (c->wideOK || !wideKnown) && c->refillShadow == 0 && !c->statsOn) ? effectiveSplit(c) : 0;
+}
+// The records of the split the next launch will make, allocated where the choice can change -- flx_set_params, flx_upload_scene, the option -- so that no
+// launch call allocates or waits (flx_wf_shadow calls it again for the paths that change the choice elsewhere: it then finds them).  When the library's OWN
+// choice does not fit into device memory the choice becomes 0 for this context and the read-only option "shadow_split_fallback" says so; an explicit value fails.
+int flxd::splitPrepare(flx_ctx *c)
+{
+    const int split = splitNow(c);
+    if (split <= 0 || (c->splitRecA && ((split >> 8) == 0 || c->splitRecB))) return 0;
+    if (splitBuffers(c, (split >> 8) > 0)) {
+        if (c->shadowSplitOpt >= 0) return 1;
+        c->splitAllocFailed = true; c->err.clear();
+    }
+    return 0;
+}
+
+// The continuation records of the split any-hit launch, allocated on first use and kept until the context goes away: the counters and the first set (64 B
+// for numTasks / 2 records: ~540 MB at 16 M paths), and the second set (numTasks / 8 records) only when a launch has a second budget.
+int flxd::splitBuffers(flx_ctx *c, bool second)
 {
     HIPCHK(c, hipSetDevice(c->device));
-    if (split && !c->splitRecA) {
-        uint32_t *cnt = nullptr; uint4 *a = nullptr, *b = nullptr;
-        if (dalloc(c, c->fixedAllocs, &cnt, shadow_split_count_words()) || dalloc(c, c->fixedAllocs, &a, (size_t)c->splitCapA * shadow_split_lists() * 4) ||
-            dalloc(c, c->fixedAllocs, &b, (size_t)c->splitCapB * shadow_split_lists() * 4)) { c->err = "flx_set_option(shadow_split): out of device memory for the continuation records"; return 1; }
+    if (!c->splitRecA) {
+        uint32_t *cnt = nullptr; uint4 *a = nullptr;
+        if (dalloc(c, c->fixedAllocs, &cnt, shadow_split_count_words()) || dalloc(c, c->fixedAllocs, &a, (size_t)c->splitCapA * shadow_split_lists() * 4)) {
+            (void)hipGetLastError(); c->err = "shadow_split: out of device memory for the continuation records"; return 1;
+        }
         HIPCHK(c, hipMemsetAsync(cnt, 0, (size_t)shadow_split_count_words() * 4, c->stream));
-        c->splitCounts = cnt; c->splitRecA = a; c->splitRecB = b;
+        HIPCHK(c, hipStreamSynchronize(c->stream));      // (once per context; the launch that follows may be on the second stream)
+        c->splitCounts = cnt; c->splitRecA = a;
     }
+    if (second && !c->splitRecB) {
+        uint4 *b = nullptr;
+        if (dalloc(c, c->fixedAllocs, &b, (size_t)c->splitCapB * shadow_split_lists() * 4)) { (void)hipGetLastError(); c->err = "shadow_split: out of device memory for the continuation records"; return 1; }
+        c->splitRecB = b;
+    }
+    return 0;
+}
+
+// Device buffers of a feature that is off by default, allocated when the option is first switched on and kept until the context goes away.
+static int optionBuffers(flx_ctx *c, bool regen)
+{
+    HIPCHK(c, hipSetDevice(c->device));
     if (regen && !c->lookback) {
         unsigned long long *lb = nullptr;
         if (dalloc(c, c->fixedAllocs, &lb, (size_t)logic_lookback_words(c->numTasks))) { c->err = "flx_set_option(regen): out of device memory for the look-back words"; return 1; }
@@ -237,6 +287,7 @@ int flx_set_params(flx_ctx *c, const void *p240)
     NEED(c, c->params.width > 0 && c->params.height > 0, "flx_set_params: zero-sized framebuffer");
     if (c->params.width != oldW || c->params.height != oldH) { c->ad.state.dropped(); c->temporal.state.imageResized(); }      // the list of active pixels and the mark index the old image
     c->haveParams = true;
+    if (splitPrepare(c)) return 1;                       // the light decides whether the any-hit launch splits (effectiveSplit)
     return allocFrame(c);
 }
 
@@ -363,7 +414,7 @@ int flx_set_option(flx_ctx *c, const char *name, int value)
     if (name && strcmp(name, "xcd_remap") == 0) { c->xcdRemap = value; return 0; }
     if (name && strcmp(name, "fuse") == 0 && (value == 0 || value == 1)) { c->fuse = value; return 0; }
     if (name && strcmp(name, "ext_order") == 0 && value >= 0 && value <= 2) { c->extOrder = value; return 0; }
-    if (name && strcmp(name, "regen") == 0 && (value == 0 || value == 1)) { if (value && optionBuffers(c, false, true)) return 1; c->regenOpt = value; return 0; }
+    if (name && strcmp(name, "regen") == 0 && (value == 0 || value == 1)) { if (value && optionBuffers(c, true)) return 1; c->regenOpt = value; return 0; }
     if (name && strcmp(name, "regen_prep") == 0 && (value == 0 || value == 1)) { c->prepOpt = value; return 0; }
     // 1: the fused RAW pass leaves the committed hit point / uv record to k_settle_hits | 0: it stores them itself.  (CALL_PEEK above has settled what was pending.)
     if (name && strcmp(name, "lazy_hit_commit") == 0 && (value == 0 || value == 1)) { c->lazyCommitOpt = value; return 0; }
@@ -410,7 +461,14 @@ int flx_set_option(flx_ctx *c, const char *name, int value)
     if (name && strcmp(name, "refill_extend") == 0 && refill_value_ok(value)) { ENTER(c, CALL_OBSERVE); c->refillExt = value; return 0; }
     if (name && strcmp(name, "refill_shadow") == 0 && (value == -1 || refill_value_ok(value))) { ENTER(c, CALL_OBSERVE); c->refillShadowOpt = value; pickSchedule(c); return 0; }
     if (name && (strcmp(name, "refill_extend") == 0 || strcmp(name, "refill_shadow") == 0)) { c->err = "flx_set_option: refill value must be 0 or refillMin (1..64) | waitMax (0..64) << 8"; return 1; }
-    if (name && strcmp(name, "shadow_split") == 0 && value >= 0 && (value & 0xFF) <= 255 && (value >> 8) <= 255 && ((value & 0xFF) > 0 || value == 0)) { ENTER(c, CALL_OBSERVE); if (value && optionBuffers(c, true, false)) return 1; c->shadowSplit = value; return 0; }
+    // (-1 = the library's choice: effectiveSplit.  An explicit value allocates its records now, so that the caller learns here when they do not fit)
+    if (name && strcmp(name, "shadow_split") == 0 && (value == -1 || (value >= 0 && (value >> 8) <= 255 && ((value & 0xFF) > 0 || value == 0)))) {
+        ENTER(c, CALL_OBSERVE);
+        if (value > 0 && splitBuffers(c, (value >> 8) > 0)) return 1;
+        c->shadowSplitOpt = value;
+        return splitPrepare(c);
+    }
+    if (name && strcmp(name, "shadow_resume") == 0 && (value == 0 || value == 1)) { ENTER(c, CALL_OBSERVE); c->shadowResume = value; return 0; }
     if (name && strcmp(name, "shadow_split_limit") == 0 && value >= 0) { ENTER(c, CALL_OBSERVE); c->splitLimit = (uint32_t)value; return 0; }
     if (name && strcmp(name, "eager_bump") == 0 && (value == 0 || value == 1)) { c->eagerBump = value; return 0; }
     if (name && strcmp(name, "node_layout") == 0 && (value == 0 || value == 1)) { c->nodeLayout = value; return 0; }
@@ -428,10 +486,21 @@ int flx_get_option(flx_ctx *c, const char *name, int *value)
     NEED(c, name && value, "flx_get_option: null");
     const struct { const char *n; int v; } tab[] = {
         {"xcd_remap", c->xcdRemap}, {"fuse", c->fuse}, {"overlap", c->overlap}, {"shadow_tree", c->shadowTree}, {"extend_tree", c->extendTree},
-        {"denoiser", c->denoiser}, {"moments", c->moments}, {"motion_history", c->motionHistory}, {"deform_history", c->deformHistory},{"mesh_lights", c->ml.state.on ? 1 : 0}, {"mesh_lights_wavefront", c->ml.state.wavefront ? 1 : 0}, {"eager_bump", c->eagerBump}, {"node_layout", c->nodeLayout}, {"fuse_set", c->fuseSet}, {"ext_order", c->extOrder}, {"regen", c->regenOpt}, {"regroup", c->regroup}, {"regen_prep", c->prepOpt}, {"lazy_hit_commit", c->lazyCommitOpt}, {"refill_extend", c->refillExt}, {"refill_shadow", c->refillShadow}, {"shadow_split", c->shadowSplit}, {"fused_queue_mask", (int)fused_queue_mask(fuseSetNow(c))}, {"fuse_set_now", fuseSetNow(c)}};
+        {"denoiser", c->denoiser}, {"moments", c->moments}, {"motion_history", c->motionHistory}, {"deform_history", c->deformHistory},{"mesh_lights", c->ml.state.on ? 1 : 0}, {"mesh_lights_wavefront", c->ml.state.wavefront ? 1 : 0}, {"eager_bump", c->eagerBump}, {"node_layout", c->nodeLayout}, {"fuse_set", c->fuseSet}, {"ext_order", c->extOrder}, {"regen", c->regenOpt}, {"regroup", c->regroup}, {"regen_prep", c->prepOpt}, {"lazy_hit_commit", c->lazyCommitOpt}, {"refill_extend", c->refillExt}, {"refill_shadow", c->refillShadow}, {"shadow_split", splitNow(c)}, {"shadow_split_fallback", c->splitAllocFailed ? 1 : 0}, {"shadow_resume", c->shadowResume},{"fused_queue_mask", (int)fused_queue_mask(fuseSetNow(c))}, {"fuse_set_now", fuseSetNow(c)}};
     for (const auto &t : tab) if (strcmp(name, t.n) == 0) { *value = t.v; return 0; }
     if (strcmp(name, "phase") == 0) { *value = phaseCode(c); return 0; }
     if (strcmp(name, "wide_far") == 0) { *value = wideFar(c); return 0; }
+    if (strcmp(name, "shadow_split_suspended") == 0) {       // rays the last split launch suspended: its counter set, read behind the stream (the main stream has joined the second one)
+        ENTER(c, CALL_OBSERVE);
+        *value = 0;
+        if (!c->splitLaunched) return 0;
+        std::vector<uint32_t> host(shadow_split_count_words());
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(host.data(), c->splitCounts, host.size() * 4, hipMemcpyDeviceToHost));
+        *value = (int)shadow_split_suspended(host.data(), c->splitParity - 1u, c->splitCapA, c->splitLastLimit);
+        return 0;
+    }
     c->err = std::string("flx_get_option: unknown option ") + name;
     return 1;
 }

@@ -273,7 +273,8 @@ int flx_upload_scene(flx_ctx *c, const void *trisv, size_t ntris, const uint32_t
     c->wideInfo[0] = (uint32_t)wide.nodes.size(); c->wideInfo[1] = (uint32_t)(wide.leafdata.size()); c->wideInfo[2] = wide.maxStack; c->wideInfo[3] = wide.nested ? 1u : 0u;
     c->wideInfo[4] = binDepth; c->wideInfo[5] = spillLevels; c->wideInfo[6] = (uint32_t)bnodes.size(); c->wideInfo[7] = wide.maxLeafCount;
     pickSchedule(c);
-    return meshLightsSync(c);                             // option "mesh_lights": the table of the new scene, on the stream
+    if (splitPrepare(c)) return 1;                        // (wideOK is known now: the records of the split any-hit launch, api.hip)
+    return meshLightsSync(c);                            // option "mesh_lights": the table of the new scene, on the stream
 }
 
 int flx_upload_envmap(flx_ctx *c, const float *rgb, int w, int h, const float *prob, const int *alias, const float *pdf)

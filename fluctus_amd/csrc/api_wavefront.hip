@@ -188,6 +188,9 @@ int flx_wf_shadow(flx_ctx *c)
     READY(c, CALL_SHADOW);
     hipStream_t s = c->stream;
     if (overlapped) { s = c->stream2; HIPCHK(c, hipStreamWaitEvent(s, early ? c->evPostLogic : c->evPreExt, 0)); }
+    // the split launch of the thread-per-ray any-hit kernel (api.hip: splitNow); its records exist since flx_set_params / flx_upload_scene / the option
+    if (splitPrepare(c)) return 1;
+    const int split = splitNow(c);
     hipEvent_t earlyStart = nullptr;
     if ((c->profile == 1 || c->profile == 2) && early) { earlyStart = getEvent(c); (void)hipEventRecord(earlyStart, s); }
     {
@@ -207,8 +210,11 @@ int flx_wf_shadow(flx_ctx *c)
             launch_shadow4(s, c->st, q2, c->sc, c->params, spill, nullptr);
         }
 #endif
-        else if (c->shadowTree == 4 && c->wideOK && c->shadowSplit > 0 && !c->statsOn)
-            launch_shadow4_split(s, c->st, c->qs, c->sc, c->params, spill, c->splitCounts, c->splitParity++, c->splitRecA, c->splitCapA, c->splitRecB, c->splitCapB, c->shadowSplit & 0xFF, c->shadowSplit >> 8, c->splitLimit);
+        else if (split > 0) {
+            launch_shadow4_split(s, c->st, c->qs, c->sc, c->params, spill, c->splitCounts, c->splitParity++, c->splitRecA, c->splitCapA, c->splitRecB, c->splitCapB, split & 0xFF, split >> 8, c->splitLimit,
+                                 c->shadowResume, (uint32_t)c->numCUs);
+            c->splitLastLimit = c->splitLimit; c->splitLaunched = true;
+        }
         else if (c->shadowTree == 4 && c->wideOK) launch_shadow4(s, c->st, c->qs, c->sc, c->params, spill, c->statsOn ? c->stats : nullptr);
         else launch_shadow(s, c->st, c->qs, c->sc, c->params, spill, c->statsOn ? c->stats : nullptr, c->xcdRemap);
     }

@@ -115,7 +115,12 @@ struct flx_ctx {
     int refillShadowOpt = -1;                   // option "refill_shadow": -1 = the default (off), else as set
     // tail splitting of the thread-per-ray any-hit kernel (trace4.hip: k_shadow4s): budget of the pass over the queue | budget of a second pass << 8
     // (0 = the second pass finishes every ray); 0 = off (k_shadow4).  Continuation records: 64 B each, in sub-lists of splitCapA / splitCapB slots (numTasks / 2 and / 8 in all).
-    int shadowSplit = 0;
+    // Option "shadow_split": -1 = the library's choice (the initial value), made at the launch from the render parameters -- FLX_SPLIT_DEFAULT where the
+    // far -> near order runs (shadow rays toward an environment light: the long-tailed population), 0 elsewhere: effectiveSplit().  An explicit value holds.
+    int shadowSplitOpt = -1;
+    int shadowResume = 1;                       // option "shadow_resume": the suspended rays of a split launch WITHOUT second budget are finished 1 by persistent waves that refill from the records (trace4r.hip: k_trace4r_resume) | 0 one lane per record slot
+    bool splitAllocFailed = false;              // the records of the library's own choice did not fit: the choice is 0 for this context
+    uint32_t splitLastLimit = 0; bool splitLaunched = false;      // read-only option "shadow_split_suspended": the slot limit of the last split launch, and that there was one
     uint32_t splitParity = 0;                   // counter set of the next split launch (trace4.hip: launch_shadow4_split)
     uint32_t splitLimit = 0;                    // test hook (option shadow_split_limit): use only this many slots per sub-list (0 = all), to reach the full-list path
     uint32_t *splitCounts = nullptr; uint4 *splitRecA = nullptr, *splitRecB = nullptr; uint32_t splitCapA = 0, splitCapB = 0;
@@ -268,4 +273,8 @@ int motionTables(flx_ctx *c);                       // api_refit.hip: objectOfTr
 int meshLightsSync(flx_ctx *c);                     // api_mesh_light.hip: (re)build the table of emissive triangles on the stream when the option is on and it is stale
 int wideFar(const flx_ctx *c);                      // api_refit.hip: 1 when sc.wideClamp is the far clamp (read-only option "wide_far")
 void pickSchedule(flx_ctx *c);                      // api.hip: the effective overlap / refill_shadow (options, flx_upload_scene)
+int effectiveSplit(const flx_ctx *c);               // api.hip: "shadow_split" under the current render parameters (option or the library's choice)
+int splitNow(const flx_ctx *c);                     // api.hip: ... and what the next flx_wf_shadow really launches with it (0 where another any-hit kernel runs)
+int splitPrepare(flx_ctx *c);                       // api.hip: allocate the records of that launch, or fall back to 0 when the library's own choice does not fit
+int splitBuffers(flx_ctx *c, bool second);          // api.hip: the continuation records, allocated on first use (the second set only for a second budget)
 }

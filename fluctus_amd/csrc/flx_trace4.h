@@ -244,6 +244,9 @@ __device__ __forceinline__ bool traverse4(const Scene &sc, WStack &stk, f3 orig,
 // Returns 0 not occluded | 1 occluded | 2 suspended (sp entries on the stack, the next node on top).  maxKeep = entries a continuation record holds;
 // a ray whose stack is deeper (or partly paged out) simply keeps going.
 #define FLX_SPLIT_KEEP 14
+// the continuation records lie in FLX_SPLIT_LISTS sub-lists with a counter each (trace4.hip: k_shadow4s writes them, trace4r.hip: k_trace4r_resume reads them)
+#define FLX_SPLIT_LISTS 256
+#define FLX_SPLIT_COUNT_STRIDE 16          // words between two sub-list counters
 template <int ANY_ORDER>
 __device__ __forceinline__ int traverse4_any_budget(const Scene &sc, WStack &stk, const WRay &r, float tmax, int &sp, uint32_t cur, int budget)
 {

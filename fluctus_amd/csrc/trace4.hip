@@ -108,8 +108,7 @@ __global__ __launch_bounds__(WIDE_BLOCK, WIDE_MIN_WAVES) void k_shadow4(State st
 // (flx_device.h), and with nearly every wave of the first pass suspending a ray that alone was 1 ms per launch (first version, round 5).  The record
 // array is cut into FLX_SPLIT_LISTS sub-lists with a counter each, 64 B apart; wave w appends to list w mod FLX_SPLIT_LISTS, the next pass runs one
 // lane per record SLOT of every sub-list and the lanes beyond a list's count leave at once.  Without `out` (last pass) the budget is unlimited.
-#define FLX_SPLIT_LISTS 256
-#define FLX_SPLIT_COUNT_STRIDE 16          // words between two sub-list counters
+// (FLX_SPLIT_LISTS, FLX_SPLIT_COUNT_STRIDE: flx_trace4.h)
 struct SplitAux {
     const uint32_t *inCount; const uint4 *inRec; uint32_t inSubCap, inLimit;      // !FIRST: records to resume: FLX_SPLIT_LISTS sub-lists of inSubCap slots, inLimit of them usable
     uint32_t *outCount; uint4 *outRec; uint32_t outSubCap, outLimit;     // where suspended rays go (nullptr: none may suspend); outLimit <= outSubCap slots per list are used
@@ -190,8 +189,12 @@ __global__ __launch_bounds__(WIDE_BLOCK, WIDE_MIN_WAVES) void k_shadow4s(State s
 // counts: 2 SETS of 2 x FLX_SPLIT_LISTS counters, FLX_SPLIT_COUNT_STRIDE words apart; recA / recB: FLX_SPLIT_LISTS x subCapA / subCapB records of 64 B.
 // The launches alternate between the two counter sets (`parity`): the first pass zeroes the OTHER set -- the previous launch's, complete in stream
 // order -- for the next launch.  (A hipMemsetAsync in front of the first pass was a fill kernel of 0.12 ms on the shadow stream beside genRays.)
+// resume (with k2 == 0 only): the suspended rays are finished by persistent waves that refill from the records (trace4r.hip: k_trace4r_resume) instead of
+// one lane per record slot -- pass 2 runs over exactly the rays whose lengths differ most, thread-per-ray it is a latency chain as long as the longest of
+// them at a sixth of the lanes.  With a second budget the chain is the three thread-per-record launches whatever `resume` says; recB is needed only then.
 void launch_shadow4_split(hipStream_t s, const State &st, const Queues &qs, const Scene &sc, const flx_render_params &p, uint32_t *spill,
-                          uint32_t *counts, uint32_t parity, uint4 *recA, uint32_t subCapA, uint4 *recB, uint32_t subCapB, int k1, int k2, uint32_t limit)
+                          uint32_t *counts, uint32_t parity, uint4 *recA, uint32_t subCapA, uint4 *recB, uint32_t subCapB, int k1, int k2, uint32_t limit,
+                          int resume, uint32_t numCUs)
 {
     const uint32_t blocks = (st.numTasks + WIDE_BLOCK - 1) / WIDE_BLOCK;
     TraceAux aux{spill, blocks * WIDE_BLOCK, nullptr};
@@ -203,7 +206,11 @@ void launch_shadow4_split(hipStream_t s, const State &st, const Queues &qs, cons
     const SplitAux a2{cA, recA, subCapA, limA, k2 > 0 ? cB : nullptr, k2 > 0 ? recB : nullptr, subCapB, limB, k2, nullptr};
     const SplitAux a3{cB, recB, subCapB, limB, nullptr, nullptr, 0u, 0u, 0, nullptr};
     const dim3 b(WIDE_BLOCK), g1(blocks), g2(FLX_SPLIT_LISTS * (subCapA / WIDE_BLOCK)), g3(FLX_SPLIT_LISTS * (subCapB / WIDE_BLOCK));
-    if (farFirst) {
+    if (resume && k2 == 0) {
+        if (farFirst) hipLaunchKernelGGL((k_shadow4s<1, true>), g1, b, 0, s, st, qs, sc, p, aux, a1);
+        else hipLaunchKernelGGL((k_shadow4s<0, true>), g1, b, 0, s, st, qs, sc, p, aux, a1);
+        launch_shadow4_resume(s, st, qs, sc, p, spill, numCUs, cA, recA, subCapA, limA);
+    } else if (farFirst) {
         hipLaunchKernelGGL((k_shadow4s<1, true>), g1, b, 0, s, st, qs, sc, p, aux, a1);
         hipLaunchKernelGGL((k_shadow4s<1, false>), g2, b, 0, s, st, qs, sc, p, aux, a2);
         if (k2 > 0) hipLaunchKernelGGL((k_shadow4s<1, false>), g3, b, 0, s, st, qs, sc, p, aux, a3);
@@ -215,6 +222,16 @@ void launch_shadow4_split(hipStream_t s, const State &st, const Queues &qs, cons
 }
 uint32_t shadow_split_lists() { return FLX_SPLIT_LISTS; }
 uint32_t shadow_split_count_words() { return 2u * 2u * FLX_SPLIT_LISTS * FLX_SPLIT_COUNT_STRIDE; }
+// rays the split launch with `parity` suspended in its first pass, from a host copy of the counters: a list's count runs past its usable slots when it
+// is full (those rays finished in pass 1), so each is cut at the limit the launch used
+uint32_t shadow_split_suspended(const uint32_t *hostCounts, uint32_t parity, uint32_t subCapA, uint32_t limit)
+{
+    const uint32_t *cA = hostCounts + (parity & 1u) * 2u * FLX_SPLIT_LISTS * FLX_SPLIT_COUNT_STRIDE;
+    const uint32_t limA = limit && limit < subCapA ? limit : subCapA;
+    uint32_t n = 0;
+    for (uint32_t l = 0; l < FLX_SPLIT_LISTS; l++) { const uint32_t v = cA[l * FLX_SPLIT_COUNT_STRIDE]; n += v < limA ? v : limA; }
+    return n;
+}
 
 void launch_extend4(hipStream_t s, const State &st, const Queues &qs, const Scene &sc, const flx_render_params &p, uint32_t *spill, unsigned long long *stats)
 {

@@ -46,16 +46,35 @@ unsigned long long *g_lab_rstats = nullptr;
 #define RSTAT(k, v) do { } while (0)
 #endif
 
-template <bool ANY_HIT, int ANY_ORDER>
-__global__ __launch_bounds__(WIDE_BLOCK, WIDE_R_MIN_WAVES) void k_trace4r(State st, Queues qs, Scene sc, flx_render_params p, TraceAux aux, int refillMin, int waitMax, uint32_t *cursor)
+// RESUME (any hit only): the items a wave hands to its lanes are the CONTINUATION RECORDS the budgeted thread-per-ray pass left (trace4.hip: k_shadow4s<ORDER, true>;
+// launch_shadow4_split), not queue entries.  What changes is where the work comes from and how a refilled lane starts -- the loop of node rounds, leaf
+// phase and refill is the one below, untouched:
+//   * Work.  The records lie in FLX_SPLIT_LISTS sub-lists with a count each.  A static share: wave w serves list w mod FLX_SPLIT_LISTS (the list the pass-1
+//     waves of its own XCD appended to) and, of that list's 64-record chunks, number w / FLX_SPLIT_LISTS and every (waves of that list)-th after it; the count is read
+//     ONCE.  No atomic at all: one ticket per possible chunk would be ~131 k atomics per launch at 16 M paths on words that serve ~88 (one) or ~14 (eight) per us.
+//     Measured: this static share only; per-XCD cursors over the non-empty chunks were not built -- at the default budget a wave gets one or two chunks,
+//     so there is little to balance (profiles/shadow_resume_ab.txt).
+//   * A refilled lane reads its record (4 x 16 B) and the ray {SHO, SHD} of queue[record.idx] -- the path id was fetched for the whole chunk when the chunk
+//     was taken, as `gidBlk` is for queue blocks, so the record and the ray arrive in ONE round trip --, restores sp and the FLX_SPLIT_KEEP stack words into its
+//     LDS column, runs WRay::setup and pops the node it stood on.  A record exists only for an unpaged stack (flx_trace4.h: traverse4_any_budget), so base = 0 and
+//     whatever pages out later goes to the lane's own spill column.
+// The ray's own sequence of visits and its arithmetic stay k_shadow4's, cut at the suspension: shadowRayBlocked is bit-identical (tests/test_gpu_shadow_resume.py).
+struct ResumeAux { const uint32_t *count; const uint4 *rec; uint32_t subCap, limit; };
+
+template <bool ANY_HIT, int ANY_ORDER, bool RESUME>
+__device__ __forceinline__ void trace4r_waves(const State &st, const Queues &qs, const Scene &sc, const flx_render_params &p, const TraceAux &aux, int refillMin, int waitMax, uint32_t *cursor, const ResumeAux &ra)
 {
+    static_assert(!RESUME || ANY_HIT, "only the any-hit query suspends");
     __shared__ uint32_t s_stack[WIDE_LDS_LEVELS * WIDE_BLOCK];
 #ifdef FLX_LAB_RSTATS
     unsigned long long *rstats = aux.stats; unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
 #endif
     const int QID = ANY_HIT ? FLX_Q_SHADOW : FLX_Q_EXTENSION;
-    const uint32_t qlen = ANY_HIT ? qs.counters[QID] : ext_len(qs);
+    // RESUME: "the queue" is this wave's sub-list of records -- qlen its (usable) count, a block one chunk of 64 records
+    const uint32_t rList = blockIdx.x & (FLX_SPLIT_LISTS - 1u);
+    const uint32_t qlen = RESUME ? min(ra.count[rList * FLX_SPLIT_COUNT_STRIDE], ra.limit) : ANY_HIT ? qs.counters[QID] : ext_len(qs);
     const uint32_t *queue = qs.q[QID];
+    const uint4 *recs = RESUME ? ra.rec + (size_t)rList * ra.subCap * 4 : nullptr;
     const uint32_t nblk = (qlen + 63u) >> 6;
     // Which 64-ray block next.  Rays differ in cost by an order of magnitude (sky vs. foliage), so a static share per wave (blocks w, w + G, ...)
     // leaves wave slots idle towards the end of the launch (courtyard: 1.60 -> 1.50 ms with this; kitchen and conference unchanged).  Blocks
@@ -79,12 +98,22 @@ __global__ __launch_bounds__(WIDE_BLOCK, WIDE_R_MIN_WAVES) void k_trace4r(State 
             ticket = issue_fetch();
         }
     };
-    uint32_t blk = resolve(issue_fetch()), pos = 0;  // wave-uniform: current block, rays of it already handed out
+    // RESUME: the static share (above): chunks blockIdx.x / LISTS, + rStep, ... of list rList; the grid is at least FLX_SPLIT_LISTS waves (launch_shadow4_resume)
+    const uint32_t rStep = RESUME ? (gridDim.x - rList + FLX_SPLIT_LISTS - 1u) / FLX_SPLIT_LISTS : 0u;
+    // the path ids of a block, one per lane, loaded when the block is taken: a refill then gets its ids from registers (one
+    // cross-lane read) and waits for ONE memory round trip -- the rays -- instead of two.  (RESUME: through the record's queue index, which pass 1 took below the
+    // queue's length; the clamp only keeps a foreign record inside the queue's allocation)
+    auto block_ids = [&](uint32_t b) -> uint32_t {
+        const uint32_t item = min((b << 6) + threadIdx.x, qlen - 1u);
+        return RESUME ? queue[min(recs[(size_t)item * 4].x, st.numTasks - 1u)] : queue[item];
+    };
+    uint32_t blk = RESUME ? blockIdx.x / FLX_SPLIT_LISTS : resolve(issue_fetch()), pos = 0;  // wave-uniform: current block, rays of it already handed out
     if (blk >= nblk) return;
-    uint32_t nextTicket = issue_fetch();             // (in flight while the current block is traced)
-    // the path ids of the current block, one per lane, loaded when the block is taken: a refill then gets its ids from registers (one
-    // cross-lane read) and waits for ONE memory round trip -- the rays -- instead of two
-    uint32_t gidBlk = queue[min((blk << 6) + threadIdx.x, qlen - 1u)];
+    // (RESUME: the grid is padded to one wave per sub-list, which can be more waves than the spill area has 64-lane columns; such a wave's list is empty --
+    //  lists are filled by pass-1 waves, of which there are no more than columns -- and should that ever change it must not touch memory it does not own)
+    if (RESUME && (blockIdx.x + 1u) * WIDE_BLOCK > aux.totalThreads) return;
+    uint32_t nextTicket = RESUME ? 0u : issue_fetch();   // (in flight while the current block is traced)
+    uint32_t gidBlk = block_ids(blk);
 
     WStack stk;
     stk.lds = s_stack + threadIdx.x;
@@ -120,15 +149,27 @@ __global__ __launch_bounds__(WIDE_BLOCK, WIDE_R_MIN_WAVES) void k_trace4r(State 
                     gid = cand;
                     const float4 o4 = rd4(st.at(ANY_HIT ? S_SHO : S_ORIG, gid));
                     const float4 d4 = rd4(st.at(ANY_HIT ? S_SHD : S_DIR, gid));
+                    if (RESUME) {
+                        // the record: {queue index, sp, FLX_SPLIT_KEEP stack words}; unconditional 16-byte loads, the entries beyond sp are never popped (k_shadow4s)
+                        const uint4 *rec = recs + (size_t)((blk << 6) + pos + rank) * 4;
+                        const uint4 h = rec[0], a = rec[1], b = rec[2], c = rec[3];
+                        stk.base = 0;
+                        stk.slot(0) = h.z; stk.slot(1) = h.w;
+                        stk.slot(2) = a.x; stk.slot(3) = a.y; stk.slot(4) = a.z; stk.slot(5) = a.w;
+                        stk.slot(6) = b.x; stk.slot(7) = b.y; stk.slot(8) = b.z; stk.slot(9) = b.w;
+                        stk.slot(10) = c.x; stk.slot(11) = c.y; stk.slot(12) = c.z; stk.slot(13) = c.w;
+                        sp = (int)h.y;
+                    }
                     r.setup(ld3(o4), ld3(d4), sc.wideClamp);
                     tbest = ANY_HIT ? o4.w : FLX_FLT_MAX;                // shadow: shadowRayLen
                     ubest = 0.0f; vbest = 0.0f; tribest = -1; occluded = false;
-                    sp = 0; stk.base = 0; cur = sc.wrootRef;
+                    if (RESUME) cur = stk.pop(sp);                       // the node the ray stood on when it suspended
+                    else { sp = 0; stk.base = 0; cur = sc.wrootRef; }
                 }
                 pos += min(nIdle, avail);
                 if (pos >= blkLen) {
-                    blk = resolve(nextTicket); pos = 0;
-                    if (blk < nblk) { nextTicket = issue_fetch(); gidBlk = queue[min((blk << 6) + threadIdx.x, qlen - 1u)]; }
+                    blk = RESUME ? blk + rStep : resolve(nextTicket); pos = 0;
+                    if (blk < nblk) { if (!RESUME) nextTicket = issue_fetch(); gidBlk = block_ids(blk); }
                 }
             } else if (nIdle == 64u) break;
         }
@@ -182,6 +223,19 @@ __global__ __launch_bounds__(WIDE_BLOCK, WIDE_R_MIN_WAVES) void k_trace4r(State 
 #ifdef FLX_LAB_RSTATS
     if (ANY_HIT == false && rstats && threadIdx.x == 0) for (int k = 0; k < 4; k++) atomicAdd(&rstats[18 + k], acc[k]);
 #endif
+}
+
+template <bool ANY_HIT, int ANY_ORDER>
+__global__ __launch_bounds__(WIDE_BLOCK, WIDE_R_MIN_WAVES) void k_trace4r(State st, Queues qs, Scene sc, flx_render_params p, TraceAux aux, int refillMin, int waitMax, uint32_t *cursor)
+{
+    trace4r_waves<ANY_HIT, ANY_ORDER, false>(st, qs, sc, p, aux, refillMin, waitMax, cursor, ResumeAux{nullptr, nullptr, 0u, 0u});
+}
+
+// the suspended rays of the budgeted any-hit pass, finished in persistent waves that refill from the continuation records (RESUME, above)
+template <int ANY_ORDER>
+__global__ __launch_bounds__(WIDE_BLOCK, WIDE_R_MIN_WAVES) void k_trace4r_resume(State st, Queues qs, Scene sc, flx_render_params p, TraceAux aux, int refillMin, int waitMax, ResumeAux ra)
+{
+    trace4r_waves<true, ANY_ORDER, true>(st, qs, sc, p, aux, refillMin, waitMax, nullptr, ra);
 }
 
 // The commit of traceExtension for every path whose hit record is still raw (flx_trace.h: RAW HIT RECORDS): what k_logic<FUSE, RAW> does in
@@ -301,6 +355,27 @@ void launch_shadow4r(hipStream_t s,const State &st, const Queues &qs, const Scen
         hipLaunchKernelGGL((k_trace4r<true, 0>), dim3(grid), dim3(WIDE_BLOCK), 0, s, st, qs, sc, p, aux, refillMin, waitMax, cursor);
     }
     if (p.useAreaLight) hipLaunchKernelGGL(k_lightfix4, dim3(numCUs * 8), dim3(256), 0, s, st, qs, p);
+}
+
+// The second half of the split any-hit launch (trace4.hip: launch_shadow4_split): finishes the rays whose records lie in `rec` (FLX_SPLIT_LISTS sub-lists of
+// subCap slots, `limit` of them usable, counts in `count`).  The area-light quad was tested by the pass that suspended them.  refillMin 16, waitMax 32: the
+// closest-hit kernel's values (its rays are the comparable population: tens of rounds each).
+// Grid: the resident waves, but never fewer than one wave per sub-list -- a wave serves ONE list.  The waves that find work are those of the non-empty
+// lists, which are the lists of pass-1 blocks, so their stack columns stay inside the spill area's numTasks lanes even when the grid is padded to the lists.
+void launch_shadow4_resume(hipStream_t s, const State &st, const Queues &qs, const Scene &sc, const flx_render_params &p, uint32_t *spill, uint32_t numCUs,
+                           const uint32_t *count, const uint4 *rec, uint32_t subCap, uint32_t limit)
+{
+    static int occ[2] = {0, 0};
+    TraceAux aux{spill, ((st.numTasks + 255u) / 256u) * 256u, nullptr};
+    const ResumeAux ra{count, rec, subCap, limit};
+    const int refillMin = 16, waitMax = 32;
+    if (p.useEnvMap && !p.useAreaLight) {
+        const uint32_t grid = max(persistent_grid(k_trace4r_resume<1>, occ[1], numCUs, st.numTasks), (uint32_t)FLX_SPLIT_LISTS);
+        hipLaunchKernelGGL((k_trace4r_resume<1>), dim3(grid), dim3(WIDE_BLOCK), 0, s, st, qs, sc, p, aux, refillMin, waitMax, ra);
+    } else {
+        const uint32_t grid = max(persistent_grid(k_trace4r_resume<0>, occ[0], numCUs, st.numTasks), (uint32_t)FLX_SPLIT_LISTS);
+        hipLaunchKernelGGL((k_trace4r_resume<0>), dim3(grid), dim3(WIDE_BLOCK), 0, s, st, qs, sc, p, aux, refillMin, waitMax, ra);
+    }
 }
 
 } // namespace flxd

@@ -482,6 +482,23 @@ int flx_set_counters(flx_ctx *ctx, const void *in32);
  *                     could observe a hit record is made -- no call sees a raw one
  *   refill_shadow     the same for the any-hit query; -1 (default) = 0: two persistent kernels cannot share the machine, so the any-hit
  *                     kernel stays thread-per-ray and fills the slots the persistent closest-hit kernel's waves leave (api.hip: pickSchedule)
+ *   shadow_split      the thread-per-ray any-hit query as a SPLIT launch (csrc/trace4.hip: k_shadow4s): value = K | K2 << 8.  A pass over
+ *                     the shadow queue gives every ray K node visits; a ray that is not done by then parks {queue position, stack} in a 64-byte
+ *                     continuation record and frees its lane.  K2 == 0: the suspended rays are then finished by persistent waves that refill
+ *                     their lanes from the records (csrc/trace4r.hip: k_trace4r_resume; see shadow_resume).  K2 > 0: a second thread-per-record
+ *                     pass with budget K2 and a third without.  0 = off (k_shadow4) | -1 (default) = the library's choice, made at every launch
+ *                     from the render parameters: K = 8 when every shadow ray runs toward the environment light (useEnvMap && !useAreaLight), else
+ *                     0.  An explicit value holds, 0 included; flx_get_option returns what flx_wf_shadow will really launch: 0 also under
+ *                     refill_shadow, shadow_tree 2, a scene without a usable wide tree and the trace statistics.  Bit-identical results.  The
+ *                     records are allocated when the choice first becomes non-zero -- in flx_set_params, flx_upload_scene or this option, not in a
+ *                     launch call -- and kept: 32 B per path (numTasks / 2 records; ~540 MB at 16 M paths), plus 8 B per path for the second set
+ *                     once a K2 > 0 is used.  When the library's own choice does not fit it becomes 0 for the context (shadow_split_fallback); an
+ *                     explicit value that does not fit fails the call
+ *   shadow_split_fallback   read-only: 1 when the records of the library's own choice did not fit into device memory and the choice is 0 for this context
+ *   shadow_resume     1 (default) | 0: with 0 the suspended rays of a split launch without K2 are finished one lane per record slot (the round-5
+ *                     pass 2); for A/B and tests
+ *   shadow_split_limit      test hook: use only this many record slots per sub-list (0 = all); rays that find their list full finish in the first pass
+ *   shadow_split_suspended  read-only: the number of rays the last split launch suspended in its first pass (0 before the first one); waits for the stream
  *   fuse              1 (default): flx_wf_logic is DEFERRED -- launched by the next call on this context; when that call is
  *                     flx_wf_materials (a flx_wf_raygen between the two is deferred along and launched right after), logic and the
  *                     material step of the most common BSDF types run as ONE pass over the path state (logic.hip: k_logic<FUSED>),
